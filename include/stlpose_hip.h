@@ -221,10 +221,6 @@ typedef struct stl_wprep { /* one conv weight: OIHW fp32 master -> kernel layout
 } stl_wprep;
 int stl_weight_prep(int dtype, const float* master, void* wk, const stl_wprep* tab, int n,
                     int nblocks, void* stream);
-/* The same over a sub-range of the table: `tab` points at the first entry of the range, blk_base is
- * that entry's blk0.  Used per gradient bucket, right after the bucket's optimiser slice. */
-int stl_weight_prep_range(int dtype, const float* master, void* wk, const stl_wprep* tab, int n,
-                          int blk_base, int nblocks, void* stream);
 
 typedef struct stl_slab { /* one wgrad result: sum partial[s] -> grad (OIHW fp32) */
     int64_t part_off; /* element offset into `partials`; a multiple of 4 (16-byte aligned) when Ci % 4 == 0 */
@@ -264,14 +260,6 @@ int stl_adam_step(float* p, const float* g, float* m, float* v, int64_t n, const
                   int32_t* step, const int32_t* overflow /* or NULL */, void* stream);
 int stl_sgd_step(float* p, const float* g, float* mom, int64_t n, const float* hyper, int32_t* step,
                  const int32_t* overflow /* or NULL */, void* stream);
-/* Per-bucket form: stl_optim_begin_step increments `step` once, the *_slice calls then update any
- * contiguous slices of the flat buffers (pointers already offset) with that step count -- the
- * optimiser of a gradient bucket runs as soon as the bucket is final, overlapped with backward. */
-int stl_optim_begin_step(int32_t* step, const int32_t* overflow /* or NULL */, void* stream);
-int stl_adam_slice(float* p, const float* g, float* m, float* v, int64_t n, const float* hyper,
-                   const int32_t* step, void* stream);
-int stl_sgd_slice(float* p, const float* g, float* mom, int64_t n, const float* hyper, const int32_t* step,
-                  void* stream);
 
 /* Device affine crop + normalisation of a batch (reference data/JointsDataset.py:189-200: cv2.warpAffine(img,
  * get_affine_transform(c, s, r, image_size), INTER_LINEAR) followed by ToTensor + Normalize, data_loaders.py:59-61).
@@ -311,8 +299,7 @@ int stl_nhwc_to_nchw(int dtype, const void* in, float* out, int B, int C, int H,
 #define STL_OP_REDUCE_RANGE 8 /* stl_reduce_slabs over a sub-range of the table (a gradient bucket) */
 #define STL_OP_BN_GRADS_RANGE 9 /* stl_bn_param_grads over a sub-range of the table */
 #define STL_OP_WGRAD_GROUP 10   /* stl_conv_wgrad_group */
-#define STL_OP_OPTIM_SLICE 11   /* stl_adam_slice / stl_sgd_slice of a gradient bucket, behind its reductions */
-#define STL_OP_WPREP_RANGE 12   /* stl_weight_prep_range of the bucket's convolutions (the NEXT step's kernel-layout weights) */
+/* 11 and 12 are retired (the in-program optimiser and weight re-layout): not reused */
 /* A gradient bucket = a contiguous slice of the flat gradient buffer whose weight-gradient slabs and
  * BatchNorm reductions are complete at some point of the backward program.  Reducing it there (and
  * recording an event) lets the data-parallel all-reduce of that slice start while the rest of
@@ -320,11 +307,6 @@ int stl_nhwc_to_nchw(int dtype, const void* in, float* out, int B, int C, int H,
 typedef struct stl_reduce_range { const float* partials; float* grads; const stl_slab* tab; int32_t n, blk_base, nblocks, pad_; } stl_reduce_range;
 typedef struct stl_bn_range { const double* rstats; float* grads; const stl_bnrec* tab; int32_t n, pad_; } stl_bn_range;
 int stl_reduce_slabs_range(const stl_reduce_range* r, void* stream);
-/* Optimiser of one gradient bucket as a program op (single-process training: with data parallelism the collective sits
- * between a bucket's reduction and its optimiser, and the host issues the slices, see train_step.py).  kind 0 = Adam,
- * 1 = SGD (v unused).  Reference: optimizer.step() after loss.backward(), 02_train.py:113-114. */
-typedef struct stl_optim_slice { int32_t kind, pad_; float* p; const float* g; float* m; float* v; int64_t n; const float* hyper; const int32_t* step; } stl_optim_slice;
-typedef struct stl_wprep_range { int32_t dtype /* STL_DT2(data-gradient layouts, forward layouts) */, n, blk_base, nblocks; const float* master; void* wk; const stl_wprep* tab; } stl_wprep_range;
 typedef struct stl_patch { int32_t dtype, B, H, W, stride, pad_; const float* img; void* out; const float* mean3; const float* std3; } stl_patch;
 typedef struct stl_head { int32_t dtype, B, H, W, Ci, J; const void* x; const float* w; const float* bias; float* out; } stl_head;
 typedef struct stl_head_bwd { int32_t dtype /* STL_DT2(dx, x) */, B, H, W, Ci, J, nblk, pad_; const void* x; const float* w; const float* dout; void* dx; float* partial; } stl_head_bwd;
@@ -342,13 +324,6 @@ int stl_program_run(void* program, void* const* streams /* hipStream_t[nstreams]
  * bucket by bucket and enqueues each bucket's all-reduce between two ranges, i.e. right behind the bucket in every in-order queue. */
 int stl_program_run_range(void* program, void* const* streams, int first, int last);
 int stl_program_destroy(void* program);
-/* The same program as ONE explicit HIP graph: stl_program_graph_build records every op's kernel launches (nothing runs) and
- * adds them as kernel nodes with the program's dependencies (in-order streams + waits) -- built, not captured, because stream
- * capture of a plan that forks onto three or more streams crashes in hipStreamEndCapture on ROCm 7.2; stl_program_graph_launch
- * replays it on `stream`.  No events exist in this mode: stl_program_wait_op (the data-parallel bucket pick-up) needs
- * stl_program_run. */
-int stl_program_graph_build(void* program);
-int stl_program_graph_launch(void* program, void* stream);
 /* Make `stream` wait for op `op` (which must record) of the LAST run of the program: how a
  * communication stream picks up a finished gradient bucket. */
 int stl_program_wait_op(void* program, int op, void* stream);

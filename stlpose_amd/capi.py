@@ -109,18 +109,9 @@ class BNRange(C.Structure):
     _fields_ = [("rstats", vp), ("grads", vp), ("tab", vp), ("n", i32), ("pad_", i32)]
 
 
-class OptimSlice(C.Structure):   # stl_optim_slice
-    _fields_ = [("kind", i32), ("pad_", i32), ("p", vp), ("g", vp), ("m", vp), ("v", vp), ("n", C.c_int64), ("hyper", vp), ("step", vp)]
-
-
-class WPrepRange(C.Structure):   # stl_wprep_range
-    _fields_ = [("dtype", i32), ("n", i32), ("blk_base", i32), ("nblocks", i32), ("master", vp), ("wk", vp), ("tab", vp)]
-
-
 OP_KIND = {"stl_conv_forward": 0, "stl_conv_wgrad": 1, "stl_fuse_forward": 2, "stl_fuse_backward": 3,
            "stl_upsample_backward": 4, "stl_patch3x3": 5, "stl_head_forward": 6, "stl_head_backward": 7,
-           "stl_reduce_slabs_range": 8, "stl_bn_grads_range": 9, "stl_conv_wgrad_group": 10,
-           "stl_optim_slice": 11, "stl_wprep_range": 12}   # the last two exist as program ops only
+           "stl_reduce_slabs_range": 8, "stl_bn_grads_range": 9, "stl_conv_wgrad_group": 10}   # 11, 12: retired, not reused
 
 # name -> argtypes (restype is always int unless noted); every symbol include/stlpose_hip.h declares
 SIGNATURES = {
@@ -142,10 +133,6 @@ SIGNATURES = {
     "stl_flip_merge": [vp, vp, vp, vp, i32, i32, i32, i32, vp],
     "stl_final_preds": [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp],
     "stl_weight_prep": [i32, vp, vp, vp, i32, i32, vp],
-    "stl_weight_prep_range": [i32, vp, vp, vp, i32, i32, i32, vp],
-    "stl_optim_begin_step": [vp, vp, vp],
-    "stl_adam_slice": [vp, vp, vp, vp, i64, vp, vp, vp],
-    "stl_sgd_slice": [vp, vp, vp, i64, vp, vp, vp],
     "stl_reduce_slabs": [vp, vp, vp, i32, i32, vp],
     "stl_reduce_slabs_range": [C.POINTER(ReduceRange), vp],
     "stl_bn_running_update": [vp, vp, vp, vp, i32, f32, vp, vp],
@@ -165,8 +152,6 @@ SIGNATURES = {
     "stl_program_run_range": [vp, C.POINTER(vp), i32, i32],
     "stl_program_destroy": [vp],
     "stl_program_wait_op": [vp, i32, vp],
-    "stl_program_graph_build": [vp],
-    "stl_program_graph_launch": [vp, vp],
     "stl_selftest_mfma": [vp, vp],
     "stl_version": [],
 }

@@ -1320,25 +1320,19 @@ extern "C" int stl_flip_merge(const float* a, const float* bflip, float* out, co
 }
 
 extern "C" int stl_weight_prep(int dtype2, const float* master, void* wk, const stl_wprep* tab, int n, int nblocks, void* stream) {
-    if (n == 0) return 0;
-    return stl_weight_prep_range(dtype2, master, wk, tab, n, 0, nblocks, stream);
-}
-
-extern "C" int stl_weight_prep_range(int dtype2, const float* master, void* wk, const stl_wprep* tab, int n, int blk_base, int nblocks,
-                                     void* stream) {
     if (n == 0 || nblocks == 0) return 0;
-    STL_CHECK(master && wk && tab && n > 0 && blk_base >= 0 && nblocks > 0, "weight_prep_range: bad arguments");
+    STL_CHECK(master && wk && tab && n > 0 && nblocks > 0, "weight_prep: bad arguments");
     const int dtype = dtype2 & 0xff, fdtype = (dtype2 >> 8) & 0xff;   // STL_DT2(type of the data-gradient layouts, type of the forward layouts)
     STL_CHECK(fdtype == 0 || fdtype == dtype || (dtype == STL_BF16 && fdtype == STL_F16), "weight_prep: forward type %d does not go with %d", fdtype, dtype);
     if (dtype == STL_BF16 && fdtype == STL_F16)
-        STL_LAUNCH((weight_prep_kernel<__bf16, f16>), dim3(nblocks), dim3(256), 0, ST, master, (__bf16*)wk, tab, n, blk_base);
+        STL_LAUNCH((weight_prep_kernel<__bf16, f16>), dim3(nblocks), dim3(256), 0, ST, master, (__bf16*)wk, tab, n, 0);
     else if (dtype == STL_F16)
-        STL_LAUNCH((weight_prep_kernel<f16, f16>), dim3(nblocks), dim3(256), 0, ST, master, (f16*)wk, tab, n, blk_base);
+        STL_LAUNCH((weight_prep_kernel<f16, f16>), dim3(nblocks), dim3(256), 0, ST, master, (f16*)wk, tab, n, 0);
     else if (dtype == STL_BF16)
-        STL_LAUNCH(weight_prep_kernel<__bf16>, dim3(nblocks), dim3(256), 0, ST, master, (__bf16*)wk, tab, n, blk_base);
+        STL_LAUNCH(weight_prep_kernel<__bf16>, dim3(nblocks), dim3(256), 0, ST, master, (__bf16*)wk, tab, n, 0);
     else
-        STL_LAUNCH(weight_prep_kernel<float>, dim3(nblocks), dim3(256), 0, ST, master, (float*)wk, tab, n, blk_base);
-    STL_LAUNCH_CHECK("weight_prep_range");
+        STL_LAUNCH(weight_prep_kernel<float>, dim3(nblocks), dim3(256), 0, ST, master, (float*)wk, tab, n, 0);
+    STL_LAUNCH_CHECK("weight_prep");
     return 0;
 }
 
@@ -1384,26 +1378,6 @@ extern "C" int stl_sgd_step(float* p, const float* g, float* mom, int64_t n, con
     STL_LAUNCH(inc_step_kernel, dim3(1), dim3(1), 0, ST, step, overflow);
     STL_LAUNCH(sgd_kernel, dim3(nblocks_for((size_t)n, 256, 4096)), dim3(256), 0, ST, p, g, mom, n, hyper, step);
     STL_LAUNCH_CHECK("sgd_step");
-    return 0;
-}
-
-extern "C" int stl_optim_begin_step(int32_t* step, const int32_t* overflow, void* stream) {
-    STL_LAUNCH(inc_step_kernel, dim3(1), dim3(1), 0, ST, step, overflow);
-    STL_LAUNCH_CHECK("optim_begin_step");
-    return 0;
-}
-
-extern "C" int stl_adam_slice(float* p, const float* g, float* m, float* v, int64_t n, const float* hyper, const int32_t* step, void* stream) {
-    if (n <= 0) return 0;
-    STL_LAUNCH(adam_kernel, dim3(nblocks_for((size_t)n, 256, 4096)), dim3(256), 0, ST, p, g, m, v, n, hyper, step);
-    STL_LAUNCH_CHECK("adam_slice");
-    return 0;
-}
-
-extern "C" int stl_sgd_slice(float* p, const float* g, float* mom, int64_t n, const float* hyper, const int32_t* step, void* stream) {
-    if (n <= 0) return 0;
-    STL_LAUNCH(sgd_kernel, dim3(nblocks_for((size_t)n, 256, 4096)), dim3(256), 0, ST, p, g, mom, n, hyper, step);
-    STL_LAUNCH_CHECK("sgd_slice");
     return 0;
 }
 

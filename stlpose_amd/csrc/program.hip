@@ -14,11 +14,6 @@ struct Program {
     hipEvent_t fork = nullptr;
     std::vector<hipEvent_t> join;
     int nstreams = 1;
-    // explicit HIP graph of the program (stl_program_graph_build): one kernel node per recorded launch
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t exec = nullptr;
-    std::vector<StlLaunchRec> recs;   // own the argument copies the kernel nodes point at
-    int nnodes = 0;
 };
 }  // namespace
 
@@ -39,7 +34,7 @@ static unsigned event_flags() {
     return hipEventDisableTiming | hipEventDisableSystemFence;
 }
 
-// one op of a program on stream `st` (also what the graph builder calls, with the launch recorder set)
+// one op of a program on stream `st`
 static int run_op(const stl_op& o, void* st, int i) {
     int rc;
         switch (o.kind) {
@@ -62,17 +57,6 @@ static int run_op(const stl_op& o, void* st, int i) {
             case STL_OP_HEAD_BWD: {
                 const stl_head_bwd* a = static_cast<const stl_head_bwd*>(o.desc);
                 rc = stl_head_backward(a->dtype, a->x, a->w, a->dout, a->dx, a->partial, a->nblk, a->B, a->H, a->W, a->Ci, a->J, st);
-                break;
-            }
-            case STL_OP_OPTIM_SLICE: {
-                const stl_optim_slice* a = static_cast<const stl_optim_slice*>(o.desc);
-                rc = a->kind == 0 ? stl_adam_slice(a->p, a->g, a->m, a->v, a->n, a->hyper, a->step, st)
-                                  : stl_sgd_slice(a->p, a->g, a->m, a->n, a->hyper, a->step, st);
-                break;
-            }
-            case STL_OP_WPREP_RANGE: {
-                const stl_wprep_range* a = static_cast<const stl_wprep_range*>(o.desc);
-                rc = stl_weight_prep_range(a->dtype, a->master, a->wk, a->tab, a->n, a->blk_base, a->nblocks, st);
                 break;
             }
             case STL_OP_REDUCE_RANGE: rc = stl_reduce_slabs_range(static_cast<const stl_reduce_range*>(o.desc), st); break;
@@ -127,12 +111,6 @@ extern "C" int stl_program_destroy(void* h) {
     if (!p) return 0;
     for (hipEvent_t e : p->ev) (void)hipEventDestroy(e);
     for (hipEvent_t e : p->join) (void)hipEventDestroy(e);
-    if (p->exec) (void)hipGraphExecDestroy(p->exec);
-    if (p->graph) (void)hipGraphDestroy(p->graph);
-    for (StlLaunchRec& r : p->recs) {
-        r.del(r.args_owner);
-        delete[] r.params;
-    }
     if (p->fork) (void)hipEventDestroy(p->fork);
     delete p;
     return 0;
@@ -186,90 +164,3 @@ extern "C" int stl_program_run(void* h, void* const* streams) {
     return stl_program_run_range(h, streams, 0, (int)p->ops.size());
 }
 
-// ---- explicit HIP graph: the planner already knows every launch and every dependency, so the graph is
-// BUILT (hipGraphAddKernelNode + dependency lists), not captured -- stream capture of a plan that forks onto >= 3 streams
-// crashes inside hipStreamEndCapture on ROCm 7.2.  Every op is executed once with the launch recorder set (common.cuh,
-// STL_LAUNCH): its kernels become nodes, ONE chain in issue order.  Issue order honours every stream order and every wait (an op
-// only waits on earlier ops), so the chain keeps all of the planner's dependencies; it gives up their concurrency because
-// ROCm 7.2 segfaults inside hipGraphLaunch on a graph with parallel branches (its multi-stream launch path) when the process
-// has two hardware queues.
-// a failed build leaves nothing behind: a retry starts from an empty graph and leaks neither nodes nor argument copies
-static void graph_discard(Program* p) {
-    if (p->graph) (void)hipGraphDestroy(p->graph);
-    p->graph = nullptr;
-    for (StlLaunchRec& r : p->recs) {
-        r.del(r.args_owner);
-        delete[] r.params;
-    }
-    p->recs.clear();
-    p->nnodes = 0;
-}
-
-extern "C" int stl_program_graph_build(void* h) {
-    Program* p = static_cast<Program*>(h);
-    STL_CHECK(p, "program_graph_build: null program");
-    if (p->exec) return 0;
-    const int n = (int)p->ops.size();
-    STL_CHECK(hipGraphCreate(&p->graph, 0) == hipSuccess, "program_graph_build: hipGraphCreate failed");
-    hipGraphNode_t last = nullptr;
-    for (int i = 0; i < n; ++i) {
-        const stl_op& o = p->ops[i];
-        StlRecorder rec{nullptr, 0, 0};
-        g_stl_recorder = &rec;
-        const int rc = run_op(o, nullptr, i);
-        g_stl_recorder = nullptr;
-        // the program owns every recorded argument copy from here on (graph_discard / stl_program_destroy release them)
-        const size_t first_rec = p->recs.size();
-        for (int k = 0; k < rec.n; ++k) p->recs.push_back(rec.recs[k]);
-        delete[] rec.recs;
-        if (rc != 0) {
-            graph_discard(p);
-            return rc;
-        }
-        std::vector<hipGraphNode_t> deps;
-        if (last) deps.push_back(last);
-        hipGraphNode_t prev = nullptr;
-        for (size_t k = first_rec; k < p->recs.size(); ++k) {
-            const StlLaunchRec& r = p->recs[k];
-            hipKernelNodeParams kp;
-            memset(&kp, 0, sizeof(kp));
-            kp.func = const_cast<void*>(r.func);
-            kp.gridDim = r.grid, kp.blockDim = r.block;
-            kp.sharedMemBytes = (unsigned)r.lds;
-            kp.kernelParams = r.params;
-            kp.extra = nullptr;
-            hipGraphNode_t node = nullptr;
-            hipError_t e = prev ? hipGraphAddKernelNode(&node, p->graph, &prev, 1, &kp)
-                                : hipGraphAddKernelNode(&node, p->graph, deps.empty() ? nullptr : deps.data(), deps.size(), &kp);
-            if (e != hipSuccess) {
-                graph_discard(p);
-                return stl_set_error("program_graph_build: hipGraphAddKernelNode failed for op %d (%s)", i, hipGetErrorString(e));
-            }
-            prev = node;
-            ++p->nnodes;
-        }
-        if (!prev) {
-            // an op without a launch: an empty node keeps the chain in issue order
-            if (hipGraphAddEmptyNode(&prev, p->graph, deps.empty() ? nullptr : deps.data(), deps.size()) != hipSuccess) {
-                graph_discard(p);
-                return stl_set_error("program_graph_build: hipGraphAddEmptyNode failed for op %d", i);
-            }
-            ++p->nnodes;
-        }
-        last = prev;
-    }
-    hipError_t e = hipGraphInstantiate(&p->exec, p->graph, nullptr, nullptr, 0);
-    if (e != hipSuccess) {
-        graph_discard(p);
-        return stl_set_error("program_graph_build: hipGraphInstantiate failed (%s)", hipGetErrorString(e));
-    }
-    return 0;
-}
-
-extern "C" int stl_program_graph_launch(void* h, void* stream) {
-    Program* p = static_cast<Program*>(h);
-    STL_CHECK(p && p->exec, "program_graph_launch: the program has no graph (stl_program_graph_build)");
-    hipError_t e = hipGraphLaunch(p->exec, (hipStream_t)stream);
-    STL_CHECK(e == hipSuccess, "program_graph_launch: %s", hipGetErrorString(e));
-    return 0;
-}

@@ -192,13 +192,6 @@ class Engine:
         # the 64-channel 3x3 blocks (16 waves, one per CU: 256 per launch): eight layers per launch keep the split-K slabs at the
         # 32-channel kernel's size (a slab is the whole [Co][9][Ci] filter bank; 256 blocks over four layers would double them)
         self.wgrad_group_wide = int(env("STLPOSE_WGRAD_GROUP_WIDE", "8"))
-        self.skip_wgrad = env("STLPOSE_SKIP_WGRAD", "0") != "0"   # calibration only (wrong numerics): no weight-gradient launches
-        # STLPOSE_GRAPH=1: replay each program as ONE explicit HIP graph (csrc/program.hip: kernel nodes chained in issue order)
-        # instead of launches and events on four streams
-        # Replay as ONE explicit HIP graph (stl_program_graph_build) instead of launches + events: slower for training plans (16.78 vs
-        # 14.53 ms per step, round 4) and for inference plans (4.37 vs 4.20 ms per W32 384x288 bs 32 forward, round 5) -- opt-in.
-        self.graph_mode = env("STLPOSE_GRAPH", "0") != "0"
-        self._graphs = set()
         self._poison = env("STLPOSE_POISON", "0") != "0"          # debug: planned buffers start as NaNs (see _alloc)
         self._stream = 0
         self._side = None
@@ -380,10 +373,8 @@ class Engine:
             e.Co, e.Ci, e.ks, e.Cip, e.patch, e.blk0 = c.Co, c.Ci, c.ks, c.Cik, int(c.patch), blk
             blk += math.ceil(c.Co * c.Ci * c.ks * c.ks / 1024)
         self._wprep_blocks = blk
-        self._wprep_blk0 = [tab[i].blk0 for i in range(len(self.convs))] + [blk]
         self._wprep_tab = _to_device(tab, self.dev)
         self._wprep_n = len(self.convs)
-        self.weights_ready = False   # set by a caller that has already run prep_weights_range for every bucket
 
     def _active_of(self, key: str) -> int:
         """Branch chains in flight around the layer `key` (its stage's branch count)."""
@@ -411,7 +402,7 @@ class Engine:
         # program, so the step has no serial tail, and an event a data-parallel all-reduce can wait on.
         self.buckets: List[dict] = []
         bucket_min = int(self.bucket_mb * (1 << 20) / 4)
-        bk = dict(done=0, lo=st.nparam, hi=st.nparam, slab0=0, reads=[], strm=0, wuse=[])
+        bk = dict(done=0, lo=st.nparam, hi=st.nparam, slab0=0, reads=[], strm=0)
         # The serial tail of backward (layer1 + stem: one branch, 113 MB tensors) finishes last.  Close a bucket
         # where it begins, whatever its size, so that the final slab reduction (the only work left after the last
         # weight gradient, in front of the optimiser) covers just the stem / layer1 slabs instead of every layer
@@ -433,13 +424,13 @@ class Engine:
             for key in list(self._wg_pending):                     # the bucket's slab reduction reads every member's slabs
                 self._flush_wgrad_group(ops, key)
             rr, br = capi.ReduceRange(), capi.BNRange()
-            b = dict(lo=bk["lo"], hi=bk["hi"], slab0=bk["slab0"], slab1=len(self.slabs), rr=rr, br=br, wuse=list(bk["wuse"]))
+            b = dict(lo=bk["lo"], hi=bk["hi"], slab0=bk["slab0"], slab1=len(self.slabs), rr=rr, br=br)
             wstrm = bk["strm"]
             ops.append(("stl_reduce_slabs_range", rr, wstrm, list(bk["reads"]), [("bucket", len(self.buckets))]))
             ops.append(("stl_bn_grads_range", br, wstrm, [("bucket", len(self.buckets))], [("bucketbn", len(self.buckets))]))
             b["op"] = len(ops) - 1
             self.buckets.append(b)
-            bk.update(done=0, hi=bk["lo"], slab0=len(self.slabs), reads=[], wuse=[])
+            bk.update(done=0, hi=bk["lo"], slab0=len(self.slabs), reads=[])
         self._nactive: Dict[int, int] = {}   # id(desc) -> branch streams busy with the data-gradient chain around that op
         cur_active = self.nstreams
 
@@ -569,10 +560,7 @@ class Engine:
                     d.mask_bn = self._src(x)
                     d.red = self.rstats.data_ptr() + 8 * x.bn.stats_off
                 d.out = out.data_ptr()
-                # ("wuse", layer): this launch is the last reader of the layer's kernel-layout weights and BatchNorm
-                # parameters in the step -- what an in-program optimiser / weight re-layout of the bucket waits for
-                ops.append(("stl_conv_forward", d, strm, dreads, [out.data_ptr(), ("wuse", ci.master_off)]))
-                bk["wuse"].append(("wuse", ci.master_off))
+                ops.append(("stl_conv_forward", d, strm, dreads, [out.data_ptr()]))
         bucket_close(force=True)
         for o in ops[n_before:]:
             self._nactive.setdefault(id(o[1]), cur_active)
@@ -684,7 +672,7 @@ class Engine:
         # tail launches are not grouped (round 3, groups of 4 / 2 / 1: 15.02 / 14.81 / 14.82 ms per step).
         tail = self._active_of(ci.key) == 1
         gmax = self.wgrad_group_wide if wide3 else self.wgrad_group
-        gsize = 1 if (tail or self.skip_wgrad) else max(1, min(gmax, capi.WGRAD_GROUP_MAX, max(1, budget // chunks)))
+        gsize = 1 if tail else max(1, min(gmax, capi.WGRAD_GROUP_MAX, max(1, budget // chunks)))
         # Grouped launches (stl_conv_wgrad_group): weight gradients of one shape -- the 3x3 convolutions of a branch --
         # wait until `gsize` of them are ready and go out as ONE launch that shares the block budget: the four hardware
         # queues carry one off-chain launch instead of gsize (in stages 3 / 4 every queue is busy with a data-gradient
@@ -702,8 +690,6 @@ class Engine:
                                ks=ci.ks, Cip=ci.Cik, patch=int(ci.patch), stride=0, struct=wg))
         bk["reads"].append(id(wg))
         bk["strm"] = strm
-        if self.skip_wgrad:
-            return
         if gsize == 1:
             ops.append(("stl_conv_wgrad", wg, strm, [y.dt.data_ptr(), x.ptr], [id(wg)]))
             return
@@ -797,12 +783,6 @@ class Engine:
         exchange module (and, in backward, the weight gradients) run concurrently; fork/join and
         cross-stream dependencies are HIP events inside stl_program_run."""
         h = self._program(ops)
-        if self.graph_mode:
-            if id(ops) not in self._graphs:
-                capi.call("stl_program_graph_build", h)
-                self._graphs.add(id(ops))
-            capi.call("stl_program_graph_launch", h, stream)
-            return
         if self._side is None:
             self._make_streams()
         self._stream_arr[0] = stream
@@ -834,27 +814,10 @@ class Engine:
         capi.call("stl_weight_prep", capi.dt2(self.dtype, self.fdtype), st.master.data_ptr(), self.wk.data_ptr(), self._wprep_tab.data_ptr(),
                   self._wprep_n, self._wprep_blocks, stream)
 
-    def prep_weights_range(self, i: int, stream: int):
-        """weights -> kernel layout for the convolutions whose parameters lie in gradient bucket i."""
-        b = self.buckets[i]
-        if "conv0" not in b:
-            import bisect
-            offs = [c.master_off for c in self.convs]          # forward order == ascending offset
-            assert offs == sorted(offs)
-            b["conv0"], b["conv1"] = bisect.bisect_left(offs, b["lo"]), bisect.bisect_left(offs, b["hi"])
-        i0, i1 = b["conv0"], b["conv1"]
-        if i1 > i0:
-            st = self.store
-            capi.call("stl_weight_prep_range", capi.dt2(self.dtype, self.fdtype), st.master.data_ptr(), self.wk.data_ptr(),
-                      self._wprep_tab.data_ptr() + i0 * C.sizeof(capi.WPrep), i1 - i0, self._wprep_blk0[i0],
-                      self._wprep_blk0[i1] - self._wprep_blk0[i0], stream)
-
     def forward(self, stream: int, update_running: bool = True):
         """weights -> kernel layout, zero statistics, forward program, running-stat update."""
         self.generation += 1   # every pass overwrites the plan's activations (hrnet._Fn stale-backward check)
-        if not self.weights_ready:
-            self.prep_weights(stream)
-        self.weights_ready = False
+        self.prep_weights(stream)
         if self.training:
             self.stats.zero_()
         self._run(self.fwd_ops, stream)
@@ -883,15 +846,14 @@ class Engine:
             "'mixed' mode are f16; for a checkpoint with badly scaled weights use compute_dtype='bf16' (same speed, bf16 range) "
             "or 'fp32'.")
 
-    def backward(self, stream: int, fused_optim: bool = False, on_bucket=None):
-        """expects self.dout filled; leaves dL/dparam in store.grads (overwrites).  fused_optim: the program of
-        attach_optimizer (optimiser + next step's weight layouts inside backward).  on_bucket(i): called on the host right after
+    def backward(self, stream: int, on_bucket=None):
+        """expects self.dout filled; leaves dL/dparam in store.grads (overwrites).  on_bucket(i): called on the host right after
         gradient bucket i's last op has been ENQUEUED (the program is issued range by range, stl_program_run_range): the
         data-parallel path enqueues the bucket's all-reduce there, so that in every in-order hardware queue it sits directly
         behind the bucket instead of behind the rest of backward."""
         assert self.training
         self.rstats.zero_()
-        if on_bucket is not None and not fused_optim and self.buckets:
+        if on_bucket is not None and self.buckets:
             h = self._program(self.bwd_ops)
             if self._side is None:
                 self._make_streams()
@@ -903,49 +865,7 @@ class Engine:
                 on_bucket(i)
             capi.call("stl_program_run_range", h, self._stream_arr, first, len(self.bwd_ops))
             return
-        self._run(self.bwd_ops_opt if fused_optim else self.bwd_ops, stream)   # includes the per-bucket slab reductions and BatchNorm gradients
-
-    def attach_optimizer(self, kind: int, p: int, g: int, m: int, v: int, hyper: int, step: int):
-        """Single-process training: the optimiser slice and the next step's kernel-layout weights of every gradient bucket
-        become ops of the backward program (``backward(stream, fused_optim=True)``), issued one bucket late on the stream
-        of that later bucket's reductions -- by then the data gradients that still read the bucket's weights / BatchNorm
-        parameters (the ("wuse", layer) tokens both ops wait for) have long finished.  The step then has no serial
-        optimiser (0.13 ms) and weight re-layout (0.10 ms at the start of the next forward) section; no fifth stream is
-        involved (a fifth active hardware queue is time-sliced).  kind: 0 Adam, 1 SGD."""
-        ops = list(self.bwd_ops)
-        at = sorted((b["op"], i) for i, b in enumerate(self.buckets))
-        self._optim_descs = []
-        new_ops, prev = [], None
-
-        def emit(i, strm):
-            b = self.buckets[i]
-            o = capi.OptimSlice()
-            lo, n = b["lo"], b["hi"] - b["lo"]
-            o.kind, o.p, o.g, o.m, o.v, o.n, o.hyper, o.step = kind, p + 4 * lo, g + 4 * lo, m + 4 * lo, (v + 4 * lo) if v else 0, n, hyper, step
-            new_ops.append(("stl_optim_slice", o, strm, [("bucketbn", i)] + b["wuse"], [("optim", i)]))
-            self._optim_descs.append(o)
-            if "conv0" not in b:
-                import bisect
-                offs = [c.master_off for c in self.convs]
-                b["conv0"], b["conv1"] = bisect.bisect_left(offs, b["lo"]), bisect.bisect_left(offs, b["hi"])
-            i0, i1 = b["conv0"], b["conv1"]
-            if i1 > i0:
-                w = capi.WPrepRange()
-                w.dtype, w.n, w.blk_base, w.nblocks = capi.dt2(self.dtype, self.fdtype), i1 - i0, self._wprep_blk0[i0], self._wprep_blk0[i1] - self._wprep_blk0[i0]
-                w.master, w.wk, w.tab = self.store.master.data_ptr(), self.wk.data_ptr(), self._wprep_tab.data_ptr() + i0 * C.sizeof(capi.WPrep)
-                new_ops.append(("stl_wprep_range", w, strm, [("optim", i)], [("wprep", i)]))
-                self._optim_descs.append(w)
-
-        nxt = dict(at)
-        for idx, op in enumerate(ops):
-            new_ops.append(op)
-            if idx in nxt:
-                if prev is not None:
-                    emit(prev, op[2])
-                prev = nxt[idx]
-        if prev is not None:
-            emit(prev, ops[self.buckets[prev]["op"]][2])
-        self.bwd_ops_opt = new_ops
+        self._run(self.bwd_ops, stream)   # includes the per-bucket slab reductions and BatchNorm gradients
 
     def bucket_wait(self, i: int, stream: int):
         """Make `stream` wait until gradient bucket i (self.buckets[i]: flat slice [lo, hi)) of the

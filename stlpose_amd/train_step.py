@@ -46,8 +46,6 @@ class TrainStep:
         self.dp = (FlatAllReduce(self.store.grads, process_group, bucket_mb, bounds=[(b["lo"], b["hi"]) for b in self.eng.buckets],
                                  bf16_buckets=bf16_buckets)
                    if process_group is not None else None)
-        if self.dp is not None:
-            self.eng.graph_mode = False   # the per-bucket all-reduce picks buckets up at the program's EVENTS (stl_program_wait_op)
         self._comm: Optional[torch.cuda.Stream] = None
         # per-bucket issue needs a collective that is a KERNEL on the communicator's stream (RCCL).  Decide by the backend serving
         # CUDA tensors: a default-initialised group reports e.g. "cpu:gloo,cuda:nccl" or "undefined" from get_backend()
@@ -92,14 +90,6 @@ class TrainStep:
         # replay, so the overlapped per-bucket all-reduce has nothing to wait on -- run eagerly instead
         if self.use_graph and process_group is not None:
             self.use_graph = False
-        # Single process, native replay: optimiser slices and the next step's weight layouts run as ops of the backward
-        # program (engine.attach_optimizer).  With a process group the collective sits between a bucket's reduction and
-        # its optimiser, so the host issues those (_allreduce / _optim).
-        self._fused_optim = (not self.use_graph and self.dp is None and os.environ.get("STLPOSE_FUSED_OPTIM", "0") != "0")   # measured neutral on one MI355X (14.93 vs 14.95 ms per step: the tail of backward it overlaps with is bandwidth-bound too): opt-in
-        if self._fused_optim:
-            self.eng.attach_optimizer(0 if optimizer == ADAM else 1, self.store.master.data_ptr(), self.store.grads.data_ptr(),
-                                      self.m.data_ptr(), self.v.data_ptr() if self.v is not None else 0,
-                                      self.hyper.data_ptr(), self.step_count.data_ptr())
 
     # ------------------------------------------------------------------ pieces
     def set_lr(self, lr: float):
@@ -127,35 +117,24 @@ class TrainStep:
         call it where the host synchronises anyway -- Trainer does at every accuracy / epoch-loss read)."""
         self.eng.check_forward_range()
 
-    def invalidate_weights(self):
-        """Call after changing the model's parameters outside of step() (load_state_dict, manual edits)."""
-        self._prepped = False
-
-    def _fwd_bwd(self, update_running: bool = True, fused_optim: bool = False):
+    def _fwd_bwd(self, update_running: bool = True):
         st = torch.cuda.current_stream().cuda_stream
         e = self.eng
-        # kernel-layout weights were refreshed bucket by bucket at the end of the previous step
-        e.weights_ready = getattr(self, "_prepped", False)
-        self._prepped = False
         e.forward(st, update_running=update_running)
         B, J = e.out.shape[:2]
         HW = e.out[0, 0].numel()
         capi.call("stl_mse_loss", e.out.data_ptr(), self.target.data_ptr(), self.tweight.data_ptr(), e.dout.data_ptr(),
                   self._partial.data_ptr(), self._nblk, None, B, J, HW, self._loss_scale, st)   # (the scalar: behind backward, below)
-        if fused_optim:
-            capi.call("stl_optim_begin_step", self.step_count.data_ptr(), self.eng.overflow.data_ptr(), st)
         # per-bucket issue while backward is being enqueued: RCCL only ("nccl": the collective is a kernel enqueued on the
         # communicator's stream, the host does not wait); gloo's all-reduce of a device tensor makes the host wait for the stream
         dp_on = self.dp is not None and (self.world > 1 or self._force_dp) and not self.use_graph and self._dp_rccl
-        e.backward(st, fused_optim=fused_optim, on_bucket=self._issue_bucket if dp_on else None)
+        e.backward(st, on_bucket=self._issue_bucket if dp_on else None)
         self._buckets_issued = dp_on
         # the loss scalar (a one-block sum of the per-block partials): enqueued BEHIND the backward program -- between the loss
         # kernel and the head's gradient it was 16 us of a single resident block at a point where nothing else can run
         capi.call("stl_sum_partials", self._partial.data_ptr(), self._nblk, 0.5 / float(B * J * HW), self.loss.data_ptr(), 0, st)
         if self._loss_scale != 1.0 or self._loss_offset != 0.0:   # the kernel scales only dL/dout
             self.loss.mul_(self._loss_scale).add_(self._loss_offset)
-        if fused_optim:
-            self._prepped = True   # every bucket's kernel-layout weights were refreshed inside the program
 
     def _optim(self):
         st = torch.cuda.current_stream().cuda_stream
@@ -213,8 +192,6 @@ class TrainStep:
             self._g_fb.replay()
             self._allreduce()
             self._g_opt.replay()
-        elif self._fused_optim and not self.use_graph:
-            self._fwd_bwd(fused_optim=True)
         else:
             self._fwd_bwd()
             self._allreduce()

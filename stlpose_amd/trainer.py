@@ -131,7 +131,6 @@ class Trainer:
         for t in (st.master, st.bufs, st.nbt, ts.m, ts.v, ts.step_count, ts.hyper):
             if t is not None:
                 dist.broadcast(t, src=dist.get_global_rank(self.pg, 0), group=self.pg)
-        self.ts.invalidate_weights()
 
     def _mean_over_ranks(self, *vals):
         """Loaders are sharded, so per-rank epoch statistics differ: average them so that every rank logs
@@ -238,7 +237,6 @@ class Trainer:
         sd = ck["model_state_dict"] if "model_state_dict" in ck else ck
         sd = {(k[len(_PREFIX):] if k.startswith(_PREFIX) else k): v for k, v in sd.items()}
         self.model.load_state_dict(sd)   # in place: the parameters are views of the flat master buffer
-        self.ts.invalidate_weights()
         if only_model:
             return
         self._load_optimizer_state_dict(ck["optimizer_state_dict"])
