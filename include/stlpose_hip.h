@@ -175,6 +175,14 @@ int stl_upsample_backward(const stl_upbwd* p, void* stream);
  * (HRnet.py:290) / VGG conv1_1 into a 1x1 convolution with Ci=32. */
 int stl_patch3x3(int dtype, const float* img, void* out, int B, int H, int W, int stride,
                  const float* mean3, const float* std3, void* stream);
+/* Adjoint of stl_patch3x3 (the data gradient of the patch gather, elementwise.hip patch_kernel): dpatch = gradient of the
+ * 32-wide patch tensor [B,Ho,Wo,32] (element type dtype; columns 27..31 are ignored) -> dimg fp32 NCHW [B,3,H,W], every
+ * element written: dimg[b,c,iy,ix] = sum of dpatch[b,oy,ox,(ky*3+kx)*3+c] over the (oy,ox,ky,kx) with oy*stride+ky-1 = iy and
+ * ox*stride+kx-1 = ix, divided by std3[c] if std3 != NULL (the normalised VGG stem; mean3 has no gradient).  Gather form in a
+ * fixed order: no atomics, deterministic.  Gives the image gradient that autograd of the reference's stem conv
+ * (HRnet.py:290, 434) returns for x. */
+int stl_patch3x3_backward(int dtype, const void* dpatch, float* dimg, int B, int H, int W, int stride, const float* std3,
+                          void* stream);
 
 /* 1x1 head with bias: NHWC dtype [B,H,W,Ci] -> NCHW fp32 [B,J,H,W]  (HRnet.py:331-337,466). */
 int stl_head_forward(int dtype, const void* x, const float* w, const float* bias, float* out,
@@ -206,6 +214,11 @@ int stl_heatmap_argmax(const float* hm, int32_t* idx, float* maxval, float* pred
  * lib/transforms.py:147-164) on device: out = 0.5*(a + shift(flip(b))). */
 int stl_flip_merge(const float* a, const float* bflip, float* out, const int32_t* perm, int B, int J,
                    int H, int W, void* stream);
+/* Adjoint of stl_flip_merge for gradient g of out (fp32 [B,J,H,W]): da = 0.5*g; dbf gathers 0.5*g through the joint
+ * permutation, the mirror and the 1-px shift (column W-1 of dbf receives the terms of x = 0 and x = 1, column 0 none).
+ * Gather form, deterministic; perm may be any map (every j with perm[j] = j' contributes to joint j'). */
+int stl_flip_merge_backward(const float* g, float* da, float* dbf, const int32_t* perm, int B, int J, int H, int W,
+                            void* stream);
 /* +-0.25 px refinement + inverse affine of get_final_preds_hrnet (lib/pose_parsing.py:58-92). */
 int stl_final_preds(const float* hm, const float* center, const float* scale, float* preds,
                     float* maxval, int B, int J, int H, int W, void* stream);
@@ -214,7 +227,8 @@ int stl_final_preds(const float* hm, const float* center, const float* scale, fl
 typedef struct stl_wprep { /* one conv weight: OIHW fp32 master -> kernel layouts */
     int64_t src_off;  /* element offset in master */
     int64_t fwd_off;  /* element offset in `wk`: [Co][tap][Cip] (Cip = padded Ci)          */
-    int64_t bwd_off;  /* element offset in `wk`: [Ci][8-tap][Co] for the data gradient, or -1 */
+    int64_t bwd_off;  /* element offset in `wk`: [Ci][8-tap][Co] for the data gradient (patch: [tap*Ci + ci][Co], rows
+                         Ci*ks*ks .. Cip-1 left as they are -- zero in a zero-initialised buffer), or -1 */
     int32_t Co, Ci, ks, Cip; /* Cip: Ci padded (stem patches: 27 -> 32)                     */
     int32_t patch;    /* 1: Ci*ks*ks flattened as k=(tap*Ci + ci) into Cip (stem / VGG conv1_1) */
     int32_t blk0;     /* first block of this entry */
@@ -300,6 +314,7 @@ int stl_nhwc_to_nchw(int dtype, const void* in, float* out, int B, int C, int H,
 #define STL_OP_BN_GRADS_RANGE 9 /* stl_bn_param_grads over a sub-range of the table */
 #define STL_OP_WGRAD_GROUP 10   /* stl_conv_wgrad_group */
 /* 11 and 12 are retired (the in-program optimiser and weight re-layout): not reused */
+#define STL_OP_PATCH_BWD 13    /* stl_patch3x3_backward (stl_patch_bwd): the image gradient of a plan with input gradients */
 /* A gradient bucket = a contiguous slice of the flat gradient buffer whose weight-gradient slabs and
  * BatchNorm reductions are complete at some point of the backward program.  Reducing it there (and
  * recording an event) lets the data-parallel all-reduce of that slice start while the rest of
@@ -308,6 +323,7 @@ typedef struct stl_reduce_range { const float* partials; float* grads; const stl
 typedef struct stl_bn_range { const double* rstats; float* grads; const stl_bnrec* tab; int32_t n, pad_; } stl_bn_range;
 int stl_reduce_slabs_range(const stl_reduce_range* r, void* stream);
 typedef struct stl_patch { int32_t dtype, B, H, W, stride, pad_; const float* img; void* out; const float* mean3; const float* std3; } stl_patch;
+typedef struct stl_patch_bwd { int32_t dtype, B, H, W, stride, pad_; const void* dpatch; float* dimg; const float* std3; } stl_patch_bwd;
 typedef struct stl_head { int32_t dtype, B, H, W, Ci, J; const void* x; const float* w; const float* bias; float* out; } stl_head;
 typedef struct stl_head_bwd { int32_t dtype /* STL_DT2(dx, x) */, B, H, W, Ci, J, nblk, pad_; const void* x; const float* w; const float* dout; void* dx; float* partial; } stl_head_bwd;
 typedef struct stl_op {

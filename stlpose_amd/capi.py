@@ -87,6 +87,11 @@ class Patch(C.Structure):
                 ("mean3", vp), ("std3", vp)]
 
 
+class PatchBwd(C.Structure):
+    _fields_ = [("dtype", i32), ("B", i32), ("H", i32), ("W", i32), ("stride", i32), ("pad_", i32), ("dpatch", vp), ("dimg", vp),
+                ("std3", vp)]
+
+
 class Head(C.Structure):
     _fields_ = [("dtype", i32), ("B", i32), ("H", i32), ("W", i32), ("Ci", i32), ("J", i32), ("x", vp), ("w", vp),
                 ("bias", vp), ("out", vp)]
@@ -111,7 +116,8 @@ class BNRange(C.Structure):
 
 OP_KIND = {"stl_conv_forward": 0, "stl_conv_wgrad": 1, "stl_fuse_forward": 2, "stl_fuse_backward": 3,
            "stl_upsample_backward": 4, "stl_patch3x3": 5, "stl_head_forward": 6, "stl_head_backward": 7,
-           "stl_reduce_slabs_range": 8, "stl_bn_grads_range": 9, "stl_conv_wgrad_group": 10}   # 11, 12: retired, not reused
+           "stl_reduce_slabs_range": 8, "stl_bn_grads_range": 9, "stl_conv_wgrad_group": 10,   # 11, 12: retired, not reused
+           "stl_patch3x3_backward": 13}
 
 # name -> argtypes (restype is always int unless noted); every symbol include/stlpose_hip.h declares
 SIGNATURES = {
@@ -125,12 +131,14 @@ SIGNATURES = {
     "stl_fuse_backward": [C.POINTER(FuseBwd), vp],
     "stl_upsample_backward": [C.POINTER(UpBwd), vp],
     "stl_patch3x3": [i32, vp, vp, i32, i32, i32, i32, vp, vp, vp],
+    "stl_patch3x3_backward": [i32, vp, vp, i32, i32, i32, i32, vp, vp],
     "stl_head_forward": [i32, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp],
     "stl_head_backward": [i32, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp],
     "stl_mse_loss": [vp, vp, vp, vp, vp, i32, vp, i32, i32, i32, f32, vp],
     "stl_gaussian_targets": [vp, vp, vp, vp, i32, i32, i32, i32, f32, f32, f32, vp],
     "stl_heatmap_argmax": [vp, vp, vp, vp, i32, i32, i32, vp],
     "stl_flip_merge": [vp, vp, vp, vp, i32, i32, i32, i32, vp],
+    "stl_flip_merge_backward": [vp, vp, vp, vp, i32, i32, i32, i32, vp],
     "stl_final_preds": [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp],
     "stl_weight_prep": [i32, vp, vp, vp, i32, i32, vp],
     "stl_reduce_slabs": [vp, vp, vp, i32, i32, vp],

@@ -1019,7 +1019,7 @@ extern "C" int stl_conv_forward(const stl_conv* pp, void* stream) {
     STL_CHECK(p.src.mode == STL_SRC_PLAIN || p.src.gamma, "conv: BN source without gamma");
     STL_CHECK(p.src.mode != STL_SRC_BN || p.src.beta, "conv: BN source without beta");
     STL_CHECK(p.src.mode != STL_SRC_BN || p.src.stats || (p.src.rmean && p.src.rvar), "conv: BN source without statistics");
-    STL_CHECK(p.src.mode != STL_SRC_BNBWD || (p.src.y && p.src.stats && p.src.rstats), "conv: BNBWD source incomplete");
+    STL_CHECK(p.src.mode != STL_SRC_BNBWD || (p.src.y && (p.src.stats || (p.src.rmean && p.src.rvar)) && p.src.rstats), "conv: BNBWD source incomplete");
     STL_CHECK(!(p.out_stats && p.red), "conv: out_stats and red are exclusive");
     STL_CHECK(!p.red || p.mask_y, "conv: red needs mask_y");
     STL_CHECK(!p.mask_y || (p.mask_bn.gamma && p.mask_bn.beta && (p.mask_bn.stats || (p.mask_bn.rmean && p.mask_bn.rvar))), "conv: mask BN incomplete");

@@ -379,6 +379,70 @@ __global__ __launch_bounds__(256) void patch_kernel(const float* img, void* out,
     }
 }
 
+// Adjoint of patch_kernel: dimg[b][c][iy][ix] = sum of the patch-gradient columns kk = tap*3 + c that read (iy, ix), divided
+// by std3[c] when the forward normalised.  Gather form, no atomics: thread (b, oy, ox) owns the S x S image pixels
+// [oy*S, oy*S + S) x [ox*S, ox*S + S) -- every pixel has exactly one owner -- and walks the 32-wide patch rows that cover them
+// ((oy..oy+1) x (ox..ox+1) for S = 2, (oy-1..oy+1) x (ox-1..ox+1) for S = 1) in a fixed order, each row as 16-byte vectors.
+template <typename T, int S>
+__global__ __launch_bounds__(256) void patch_bwd_kernel(const void* dp, float* dimg, int B, int H, int W, int Ho, int Wo,
+                                                        const float* std3) {
+    constexpr int R0 = S == 1 ? -1 : 0;
+    const size_t total = (size_t)B * Ho * Wo;
+    for (size_t pi = (size_t)blockIdx.x * 256 + threadIdx.x; pi < total; pi += (size_t)gridDim.x * 256) {
+        const int ox = (int)(pi % Wo);
+        const size_t by = pi / Wo;
+        const int oy = (int)(by % Ho), b = (int)(by / Ho);
+        float acc[3][S][S];
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+#pragma unroll
+            for (int u = 0; u < S; ++u)
+#pragma unroll
+                for (int v = 0; v < S; ++v) acc[c][u][v] = 0.f;
+#pragma unroll
+        for (int ry = R0; ry <= 1; ++ry) {
+#pragma unroll
+            for (int rx = R0; rx <= 1; ++rx) {
+                const int qy = oy + ry, qx = ox + rx;
+                if (qy < 0 || qy >= Ho || qx < 0 || qx >= Wo) continue;
+                const size_t row = (((size_t)b * Ho + qy) * Wo + qx) * 32;
+                float f[32];   // columns 27..31 are padding
+#pragma unroll
+                for (int q = 0; q < 4; ++q) load8<T>(dp, row + q * 8, f + q * 8);
+#pragma unroll
+                for (int ky = 0; ky < 3; ++ky) {
+                    const int dy = ry * S + ky - 1;   // image row (qy*S + ky - 1) relative to oy*S
+                    if (dy < 0 || dy >= S) continue;
+#pragma unroll
+                    for (int kx = 0; kx < 3; ++kx) {
+                        const int dx = rx * S + kx - 1;
+                        if (dx < 0 || dx >= S) continue;
+#pragma unroll
+                        for (int c = 0; c < 3; ++c) acc[c][dy][dx] += f[(ky * 3 + kx) * 3 + c];
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const float sd = std3 ? std3[c] : 1.f;
+#pragma unroll
+            for (int u = 0; u < S; ++u) {
+                const int iy = oy * S + u;
+                if (iy >= H) continue;
+                float* dst = dimg + (((size_t)b * 3 + c) * H + iy) * W + (size_t)ox * S;
+                if (S == 2 && (W & 1) == 0) {   // both columns exist and the pair is 8-byte aligned
+                    *reinterpret_cast<float2*>(dst) = make_float2(acc[c][u][0] / sd, acc[c][u][S - 1] / sd);
+                } else {
+#pragma unroll
+                    for (int v = 0; v < S; ++v)
+                        if (ox * S + v < W) dst[v] = acc[c][u][v] / sd;
+                }
+            }
+        }
+    }
+}
+
 // ---------------------------------------------------------------- head
 template <typename T, int J>
 __global__ __launch_bounds__(256) void head_fwd_kernel(const void* x, const float* w, const float* bias, float* out,
@@ -638,6 +702,31 @@ __global__ __launch_bounds__(256) void flip_merge_kernel(const float* a, const f
     }
 }
 
+// Adjoint of flip_merge_kernel, gather form: da = 0.5 g; dbf[b][j'][y][x'] = 0.5 * (sum of g[b][j][y][x] over every (j, x) whose
+// output read that element): joints j with perm[j] == j' in ascending order, and per joint x = 0 (only for x' = W-1: the
+// kept column 0) then x = W - x' (x' >= 1).  Column W-1 receives two terms, column 0 none.
+__global__ __launch_bounds__(256) void flip_merge_bwd_kernel(const float* g, float* da, float* dbf, const int32_t* perm,
+                                                             int J, int H, int W, size_t n) {
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
+        const int x = (int)(i % W);
+        const size_t r = i / W;
+        const int y = (int)(r % H);
+        const size_t bj = r / H;
+        const int jp = (int)(bj % J);
+        const size_t b = bj / J;
+        const float gi = g[i];
+        float s = 0.f;
+        for (int j = 0; j < J; ++j) {
+            if (perm[j] != jp) continue;
+            const float* gr = g + ((b * J + j) * H + y) * W;
+            if (x == W - 1) s += gr[0];
+            if (x >= 1) s += gr[W - x];
+        }
+        da[i] = 0.5f * gi;
+        dbf[i] = 0.5f * s;
+    }
+}
+
 // ---------------------------------------------------------------- batched tables
 __device__ __forceinline__ int find_entry(const int* blk0_first, int stride_ints, int n, int blk) {
     int lo = 0, hi = n - 1;
@@ -753,7 +842,12 @@ __global__ __launch_bounds__(256) void weight_prep_kernel(const float* master, T
             wkf[e.fwd_off + (int64_t)co * e.Cip + tap * e.Ci + ci] = (TF)v;
         else
             wkf[e.fwd_off + ((int64_t)co * t + tap) * e.Cip + ci] = (TF)v;
-        if (e.bwd_off >= 0) wk[e.bwd_off + ((int64_t)ci * t + (t - 1 - tap)) * e.Co + co] = (T)v;
+        if (e.bwd_off >= 0) {
+            if (e.patch)   // data gradient of the 1x1 patch conv: [kk = tap*Ci + ci][Co]; rows Ci*taps .. Cip-1 stay zero
+                wk[e.bwd_off + (int64_t)(tap * e.Ci + ci) * e.Co + co] = (T)v;
+            else
+                wk[e.bwd_off + ((int64_t)ci * t + (t - 1 - tap)) * e.Co + co] = (T)v;
+        }
     }
 }
 
@@ -1162,7 +1256,7 @@ extern "C" int stl_fuse_backward(const stl_fuse_bwd* pp, void* stream) {
     STL_CHECK(p.C % 8 == 0 && p.C > 0 && p.C <= 1024, "fuse_bwd: C=%d", p.C);
     STL_CHECK(p.ngrads >= 1 && p.ngrads <= 4 && p.nbn >= 0 && p.nbn <= 4, "fuse_bwd: ngrads/nbn");
     STL_CHECK(!p.relu || p.z, "fuse_bwd: relu needs z");
-    for (int t = 0; t < p.nbn; ++t) STL_CHECK(p.bn[t].x && p.bn[t].stats && p.rstats[t], "fuse_bwd: bn term %d incomplete", t);
+    for (int t = 0; t < p.nbn; ++t) STL_CHECK(p.bn[t].x && (p.bn[t].stats || (p.bn[t].rmean && p.bn[t].rvar)) && p.rstats[t], "fuse_bwd: bn term %d incomplete", t);
     const int bd = stat_block(p.C);
     const size_t total = (size_t)p.B * p.H * p.W * (p.C / 8);
     // grid: 256 blocks measured best end to end for the branch tensors (fewer statistics atomics, less
@@ -1186,7 +1280,7 @@ extern "C" int stl_upsample_backward(const stl_upbwd* pp, void* stream) {
     const stl_upbwd& p = *pp;
     STL_CHECK(p.C % 8 == 0 && p.C > 0 && p.C <= 1024, "upsample_bwd: C=%d", p.C);
     STL_CHECK(p.shift >= 1 && p.shift <= 3, "upsample_bwd: shift %d (1 .. 3)", p.shift);
-    STL_CHECK(p.du && p.dt && p.bn.x && p.bn.stats && p.rstats, "upsample_bwd: null pointer");
+    STL_CHECK(p.du && p.dt && p.bn.x && (p.bn.stats || (p.bn.rmean && p.bn.rvar)) && p.rstats, "upsample_bwd: null pointer");
     const int bd = stat_block(p.C);
     const size_t total = (size_t)p.B * p.H * p.W * (p.C / 8);
     // grid: 256 blocks measured best end to end for the branch tensors (fewer statistics atomics, less
@@ -1229,6 +1323,26 @@ extern "C" int stl_patch3x3(int dtype, const float* img, void* out, int B, int H
     else
         STL_LAUNCH(patch_kernel<float>, dim3(nblocks_for(total, 256, 4096)), dim3(256), 0, ST, img, out, B, H, W, Ho, Wo, stride, mean3, std3);
     STL_LAUNCH_CHECK("patch3x3");
+    return 0;
+}
+
+extern "C" int stl_patch3x3_backward(int dtype, const void* dpatch, float* dimg, int B, int H, int W, int stride, const float* std3,
+                                     void* stream) {
+    STL_CHECK(stride == 1 || stride == 2, "patch3x3_backward: stride");
+    STL_CHECK(dpatch && dimg && B > 0 && H > 0 && W > 0, "patch3x3_backward: bad args");
+    const int Ho = (H + 2 - 3) / stride + 1, Wo = (W + 2 - 3) / stride + 1;
+    const size_t total = (size_t)B * Ho * Wo;
+    const dim3 grid(nblocks_for(total, 256, 4096));
+#define PB(TT)                                                                                                              \
+    do {                                                                                                                    \
+        if (stride == 2) STL_LAUNCH((patch_bwd_kernel<TT, 2>), grid, dim3(256), 0, ST, dpatch, dimg, B, H, W, Ho, Wo, std3); \
+        else STL_LAUNCH((patch_bwd_kernel<TT, 1>), grid, dim3(256), 0, ST, dpatch, dimg, B, H, W, Ho, Wo, std3);            \
+    } while (0)
+    if (dtype == STL_BF16) PB(__bf16);
+    else if (dtype == STL_F16) PB(f16);
+    else PB(float);
+#undef PB
+    STL_LAUNCH_CHECK("patch3x3_backward");
     return 0;
 }
 
@@ -1316,6 +1430,16 @@ extern "C" int stl_flip_merge(const float* a, const float* bflip, float* out, co
     if (n == 0) return 0;
     STL_LAUNCH(flip_merge_kernel, dim3(nblocks_for(n)), dim3(256), 0, ST, a, bflip, out, perm, J, H, W, n);
     STL_LAUNCH_CHECK("flip_merge");
+    return 0;
+}
+
+extern "C" int stl_flip_merge_backward(const float* g, float* da, float* dbf, const int32_t* perm, int B, int J, int H, int W,
+                                       void* stream) {
+    const size_t n = (size_t)B * J * H * W;
+    if (n == 0) return 0;
+    STL_CHECK(g && da && dbf && perm, "flip_merge_backward: null pointer");
+    STL_LAUNCH(flip_merge_bwd_kernel, dim3(nblocks_for(n)), dim3(256), 0, ST, g, da, dbf, perm, J, H, W, n);
+    STL_LAUNCH_CHECK("flip_merge_backward");
     return 0;
 }
 

@@ -49,6 +49,11 @@ static int run_op(const stl_op& o, void* st, int i) {
                 rc = stl_patch3x3(a->dtype, a->img, a->out, a->B, a->H, a->W, a->stride, a->mean3, a->std3, st);
                 break;
             }
+            case STL_OP_PATCH_BWD: {
+                const stl_patch_bwd* a = static_cast<const stl_patch_bwd*>(o.desc);
+                rc = stl_patch3x3_backward(a->dtype, a->dpatch, a->dimg, a->B, a->H, a->W, a->stride, a->std3, st);
+                break;
+            }
             case STL_OP_HEAD: {
                 const stl_head* a = static_cast<const stl_head*>(o.desc);
                 rc = stl_head_forward(a->dtype, a->x, a->w, a->bias, a->out, a->B, a->H, a->W, a->Ci, a->J, st);

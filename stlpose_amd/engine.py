@@ -133,9 +133,18 @@ class ParamStore:
 
 
 class Engine:
-    """One plan: fixed batch/resolution/dtype/mode."""
+    """One plan: fixed batch/resolution/dtype/mode.
 
-    def __init__(self, arch: Arch, store: ParamStore, B: int, H: int, W: int, dtype: int, training: bool):
+    input_grad: the backward program also produces dL/d(image) in ``self.dimg`` (fp32 NCHW): the stem's patch tensor gets a
+    data gradient and ``stl_patch3x3_backward`` turns it into the image gradient.  A training plan keeps everything else as
+    without the flag (same forward, same parameter gradients).  An eval plan (training=False) gets a data-gradient-only backward
+    through the eval-mode network: BatchNorm backward with the running statistics (BNBWD sources read ``stats = NULL`` and an
+    ``rstats`` arena that stays zero), no weight gradients, no slabs or buckets, nothing written to the running statistics or
+    ``store.grads``; every reduction the backward kernels perform lands in ``self.sink``, which nothing reads.  Without the
+    flag a plan is exactly what it was before the flag existed."""
+
+    def __init__(self, arch: Arch, store: ParamStore, B: int, H: int, W: int, dtype: int, training: bool,
+                 input_grad: bool = False):
         assert H % 32 == 0 and W % 32 == 0, "input H, W must be multiples of 32 (four stride-2 stages + 8x upsample)"
         self.arch, self.store, self.B, self.H, self.W = arch, store, B, H, W
         # dtype: capi.F32, capi.BF16 or capi.MIXED (= dt2(BF16, F16)).  self.dtype = element type of the GRADIENT tensors (and, in
@@ -146,6 +155,7 @@ class Engine:
         self.dtype, self.fdtype = dtype & 0xff, ((dtype >> 8) & 0xff) or (dtype & 0xff)
         self.ydtype = self.fdtype if self.fdtype != self.dtype else 0   # what the backward descriptors carry (0 = same)
         self.training = training
+        self.input_grad = input_grad
         self.dev = store.device
         self.esz = _esz(dtype)
         self.tdtype = torch.float32 if self.dtype == capi.F32 else torch.bfloat16   # kernel-layout weights: just a byte container in the 16-bit modes
@@ -163,10 +173,14 @@ class Engine:
         self.img = torch.zeros(B, 3, H, W, dtype=torch.float32, device=self.dev)
         self.out: Optional[torch.Tensor] = None
         self.dout: Optional[torch.Tensor] = None
+        self.dimg: Optional[torch.Tensor] = None   # input_grad: dL/d(img), fp32 NCHW
         # pass 1: count BN channels to size the statistics arenas
         nstat = bn_stat_elems(store.reg)
         self.stats = torch.zeros(max(nstat, 1), dtype=torch.float64, device=self.dev)
-        self.rstats = torch.zeros(max(nstat, 1), dtype=torch.float64, device=self.dev) if training else None
+        self.rstats = torch.zeros(max(nstat, 1), dtype=torch.float64, device=self.dev) if training or input_grad else None
+        # eval + input_grad: rstats above stays all-zero (eval-mode BatchNorm backward is v = gamma * rstd_running * dt), and the
+        # reductions the backward kernels cannot skip (data-gradient epilogues, sums, upsamples) go here instead
+        self.sink = torch.zeros(max(nstat, 1), dtype=torch.float64, device=self.dev) if input_grad and not training else None
         self.overflow = torch.full((1,), 2 ** 31 - 1, dtype=torch.int32, device=self.dev)   # range guard, see check_forward_range
         # ---- the planner's knobs (all of them; INTEGRATION.md lists what each is for and what was measured)
         env = os.environ.get
@@ -202,7 +216,7 @@ class Engine:
         self._check_stats_arena(nstat)
         self._finalize_weights()
         self._build_tables()
-        if training:
+        if training or input_grad:
             self._build_backward()
 
     def _check_stats_arena(self, nstat: int):
@@ -267,7 +281,8 @@ class Engine:
         pd.dtype, pd.B, pd.H, pd.W, pd.stride = self.fdtype, B, H, W, 2
         pd.img, pd.out = self.img.data_ptr(), t.data_ptr()
         self.fwd_ops.append(("stl_patch3x3", pd, 0, [], [t.data_ptr()]))
-        return Act("plain", t, B, Ho, Wo, 32, needs_grad=False)
+        self._patches = Act("plain", t, B, Ho, Wo, 32, needs_grad=self.input_grad)
+        return self._patches
 
     def conv_bn(self, ck, bk, x: Act, cout, ks, stride, relu, patch=False) -> Act:
         st = self.store
@@ -279,7 +294,7 @@ class Engine:
         # kernel-layout weights: forward [Co][taps][Cik]; data-gradient [Cik][taps][Co]
         ci.fwd_off = self._wk_elems
         self._wk_elems += cout * kks * kks * x.C
-        if x.needs_grad and self.training:
+        if x.needs_grad and (self.training or self.input_grad):
             ci.bwd_off = self._wk_elems
             self._wk_elems += cout * kks * kks * x.C
         self.convs.append(ci)
@@ -396,6 +411,11 @@ class Engine:
         J = self.out.shape[1]
         self.dout = torch.zeros_like(self.out)
         producer = {id(n[2]): n for n in self.tape if n[0] == "fuse"}
+        wgrads = self.training   # eval plans (input_grad) compute data gradients only
+        red_arena = self.rstats if self.training else self.sink
+
+        def red(bn: BNInfo) -> int:   # where a BatchNorm's backward reductions go
+            return red_arena.data_ptr() + 8 * bn.stats_off
         # ---- gradient buckets: contiguous suffixes of the flat gradient buffer, closed as soon as every
         # parameter in them has its slabs / BatchNorm reductions complete (backward finishes the last
         # layers first).  Each bucket gets one ranged slab reduction + BN-gradient launch inside the
@@ -457,10 +477,12 @@ class Engine:
                 hb.x, hb.w, hb.dout, hb.dx = x.ptr, self.head_w, self.dout.data_ptr(), dx.data_ptr()
                 self._head_bwd_args = (hb, part_off)
                 ops.append(("stl_head_backward", hb, 0, [self.dout.data_ptr(), x.ptr], [dx.data_ptr(), id(hb)]))
+                x.grads.append(dx)
+                if not wgrads:   # the kernel still writes its weight-gradient partials: into the slab arena, unreduced
+                    continue
                 bk["reads"].append(id(hb))
                 bucket_add(st.param_off[key + ".weight"], joints * x.C)
                 bucket_add(st.param_off[key + ".bias"], joints)
-                x.grads.append(dx)
                 self.slabs.append(dict(part_off=part_off, grad_off=st.param_off[key + ".weight"], nsplit=nblk,
                                        Co=joints, Ci=x.C, ks=1, Cip=x.C, patch=0, stride=nel))
                 self.slabs.append(dict(part_off=part_off + joints * x.C, grad_off=st.param_off[key + ".bias"],
@@ -486,7 +508,7 @@ class Engine:
                 p.nbn = len(same_bn)
                 for i, a in enumerate(same_bn):
                     p.bn[i] = self._src(a)
-                    p.rstats[i] = self.rstats.data_ptr() + 8 * a.bn.stats_off
+                    p.rstats[i] = red(a.bn)
                 trivial = (len(z.grads) == 1 and not relu and not same_bn) or z.fused_du is not None
                 du = z.grads[0] if trivial else self._new_grad(z)
                 p.du = du.data_ptr()
@@ -507,16 +529,17 @@ class Engine:
                         a.dt = self._new_grad(a)
                         u.dt = a.dt.data_ptr()
                         u.bn = self._src(a)
-                        u.rstats = self.rstats.data_ptr() + 8 * a.bn.stats_off
+                        u.rstats = red(a.bn)
                         ops.append(("stl_upsample_backward", u, strm, [du.data_ptr()], [a.dt.data_ptr()]))
             else:  # conv
                 _, x, y, ci, (kks, kstride), strm = node
                 x.bwd_seen += 1
                 assert y.consumers == 1 and y.dt is not None, f"{ci.key}: BN activation must have exactly one consumer"
                 g = self._gsrc(y)
-                self._emit_wgrad(ops, bk, x, y, ci, g, kks, kstride, strm)
-                bucket_add(ci.master_off, ci.Co * ci.Ci * ci.ks * ci.ks)
-                bucket_add(y.bn.param_off, 2 * y.bn.C)   # gamma, beta of the BatchNorm behind this conv
+                if wgrads:
+                    self._emit_wgrad(ops, bk, x, y, ci, g, kks, kstride, strm)
+                    bucket_add(ci.master_off, ci.Co * ci.Ci * ci.ks * ci.ks)
+                    bucket_add(y.bn.param_off, 2 * y.bn.C)   # gamma, beta of the BatchNorm behind this conv
                 # ---- data gradient
                 if not x.needs_grad:
                     continue
@@ -547,7 +570,7 @@ class Engine:
                         d.mask_z = x.ptr
                         d.mask_y = ybn.ptr
                         d.mask_bn = self._src(ybn, relu=False)
-                        d.red = self.rstats.data_ptr() + 8 * ybn.bn.stats_off
+                        d.red = red(ybn.bn)
                         dreads += [x.ptr, ybn.ptr]
                         x.fused_du = out
                     else:
@@ -558,18 +581,24 @@ class Engine:
                     x.dt = out
                     d.mask_y = x.ptr
                     d.mask_bn = self._src(x)
-                    d.red = self.rstats.data_ptr() + 8 * x.bn.stats_off
+                    d.red = red(x.bn)
                 d.out = out.data_ptr()
                 ops.append(("stl_conv_forward", d, strm, dreads, [out.data_ptr()]))
-        bucket_close(force=True)
+        if wgrads:
+            bucket_close(force=True)
+        if self.input_grad:
+            self._emit_patch_backward(ops)
         for o in ops[n_before:]:
             self._nactive.setdefault(id(o[1]), cur_active)
-        assert bk["done"] == 0 and bk["hi"] == 0, "gradient buckets do not cover the parameter buffer"
         # slab arena + reduce table
         self.slab_arena = torch.zeros(max(self._slab_elems, 1), dtype=torch.float32, device=self.dev)
         base = self.slab_arena.data_ptr()
         hb, off = self._head_bwd_args
         hb.partial = base + 4 * off
+        if not wgrads:
+            self.bwd_ops = self._balance_streams(ops)
+            return
+        assert bk["done"] == 0 and bk["hi"] == 0, "gradient buckets do not cover the parameter buffer"
         for s in self.slabs:
             if "struct" in s:
                 s["struct"].partial = base + 4 * s["part_off"]
@@ -597,6 +626,17 @@ class Engine:
         self.bwd_ops = self._balance_streams(ops)
         for b in self.buckets:   # bucket events are addressed by op index
             b["op"] = next(i for i, o in enumerate(self.bwd_ops) if o[1] is b["br"])
+
+    def _emit_patch_backward(self, ops):
+        """Image gradient: the adjoint of the stem's patch gather (stl_patch3x3_backward) over the patch tensor's data gradient,
+        which the stem conv's data-gradient launch (a 1x1 conv onto 32-wide patches, weights [kk][Co]) has just written."""
+        x = self._patches
+        assert len(x.grads) == 1 and x.bwd_seen == x.consumers == 1, "patch tensor: expected one data-gradient contribution"
+        self.dimg = torch.zeros(self.B, 3, self.H, self.W, dtype=torch.float32, device=self.dev)
+        pb = capi.PatchBwd()
+        pb.dtype, pb.B, pb.H, pb.W, pb.stride = self.dtype, self.B, self.H, self.W, 2
+        pb.dpatch, pb.dimg = x.grads[0].data_ptr(), self.dimg.data_ptr()
+        ops.append(("stl_patch3x3_backward", pb, 0, [x.grads[0].data_ptr()], [self.dimg.data_ptr()]))
 
     def _op_cost_us(self, op) -> float:
         """Rough duration of a backward launch for the list scheduler: a fixed launch + latency-chain part plus its
@@ -847,11 +887,15 @@ class Engine:
             "or 'fp32'.")
 
     def backward(self, stream: int, on_bucket=None):
-        """expects self.dout filled; leaves dL/dparam in store.grads (overwrites).  on_bucket(i): called on the host right after
+        """expects self.dout filled; leaves dL/dparam in store.grads (overwrites; training plans) and, with input_grad, dL/d(img)
+        in self.dimg (an eval plan writes nothing else that outlives the call).  on_bucket(i): called on the host right after
         gradient bucket i's last op has been ENQUEUED (the program is issued range by range, stl_program_run_range): the
         data-parallel path enqueues the bucket's all-reduce there, so that in every in-order hardware queue it sits directly
         behind the bucket instead of behind the rest of backward."""
-        assert self.training
+        assert self.training or self.input_grad
+        if not self.training:   # eval + input_grad: dimg only; rstats stays zero, the reductions go to the sink
+            self._run(self.bwd_ops, stream)
+            return
         self.rstats.zero_()
         if on_bucket is not None and self.buckets:
             h = self._program(self.bwd_ops)

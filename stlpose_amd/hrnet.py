@@ -6,6 +6,19 @@ same ``state_dict`` names/shapes (1754 entries for W32; loads the reference's
 ``pose_hrnet_w32_256x192.pth`` strictly), ``.train()/.eval()/.to()/.parameters()`` and
 ``model(img) -> (B, 17, H/4, W/4)`` fp32 NCHW, differentiable through ``loss.backward()``.
 
+Gradient with respect to the input image (``img.requires_grad_()``; saliency maps, robustness checks, optimising an image
+against a pose loss):
+  * training mode: ``img.grad`` together with the parameter gradients (a plan of its own, built with ``input_grad``; the
+    parameter gradients are bit-identical to those of the same step without ``img.requires_grad``);
+  * eval mode: when grad mode is on and ``img.requires_grad``, the output carries a ``grad_fn`` whose backward gives ``img.grad``
+    through the eval-mode network (BatchNorm with the running statistics) and NOTHING else: parameters' ``.grad`` stay untouched
+    (``None`` or whatever they were), running statistics are not updated.  Every other eval call runs under ``no_grad`` as
+    before and returns a tensor without ``grad_fn``;
+  * one activation set per plan: backward must follow its own forward before the next forward of the same (batch, resolution,
+    mode) -- otherwise the loud stale-forward error below.  ``forward_pass(..., flip=True)`` in eval mode therefore runs the
+    image and its mirror as ONE batch when the image requires grad; in training mode the two forwards of the flip test share
+    a plan, and backward through the first raises that error.
+
 Everything between input and output runs in the hand-written HIP kernels of
 ``libstlpose_hip.so`` through the static plans of ``engine.py``; there is no torch.nn compute and
 no CPU fallback (a CPU tensor raises).
@@ -81,9 +94,36 @@ class _Fn(torch.autograd.Function):
                 "differentiated, and its activations were overwritten (the reference's autograd keeps one set "
                 "per call; this engine keeps one per plan).  Call backward before the next forward of the same "
                 "shape, or concatenate the inputs into one batch.")
-        flat = torch.ops.stlpose.hrnet_backward(gout.contiguous(), ops.register_engine(eng))   # the flat parameter gradient
+        if eng.input_grad:   # built for an img that requires grad (PoseHighResolutionNet.forward)
+            flat, dimg = torch.ops.stlpose.hrnet_backward_input(gout.contiguous(), ops.register_engine(eng))
+        else:
+            flat, dimg = torch.ops.stlpose.hrnet_backward(gout.contiguous(), ops.register_engine(eng)), None   # the flat parameter gradient
         net._publish_grads(flat)
-        return None, None, None, None
+        return (dimg if ctx.needs_input_grad[0] else None), None, None, None
+
+
+class _EvalFn(torch.autograd.Function):
+    """Eval-mode autograd bridge for an input that requires grad: the forward is the eval plan's (built with input_grad), the
+    backward its data-gradient-only program.  Yields dL/d(img) only -- parameter gradients are not computed in eval mode."""
+
+    @staticmethod
+    def forward(ctx, img, eng):
+        ctx.eng = eng
+        out = torch.ops.stlpose.hrnet_forward(img, ops.register_engine(eng))
+        ctx.generation = eng.generation
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        eng = ctx.eng
+        if ctx.generation != eng.generation:
+            raise RuntimeError(
+                "stlpose_amd.PoseHighResolutionNet: backward through a stale forward -- the eval plan for this "
+                f"(batch, resolution) ran forward #{eng.generation} after the forward (#{ctx.generation}) being "
+                "differentiated, and its activations were overwritten.  Call backward before the next forward of the same "
+                "shape, or concatenate the inputs into one batch.")
+        _, dimg = torch.ops.stlpose.hrnet_backward_input(gout.contiguous(), ops.register_engine(eng))
+        return dimg, None
 
 
 class PoseHighResolutionNet(nn.Module):
@@ -206,11 +246,11 @@ class PoseHighResolutionNet(nn.Module):
             off = st.param_off[key]
             self._tensor(key).grad = pub[off:off + int(math.prod(shape))].view(shape)
 
-    def engine(self, B: int, H: int, W: int, training: bool) -> Engine:
-        key = (B, H, W, training, self.compute_dtype)
+    def engine(self, B: int, H: int, W: int, training: bool, input_grad: bool = False) -> Engine:
+        key = (B, H, W, training, self.compute_dtype, input_grad)
         e = self._engines.get(key)
         if e is None:
-            e = self._engines[key] = Engine(self.arch, self._store, B, H, W, self.compute_dtype, training)
+            e = self._engines[key] = Engine(self.arch, self._store, B, H, W, self.compute_dtype, training, input_grad)
         return e
 
     # ------------------------------------------------------------------ forward
@@ -223,9 +263,12 @@ class PoseHighResolutionNet(nn.Module):
         if not self._packed(x.device):
             self._pack(x.device)
         B, _, H, W = x.shape
-        eng = self.engine(B, H, W, self.training)
+        want_dimg = torch.is_grad_enabled() and x.requires_grad
         if self.training and torch.is_grad_enabled():
-            return _Fn.apply(x, self._anchor, self, eng)
+            return _Fn.apply(x, self._anchor, self, self.engine(B, H, W, True, want_dimg))
+        if want_dimg:
+            return _EvalFn.apply(x, self.engine(B, H, W, False, True))
+        eng = self.engine(B, H, W, self.training)
         with torch.no_grad():
             return torch.ops.stlpose.hrnet_forward(x, ops.register_engine(eng))
 

@@ -5,8 +5,9 @@ host reaches the HIP kernels.  Every op below is a thin dispatcher-visible wrapp
 C ABI (``include/stlpose_hip.h`` -> ``libstlpose_hip.so``): tensors are allocated by torch, the kernel is
 enqueued on the current HIP stream, nothing is computed by ATen.  There is no CPU implementation: on a CPU
 tensor the dispatcher raises (no kernel registered for that backend).  Fake (meta) implementations make the ops
-traceable.  The stateful whole-network ops (``stlpose::hrnet_forward`` / ``hrnet_backward``) take the handle of
-a planned engine (``engine.Engine``), because their plans own the activation buffers.
+traceable.  The stateful whole-network ops (``stlpose::hrnet_forward`` / ``hrnet_backward`` / ``hrnet_backward_input``) take
+the handle of a planned engine (``engine.Engine``), because their plans own the activation buffers.  ``flip_merge`` has an
+autograd formula (``flip_merge_backward``, the kernel's adjoint).
 """
 from __future__ import annotations
 
@@ -90,6 +91,31 @@ def _flip_merge(out: torch.Tensor, out_flipped: torch.Tensor, perm: torch.Tensor
 _define("flip_merge(Tensor out, Tensor out_flipped, Tensor perm) -> Tensor", _flip_merge, lambda a, f, p: torch.empty_like(a))
 
 
+def _flip_merge_bwd(grad: torch.Tensor, perm: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    g = grad.contiguous().float()
+    da, dbf = torch.empty_like(g), torch.empty_like(g)
+    b, j, h, w = g.shape
+    capi.call("stl_flip_merge_backward", g.data_ptr(), da.data_ptr(), dbf.data_ptr(), perm.to(torch.int32).contiguous().data_ptr(),
+              b, j, h, w, _st())
+    return da, dbf
+
+
+_define("flip_merge_backward(Tensor grad, Tensor perm) -> (Tensor, Tensor)", _flip_merge_bwd,
+        lambda g, p: (torch.empty_like(g, dtype=torch.float32), torch.empty_like(g, dtype=torch.float32)))
+
+
+def _flip_merge_setup(ctx, inputs, output):
+    ctx.perm = inputs[2]
+
+
+def _flip_merge_autograd(ctx, grad):
+    da, dbf = torch.ops.stlpose.flip_merge_backward(grad, ctx.perm)
+    return da, dbf, None
+
+
+torch.library.register_autograd("stlpose::flip_merge", _flip_merge_autograd, setup_context=_flip_merge_setup, lib=_LIB)
+
+
 # ------------------------------------------------------------------ data pipeline (data/JointsDataset.py:189-286)
 def _targets(joints: torch.Tensor, vis: torch.Tensor, hh: int, wh: int, sx: float, sy: float, sigma: float) -> Tuple[torch.Tensor, torch.Tensor]:
     j, v = joints.contiguous().float(), vis.contiguous().float()
@@ -140,6 +166,17 @@ def _hrnet_bwd(grad_out: torch.Tensor, handle: int) -> torch.Tensor:
     return eng.store.grads.clone()   # a fresh tensor: an op must not hand out an alias of the plan's own buffer
 
 
+def _hrnet_bwd_input(grad_out: torch.Tensor, handle: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Backward of a plan built with input_grad, for the LAST forward of that plan: (flat parameter gradient, dL/d(img)).  An eval
+    plan computes no parameter gradients: its first result is empty (0 elements) and store.grads is left as it was."""
+    eng = _ENGINES[handle]
+    assert eng.input_grad, "hrnet_backward_input: the plan was built without input_grad"
+    eng.dout.copy_(grad_out)
+    eng.backward(_st())
+    flat = eng.store.grads.clone() if eng.training else grad_out.new_empty(0, dtype=torch.float32)
+    return flat, eng.dimg.clone()
+
+
 def _hrnet_fwd_fake(img, engine):
     eng = _ENGINES[engine]   # joints and output stride come from the planned engine, not from constants
     return img.new_empty(tuple(eng.out.shape), dtype=torch.float32)
@@ -152,4 +189,14 @@ def _hrnet_bwd_fake(grad_out, engine):
 _define("hrnet_forward(Tensor img, int engine) -> Tensor", _hrnet_fwd, _hrnet_fwd_fake)
 _define("hrnet_backward(Tensor grad_out, int engine) -> Tensor", _hrnet_bwd, _hrnet_bwd_fake)
 
-OPS = ["person_mse", "heatmap_argmax", "final_preds", "flip_merge", "gaussian_targets", "affine_crop", "hrnet_forward", "hrnet_backward"]
+
+def _hrnet_bwd_input_fake(grad_out, engine):
+    eng = _ENGINES[engine]
+    return (grad_out.new_empty(eng.store.nparam if eng.training else 0, dtype=torch.float32),
+            grad_out.new_empty((eng.B, 3, eng.H, eng.W), dtype=torch.float32))
+
+
+_define("hrnet_backward_input(Tensor grad_out, int engine) -> (Tensor, Tensor)", _hrnet_bwd_input, _hrnet_bwd_input_fake)
+
+OPS = ["person_mse", "heatmap_argmax", "final_preds", "flip_merge", "flip_merge_backward", "gaussian_targets", "affine_crop",
+       "hrnet_forward", "hrnet_backward", "hrnet_backward_input"]
