@@ -347,6 +347,53 @@ int stl_program_wait_op(void* program, int op, void* stream);
 /* Self-checks that need no reference: MFMA / LDS-transpose lane maps (used by tests). */
 int stl_selftest_mfma(float* out /* [4] max abs err: bf16 mfma, f32 mfma, tr-read, f64 atomic */, void* stream);
 
+/* ---- pose retrieval (stlpose_amd/csrc/retrieval.hip): the second half of the reference, src/06_fit_knn_tree.py and
+ * src/07_retrieval_experiments.py.  Pose vectors are fp32 [N, D], D = 34 / 26 / 18 (STL_POSE_ALL_KPTS / FULL_BODY / UPPER_BODY).
+ * Every kernel evaluates a (query, row) pair through one device routine with a fixed accumulation order (a sequential chain over
+ * d = 0 .. D-1), so distances, top-k and rank agree bit for bit.  Result order: ascending distance, ties by ascending database
+ * index, NaN last (np.argsort(kind="stable")). */
+#define STL_POSE_ALL_KPTS 0   /* keypoints 0..16, D = 34 */
+#define STL_POSE_FULL_BODY 1  /* keypoints 5..16, 0, D = 26 (the origin is the left shoulder, not the nose: the reference's order) */
+#define STL_POSE_UPPER_BODY 2 /* keypoints 5..12, 0, D = 18 */
+#define STL_POSE_EUCLIDEAN 0       /* pose_database.py:201-202 "euclidean_distance" */
+#define STL_POSE_COSINE 1          /* :199-200 "cosine_similarity": 1 - x.y, no normalisation */
+#define STL_POSE_MANHATTAN 2       /* :203-204 "manhattan_distance" */
+#define STL_POSE_CONFIDENCE 3      /* :205-206, metrics.py:97-117 "confidence_score" (conf [Q, D], NULL = ones) */
+#define STL_POSE_OKS 4             /* :207-210, metrics.py:120-149 "oks_score" (sigmas chosen by D) */
+#define STL_POSE_L2SQ 5            /* hnswlib space "l2": squared L2 (penalization ignored) */
+#define STL_POSE_COS_NORMALISED 6  /* hnswlib space "cosine": 1 - x.y / (|x| |y|) (penalization ignored) */
+#define STL_POSE_PEN_ZERO_COORD 0  /* pose_database.py:226-229 */
+#define STL_POSE_PEN_NONE 1        /* :231-236 |q| < 1e-5: q, row and confidence zeroed */
+#define STL_POSE_PEN_MEAN 2        /* :238-243 |q| < 1e-5 and |row| > 1e-5: q = mean of the unmasked metric over rows 0..min(100,N)-1 */
+#define STL_POSE_PEN_MAX 3         /*          ... = max of it (:251-285); computed per query inside the launch */
+#define STL_POSE_TOPK_MAX 1024     /* largest k of stl_pose_topk */
+#define STL_POSE_RANK_MAX 16384    /* largest N of stl_pose_rank: one workgroup holds N (dist, idx) keys in LDS (128 KiB) */
+#define STL_POSE_RANK_LABELS_MAX 4 /* label levels scored by stl_pose_rank */
+#define STL_POSE_NSCORES 10        /* p@1, p@5, p@10, p@rel, mAP, r@1, r@5, r@10, r@rel, mAR (metrics.py:25-94) */
+
+/* joints [N, 17, C >= 2] (pose n at joints + n * row_stride, keypoint k at + k * C) -> out [N, D]: the selected keypoints' (x, y),
+ * minus the first selected keypoint, entries that were exactly 0 kept 0, then (normalize) divided by max(L2 norm, 1e-5).
+ * Replaces process_pose_vector (pose_database.py:19-69) and process_data (06_fit_knn_tree.py:84-147). */
+int stl_pose_vectors(const float* joints, int64_t row_stride, int C, float* out, int N, int approach, int normalize, void* stream);
+/* out [Q, N] = metric(q[i], db[j]) with the penalization of the query: the loop of get_neighbors_idxs (pose_database.py:220-245)
+ * before its argsort.  Q <= 65535. */
+int stl_pose_distances(const float* q, const float* conf, const float* db, float* out, int Q, int N, int D, int method,
+                       int penalization, void* stream);
+/* Bytes of the `work` buffer stl_pose_topk needs for (Q, N, k) (0: none), or a negative error code (k > N, k > STL_POSE_TOPK_MAX). */
+int stl_pose_topk_workspace(int Q, int N, int k, int D);
+/* Fused distance + top-k: idx int64 [Q, k], dist [Q, k], the first k of the ranking; never materialises [Q, N].  Replaces
+ * get_neighbors_idxs with num_retrievals = k (pose_database.py:247-248) and hnswlib knn_query (:182-185, 06_fit_knn_tree.py:150-166)
+ * exactly.  N is split across workgroups; a second launch merges the per-chunk lists. */
+int stl_pose_topk(const float* q, const float* conf, const float* db, int Q, int N, int D, int method, int penalization, int k,
+                  int64_t* idx, float* dist, void* work, int64_t work_bytes, void* stream);
+/* Full ranking of N <= STL_POSE_RANK_MAX rows per query: the first k_out (0 .. N) indices / distances, and, when labels [L, N] is
+ * given (with the queries' labels qlabels [L, Q], L <= 4), score_retrievals (metrics.py:25-94) of the first k_eff retrievals per
+ * query and level into scores fp64 [Q, L, STL_POSE_NSCORES] (rank 0 dropped; all -1 when nothing relevant is retrieved;
+ * 11 <= k_eff <= N).  The all-vs-all experiment (07_retrieval_experiments.py:67-112) without any [N, N] array. */
+int stl_pose_rank(const float* q, const float* conf, const float* db, int Q, int N, int D, int method, int penalization, int k_out,
+                  int64_t* idx, float* dist, const int32_t* labels, const int32_t* qlabels, int L, int k_eff, double* scores,
+                  void* stream);
+
 const char* stl_last_error(void);
 int stl_version(void);
 /* Hash (16 hex digits) of the kernel and header sources this library was compiled from (stlpose_amd/build.py). */

@@ -19,6 +19,13 @@ def dt2(grad_dtype: int, fwd_dtype: int) -> int:
     return grad_dtype | ((fwd_dtype if fwd_dtype != grad_dtype else 0) << 8)
 
 
+# pose retrieval (STL_POSE_* of include/stlpose_hip.h)
+POSE_APPROACH = {"all_kpts": 0, "full_body": 1, "upper_body": 2}
+POSE_DIM = {"all_kpts": 34, "full_body": 26, "upper_body": 18}
+POSE_METHOD = {"euclidean": 0, "cosine": 1, "manhattan": 2, "confidence": 3, "oks": 4, "l2sq": 5, "cos_normalised": 6}
+POSE_PEN = {"zero_coord": 0, "none": 1, "mean": 2, "max": 3}
+POSE_TOPK_MAX, POSE_RANK_MAX, POSE_RANK_LABELS_MAX, POSE_NSCORES = 1024, 16384, 4, 10
+
 MIXED = dt2(BF16, F16)   # the mixed 16-bit mode: forward tensors f16, gradients bf16
 NSHARD = 2
 WGRAD_GROUP_MAX = 8
@@ -161,6 +168,11 @@ SIGNATURES = {
     "stl_program_destroy": [vp],
     "stl_program_wait_op": [vp, i32, vp],
     "stl_selftest_mfma": [vp, vp],
+    "stl_pose_vectors": [vp, i64, i32, vp, i32, i32, i32, vp],
+    "stl_pose_distances": [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp],
+    "stl_pose_topk_workspace": [i32, i32, i32, i32],
+    "stl_pose_topk": [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, i64, vp],
+    "stl_pose_rank": [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, i32, i32, vp, vp],
     "stl_version": [],
 }
 

@@ -198,5 +198,112 @@ def _hrnet_bwd_input_fake(grad_out, engine):
 
 _define("hrnet_backward_input(Tensor grad_out, int engine) -> (Tensor, Tensor)", _hrnet_bwd_input, _hrnet_bwd_input_fake)
 
+# ------------------------------------------------------------------ pose retrieval (lib/pose_database.py, lib/metrics.py:25-149)
+# method / penalization / approach travel as strings; an unknown name reaches the C ABI as -1 and is refused there.
+# The C ABI sees pointers and (Q, N, D) only: every shape it relies on is checked here, before anything is launched.
+def _same_device(ts, dev):
+    for name, t in ts:
+        if t is not None and t.device != dev:
+            raise RuntimeError(f"stlpose pose op: {name} is on {t.device}, the queries on {dev}")
+
+
+def _check_pose_shapes(query, conf, database, labels=None, qlabels=None):
+    if query.dim() != 2 or database.dim() != 2:
+        raise RuntimeError(f"stlpose pose op: query and database must be 2-D [Q, D] / [N, D], got {tuple(query.shape)} and "
+                           f"{tuple(database.shape)}")
+    if query.shape[1] != database.shape[1]:
+        raise RuntimeError(f"stlpose pose op: query width {query.shape[1]} differs from database width {database.shape[1]}")
+    if conf is not None and tuple(conf.shape) != tuple(query.shape):
+        raise RuntimeError(f"stlpose pose op: confidence must have the query's shape {tuple(query.shape)}, got {tuple(conf.shape)}")
+    if labels is not None:
+        nl = labels.shape[0] if labels.dim() == 2 else -1
+        if labels.dim() != 2 or labels.shape[1] != database.shape[0]:
+            raise RuntimeError(f"stlpose pose_rank: labels must be [L, N={database.shape[0]}], got {tuple(labels.shape)}")
+        if qlabels is None or tuple(qlabels.shape) != (nl, query.shape[0]):
+            raise RuntimeError(f"stlpose pose_rank: qlabels must be [L={nl}, Q={query.shape[0]}], got "
+                               f"{None if qlabels is None else tuple(qlabels.shape)}")
+    _same_device((("database", database), ("confidence", conf), ("labels", labels), ("qlabels", qlabels)), query.device)
+
+
+def _pose_args(query, conf, database, method, penalization):
+    _check_pose_shapes(query, conf, database)
+    q, db = query.contiguous().float(), database.contiguous().float()
+    c = conf.contiguous().float() if conf is not None else None
+    return q, c, db, capi.POSE_METHOD.get(method, -1), capi.POSE_PEN.get(penalization, -1)
+
+
+def _ptr(t):
+    return t.data_ptr() if t is not None else None
+
+
+def _pose_vectors(joints: torch.Tensor, approach: str, normalize: bool) -> torch.Tensor:
+    if joints.dim() != 3 or joints.shape[1] != 17 or joints.shape[2] < 2:
+        raise RuntimeError(f"stlpose pose_vectors: joints must be [N, 17, C >= 2], got {tuple(joints.shape)}")
+    j = joints.contiguous().float()
+    n = j.shape[0]
+    out = torch.empty(n, capi.POSE_DIM.get(approach, 34), dtype=torch.float32, device=j.device)
+    # row stride from the shape: a contiguous tensor may report any stride for a size-1 batch dimension
+    capi.call("stl_pose_vectors", j.data_ptr(), j.shape[1] * j.shape[2], j.shape[2], out.data_ptr(), n, capi.POSE_APPROACH.get(approach, -1),
+              int(normalize), _st())
+    return out
+
+
+_define("pose_vectors(Tensor joints, str approach, bool normalize) -> Tensor", _pose_vectors,
+        lambda j, approach, normalize: j.new_empty(j.shape[0], capi.POSE_DIM.get(approach, 34), dtype=torch.float32))
+
+
+def _pose_distances(query, conf, database, method: str, penalization: str) -> torch.Tensor:
+    q, c, db, m, p = _pose_args(query, conf, database, method, penalization)
+    out = torch.empty(q.shape[0], db.shape[0], dtype=torch.float32, device=q.device)
+    capi.call("stl_pose_distances", q.data_ptr(), _ptr(c), db.data_ptr(), out.data_ptr(), q.shape[0], db.shape[0], q.shape[1], m, p,
+              _st())
+    return out
+
+
+_define("pose_distances(Tensor query, Tensor? conf, Tensor database, str method, str penalization) -> Tensor", _pose_distances,
+        lambda q, c, db, m, p: q.new_empty(q.shape[0], db.shape[0], dtype=torch.float32))
+
+
+def _pose_topk(query, conf, database, method: str, penalization: str, k: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    q, c, db, m, p = _pose_args(query, conf, database, method, penalization)
+    nq, n, d = q.shape[0], db.shape[0], q.shape[1]
+    need = capi.lib().stl_pose_topk_workspace(nq, n, k, d)
+    capi.check(min(need, 0), "stl_pose_topk")
+    work = torch.empty(max(need, 8), dtype=torch.uint8, device=q.device)
+    idx = torch.empty(nq, k, dtype=torch.int64, device=q.device)
+    dist = torch.empty(nq, k, dtype=torch.float32, device=q.device)
+    capi.call("stl_pose_topk", q.data_ptr(), _ptr(c), db.data_ptr(), nq, n, d, m, p, k, idx.data_ptr(), dist.data_ptr(), work.data_ptr(),
+              work.numel(), _st())
+    return idx, dist
+
+
+_define("pose_topk(Tensor query, Tensor? conf, Tensor database, str method, str penalization, int k) -> (Tensor, Tensor)", _pose_topk,
+        lambda q, c, db, m, p, k: (q.new_empty(q.shape[0], k, dtype=torch.int64), q.new_empty(q.shape[0], k, dtype=torch.float32)))
+
+
+def _pose_rank(query, conf, database, method: str, penalization: str, k_out: int, labels, qlabels, k_eff: int):
+    _check_pose_shapes(query, conf, database, labels, qlabels)
+    q, c, db, m, p = _pose_args(query, conf, database, method, penalization)
+    nq, n, d = q.shape[0], db.shape[0], q.shape[1]
+    idx = torch.empty(nq, k_out, dtype=torch.int64, device=q.device)
+    dist = torch.empty(nq, k_out, dtype=torch.float32, device=q.device)
+    lab = labels.contiguous().to(torch.int32) if labels is not None else None
+    qlab = qlabels.contiguous().to(torch.int32) if qlabels is not None else None
+    nl = lab.shape[0] if lab is not None else 0
+    scores = torch.empty(nq, nl, capi.POSE_NSCORES, dtype=torch.float64, device=q.device)
+    capi.call("stl_pose_rank", q.data_ptr(), _ptr(c), db.data_ptr(), nq, n, d, m, p, k_out, idx.data_ptr(), dist.data_ptr(), _ptr(lab),
+              _ptr(qlab), nl, k_eff, scores.data_ptr(), _st())
+    return idx, dist, scores
+
+
+def _pose_rank_fake(q, c, db, m, p, k_out, labels, qlabels, k_eff):
+    nl = labels.shape[0] if labels is not None else 0
+    return (q.new_empty(q.shape[0], k_out, dtype=torch.int64), q.new_empty(q.shape[0], k_out, dtype=torch.float32),
+            q.new_empty(q.shape[0], nl, capi.POSE_NSCORES, dtype=torch.float64))
+
+
+_define("pose_rank(Tensor query, Tensor? conf, Tensor database, str method, str penalization, int k_out, Tensor? labels, "
+        "Tensor? qlabels, int k_eff) -> (Tensor, Tensor, Tensor)", _pose_rank, _pose_rank_fake)
+
 OPS = ["person_mse", "heatmap_argmax", "final_preds", "flip_merge", "flip_merge_backward", "gaussian_targets", "affine_crop",
-       "hrnet_forward", "hrnet_backward", "hrnet_backward_input"]
+       "hrnet_forward", "hrnet_backward", "hrnet_backward_input", "pose_vectors", "pose_distances", "pose_topk", "pose_rank"]
