@@ -290,6 +290,17 @@ int stl_l1_partial(int dtype, const void* a, const void* b, int64_t n, double* p
                    void* stream); /* partial[i] = sum |a-b| over block i's share */
 /* Same with squared differences (content / Gram MSE of the VGG19 style loss, V2 -- no reference counterpart). */
 int stl_l2_partial(int dtype, const void* a, const void* b, int64_t n, double* partial, int nblk, void* stream);
+/* Image gradient of the VGG19 style loss (V2; stlpose_amd/vgg19_style.py, stylise.py).  Adjoint of stl_maxpool2x2
+ * (max_pool2d backward, 2x2 / stride 2, floor mode): x = the pool's input [B,H,W,C], dy = gradient of its output
+ * [B,H/2,W/2,C] -> dx [B,H,W,C], every element written.  Each window's gradient goes to its FIRST maximum in row-major order
+ * (a later element wins only if strictly greater, or NaN: torch CPU's rule); the row / column an odd H / W drops gets 0;
+ * mask != 0 also zeroes dx where x <= 0 (the ReLU in front of the pool, whose output x is).  Gather form: no atomics,
+ * deterministic.  dtype STL_F32 or STL_BF16; C % 8 == 0. */
+int stl_maxpool2x2_backward(int dtype, const void* x, const void* dy, void* dx, int B, int H, int W, int C, int mask, void* stream);
+/* Adjoint of the content term at one tap, in place: g += scale[0] * (a - b) over n elements (n % 8 == 0), then, if mask != 0,
+ * g = 0 where a <= 0 (the ReLU whose output a is).  scale is a DEVICE float (content weight of the backward pass * 2 / n of the
+ * MSE), read by the kernel.  dtype STL_F32 or STL_BF16. */
+int stl_l2_backward(int dtype, const void* a, const void* b, void* g, int64_t n, const float* scale, int mask, void* stream);
 int stl_bilinear_nchw(const float* in, float* out, int B, int C, int H, int W, int Ho, int Wo,
                       void* stream); /* F.interpolate(mode='bilinear', align_corners=False) */
 int stl_sum_partials(const double* partial, int n, double scale, float* out, int accumulate, void* stream);

@@ -5,6 +5,8 @@ from .loss import PersonMSELoss, apply_perceptual_loss  # noqa: F401,E402
 from .inference import forward_pass  # noqa: F401,E402
 from .pose_parsing import get_max_preds_hrnet, get_final_preds_hrnet, accuracy  # noqa: F401,E402
 from .vgg import VGGPerceptualLoss  # noqa: F401,E402
+from .vgg19_style import VGG19StyleLoss  # noqa: F401,E402
+from .stylise import GatysStylizer  # noqa: F401,E402
 from .pose_database import (PoseIndex, process_pose_vector, process_pose_vectors, get_neighbors_idxs,  # noqa: F401,E402
                             get_penalization_metric, fit_knn_structure, load_knn)
 from .retrieval import score_retrievals, retrieval_experiment, process_retrieval_results  # noqa: F401,E402

@@ -1074,6 +1074,73 @@ __global__ __launch_bounds__(256) void maxpool_kernel(const void* x, void* out, 
     }
 }
 
+// Adjoint of maxpool_kernel (torch CPU's max_pool2d backward for a 2x2 / stride-2 window, floor mode), gather form: thread v owns
+// the 2x2 input window (wy, wx) over 8 channels -- every input pixel has exactly one owner -- finds per channel the window's first
+// maximum in row-major order (a later element wins only if strictly greater, or NaN: torch CPU's tie rule), writes dy there and 0
+// at the other three.  Windows the floor drops (row H-1 of an odd H, column W-1 of an odd W) are written 0.  mask != 0: also 0
+// where x <= 0 (the ReLU whose output x is).  No atomics, every element written once: deterministic.
+template <typename T>
+__global__ __launch_bounds__(256) void maxpool_bwd_kernel(const void* x, const void* dy, void* dx, int B, int H, int W, int C, int mask) {
+    const int Ho = H >> 1, Wo = W >> 1, Hc = (H + 1) >> 1, Wc = (W + 1) >> 1, VPC = C >> 3;
+    const size_t total = (size_t)B * Hc * Wc * VPC;
+    for (size_t v = (size_t)blockIdx.x * 256 + threadIdx.x; v < total; v += (size_t)gridDim.x * 256) {
+        const size_t pi = v / VPC;
+        const int c0 = (int)(v - pi * VPC) * 8;
+        const int wx = (int)(pi % Wc);
+        const size_t by = pi / Wc;
+        const int wy = (int)(by % Hc), b = (int)(by / Hc);
+        const size_t e00 = (((size_t)b * H + 2 * wy) * W + 2 * wx) * C + c0;
+        if (wy < Ho && wx < Wo) {
+            float f[4][8], g[8];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) load8<T>(x, e00 + ((size_t)(k >> 1) * W + (k & 1)) * C, f[k]);
+            load8<T>(dy, (((size_t)b * Ho + wy) * Wo + wx) * C + c0, g);
+            int idx[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                float m = f[0][j];
+                idx[j] = 0;
+#pragma unroll
+                for (int k = 1; k < 4; ++k)
+                    if (f[k][j] > m || isnan(f[k][j])) m = f[k][j], idx[j] = k;
+            }
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                float o[8];
+#pragma unroll
+                for (int j = 0; j < 8; ++j) o[j] = (idx[j] == k && (!mask || f[k][j] > 0.f)) ? g[j] : 0.f;
+                store8<T>(dx, e00 + ((size_t)(k >> 1) * W + (k & 1)) * C, o);
+            }
+        } else {   // a dropped edge window: one or two pixels
+            float z[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) z[j] = 0.f;
+            const int ny = min(2, H - 2 * wy), nx = min(2, W - 2 * wx);
+            for (int u = 0; u < ny; ++u)
+                for (int w = 0; w < nx; ++w) store8<T>(dx, e00 + ((size_t)u * W + w) * C, z);
+        }
+    }
+}
+
+// Adjoint of the content MSE at one tap: g += scale * (a - b), then (mask != 0) g = 0 where a <= 0, the ReLU whose output a is.
+// In place on g; scale is a DEVICE scalar (the loss weight of the backward pass times 2 / n), so no host round trip.
+template <typename T>
+__global__ __launch_bounds__(256) void l2_bwd_kernel(const void* a, const void* b, void* g, size_t nvec, const float* scale, int mask) {
+    const float s = *scale;
+    for (size_t v = (size_t)blockIdx.x * 256 + threadIdx.x; v < nvec; v += (size_t)gridDim.x * 256) {
+        float x[8], y[8], d[8];
+        load8<T>(a, v * 8, x);
+        load8<T>(b, v * 8, y);
+        load8<T>(g, v * 8, d);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            d[j] += s * (x[j] - y[j]);
+            if (mask && !(x[j] > 0.f)) d[j] = 0.f;
+        }
+        store8<T>(g, v * 8, d);
+    }
+}
+
 template <typename T, bool SQ>
 __global__ __launch_bounds__(256) void l1_kernel(const void* a, const void* b, size_t nvec, double* partial) {
     double acc = 0.0;
@@ -1563,6 +1630,32 @@ extern "C" int stl_maxpool2x2(int dtype, const void* x, void* out, int B, int H,
     else
         STL_LAUNCH(maxpool_kernel<float>, dim3(nblocks_for(total, 256, 4096)), dim3(256), 0, ST, x, out, B, H, W, C);
     STL_LAUNCH_CHECK("maxpool2x2");
+    return 0;
+}
+
+extern "C" int stl_maxpool2x2_backward(int dtype, const void* x, const void* dy, void* dx, int B, int H, int W, int C, int mask,
+                                       void* stream) {
+    STL_CHECK(x && dy && dx && B > 0, "maxpool2x2_backward: bad arguments");
+    STL_CHECK(C % 8 == 0 && H >= 2 && W >= 2, "maxpool2x2_backward: C%%8 == 0 and H, W >= 2 required");
+    STL_CHECK(dtype == STL_F32 || dtype == STL_BF16, "maxpool2x2_backward: dtype %d (fp32 or bf16)", dtype);
+    const size_t total = (size_t)B * ((H + 1) / 2) * ((W + 1) / 2) * (C / 8);
+    if (dtype == STL_BF16)
+        STL_LAUNCH(maxpool_bwd_kernel<__bf16>, dim3(nblocks_for(total, 256, 4096)), dim3(256), 0, ST, x, dy, dx, B, H, W, C, mask);
+    else
+        STL_LAUNCH(maxpool_bwd_kernel<float>, dim3(nblocks_for(total, 256, 4096)), dim3(256), 0, ST, x, dy, dx, B, H, W, C, mask);
+    STL_LAUNCH_CHECK("maxpool2x2_backward");
+    return 0;
+}
+
+extern "C" int stl_l2_backward(int dtype, const void* a, const void* b, void* g, int64_t n, const float* scale, int mask, void* stream) {
+    STL_CHECK(a && b && g && scale && n > 0 && n % 8 == 0, "l2_backward: bad arguments (n %% 8 == 0 required)");
+    STL_CHECK(dtype == STL_F32 || dtype == STL_BF16, "l2_backward: dtype %d (fp32 or bf16)", dtype);
+    const size_t nvec = (size_t)n / 8;
+    if (dtype == STL_BF16)
+        STL_LAUNCH(l2_bwd_kernel<__bf16>, dim3(nblocks_for(nvec, 256, 4096)), dim3(256), 0, ST, a, b, g, nvec, scale, mask);
+    else
+        STL_LAUNCH(l2_bwd_kernel<float>, dim3(nblocks_for(nvec, 256, 4096)), dim3(256), 0, ST, a, b, g, nvec, scale, mask);
+    STL_LAUNCH_CHECK("l2_backward");
     return 0;
 }
 

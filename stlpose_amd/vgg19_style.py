@@ -13,6 +13,12 @@ ImageNet normalisation fused into the patch kernel), 2x2 max-pools, and every Gr
 the MFMA weight-gradient kernel run as a 1x1 "convolution" of the NHWC feature map with itself
 (dw[c1][c2] = sum_pixels F[p][c1] F[p][c2]: K = pixels, transposed LDS reads, split-K slabs), one launch per image
 and tap.  The content term is a two-level fp64 reduction of squared differences (``stl_l2_partial``).
+
+Differentiable in the stylised images: with ``x.requires_grad`` the plan (keyed by a grad flag; without it the plan and its launches
+are exactly the forward ones) also holds the image gradient of images [0, B) -- 13 data gradients on the transposed weights with
+the ReLU masks in their epilogue (``mask_z``), the max-pool adjoints (``stl_maxpool2x2_backward``), per image and style tap a 1x1
+conv with weight 4 / (B C^3 HW) * (G_b - A_b) whose epilogue adds the gradient from deeper layers, the content term
+(``stl_l2_backward``) and the patch adjoint (``stl_patch3x3_backward``) to the NCHW image.
 """
 from __future__ import annotations
 
@@ -43,17 +49,34 @@ def vgg19_flops_per_image(H: int, W: int) -> float:
     return fl
 
 
+def _run(ops, st) -> None:
+    lib = capi.lib()
+    for name, args in ops:
+        rc = getattr(lib, name)(*args, st)
+        if rc != 0:
+            raise RuntimeError(f"{name}: {lib.stl_last_error().decode()}")
+
+
 class _Plan:
-    def __init__(self, mod: "VGG19StyleLoss", B3: int, H: int, W: int, dev):
+    """The native launches of one batch geometry.
+
+    nb images of H x W run as one batch.  content = "batch": the content term compares images [0, B) with [B, 2B) of the batch
+    (VGG19StyleLoss: stylised, content, style); "buffer": with the relu4_2 features in ``self.ctarget`` (the stylisation driver's
+    cached targets); None: no content term.  gram_imgs: the images whose Gram matrices are formed, in slab order.
+    grad: also plan the image gradient of images [0, B) (``self.bwd_ops``); a plan without it is exactly the forward plan."""
+
+    def __init__(self, mod: "VGG19StyleLoss", nb: int, H: int, W: int, dev, B: int, content: Optional[str], gram_imgs,
+                 grad: bool = False):
         self.ops, self.keep = [], []
+        self.B, self.H, self.W = B, H, W
         dt, esz = mod.dtype, (2 if mod.dtype == capi.BF16 else 4)
+        self.dt, self.esz = dt, esz
         tdt = torch.bfloat16 if dt == capi.BF16 else torch.float32
-        B = B3 // 3
-        self.img = torch.zeros(B3, 3, H, W, device=dev)
+        self.img = torch.zeros(nb, 3, H, W, device=dev)
         nconv = len(VGG19_LAYOUT)
         tab = (capi.WPrep * nconv)()
         src = fwd = blk = 0
-        offs = []
+        offs, boffs = [], []
         for i, (_, ci, co, _) in enumerate(VGG19_LAYOUT):
             patch = i == 0
             cip, kk = (32, 1) if patch else (ci, 9)
@@ -64,43 +87,58 @@ class _Plan:
             src += co * ci * 9
             fwd += co * kk * cip
             blk += math.ceil(co * ci * 9 / 1024)
+        if grad:   # data-gradient layouts behind the forward ones: [Ci][flipped tap][Co], conv1_1 [kk][Co] over 32 patch rows
+            for i, (_, ci, co, _) in enumerate(VGG19_LAYOUT):
+                cip, kk = (32, 1) if i == 0 else (ci, 9)
+                tab[i].bwd_off = fwd
+                boffs.append(fwd)
+                fwd += co * kk * cip
         self.wk = torch.zeros(fwd, dtype=tdt, device=dev)
         self.wtab = torch.frombuffer(bytearray(bytes(tab)), dtype=torch.uint8).clone().to(dev)
         self.wblocks, self.nconv = blk, nconv
         self.cpartial = torch.zeros(1024, dtype=torch.float64, device=dev)
         self.content = torch.zeros((), dtype=torch.float32, device=dev)
-        self.grams = []   # per style tap: (slabs [2B, nsplit, C, C] fp32, 1 / (C H W))
+        self.grams = []   # per style tap: (slabs [len(gram_imgs), nsplit, C, C] fp32, 1 / (C H W))
+        self.acts, self.dims = [], []   # per conv: post-ReLU output [nb, h, w, co], (h, w, co)
 
         def act(b, h, w, c):
             t = torch.empty(b * h * w * c * esz, dtype=torch.uint8, device=dev)
             self.keep.append(t)
             return t
 
-        x = act(B3, H, W, 32)
-        self.ops.append(("stl_patch3x3", (dt, self.img.data_ptr(), x.data_ptr(), B3, H, W, 1, mod.mean.data_ptr(), mod.std.data_ptr())))
+        x = act(nb, H, W, 32)
+        self.ops.append(("stl_patch3x3", (dt, self.img.data_ptr(), x.data_ptr(), nb, H, W, 1, mod.mean.data_ptr(), mod.std.data_ptr())))
         h, w, c = H, W, 32
         for i, (_, ci, co, pool) in enumerate(VGG19_LAYOUT):
             if pool:
-                y = act(B3, h // 2, w // 2, c)
-                self.ops.append(("stl_maxpool2x2", (dt, x.data_ptr(), y.data_ptr(), B3, h, w, c)))
+                y = act(nb, h // 2, w // 2, c)
+                self.ops.append(("stl_maxpool2x2", (dt, x.data_ptr(), y.data_ptr(), nb, h, w, c)))
                 x, h, w = y, h // 2, w // 2
             p = capi.Conv()
-            p.dtype, p.B, p.Hi, p.Wi, p.Ci, p.Ho, p.Wo, p.Co = dt, B3, h, w, c, h, w, co
+            p.dtype, p.B, p.Hi, p.Wi, p.Ci, p.Ho, p.Wo, p.Co = dt, nb, h, w, c, h, w, co
             p.ks, p.stride, p.shape = (1 if i == 0 else 3), 1, -1
             p.src.x, p.src.mode = x.data_ptr(), capi.SRC_PLAIN
-            y = act(B3, h, w, co)
+            y = act(nb, h, w, co)
             p.w = self.wk.data_ptr() + offs[i] * esz
             p.out, p.bias, p.out_relu = y.data_ptr(), mod.bias_flat.data_ptr() + 4 * mod.bias_off[i], 1
             capi.call("stl_conv_plan", C.byref(p))
             self.keep.append(p)
             self.ops.append(("stl_conv_forward", (C.byref(p),)))
             x, c = y, co
+            self.acts.append(y)
+            self.dims.append((h, w, c))
             img_elems = h * w * c
-            if i == CONTENT_TAP:   # images [0, B) = stylised, [B, 2B) = content
+            if i == CONTENT_TAP and content is not None:   # images [0, B) = stylised; target: images [B, 2B) or the cached buffer
                 n = B * img_elems
-                self.ops.append(("stl_l2_partial", (dt, x.data_ptr(), x.data_ptr() + n * esz, n, self.cpartial.data_ptr(), 1024)))
+                if content == "batch":
+                    tgt = x.data_ptr() + n * esz
+                else:
+                    self.ctarget = torch.zeros(n, dtype=tdt, device=dev)
+                    tgt = self.ctarget.data_ptr()
+                self.ops.append(("stl_l2_partial", (dt, x.data_ptr(), tgt, n, self.cpartial.data_ptr(), 1024)))
                 self.ops.append(("stl_sum_partials", (self.cpartial.data_ptr(), 1024, 1.0 / n, self.content.data_ptr(), 0)))
-            if i in STYLE_TAPS:    # Gram of the stylised images [0, B) and the style images [2B, 3B)
+                self.ctarget_ptr = tgt
+            if i in STYLE_TAPS and len(gram_imgs):
                 from .engine import choose_tile
                 th, tw = choose_tile(1, h, w, 1, 1, esz, bn_cols=32, maxhalo=576)
                 npt = math.ceil((h + 1) / th) * math.ceil(w / tw)
@@ -109,8 +147,8 @@ class _Plan:
                 ctile = capi.lib().stl_wgrad_chunk(C.byref(wg0))
                 chunks = math.ceil(c / ctile) ** 2
                 nsplit = max(1, min(npt, max(1, 256 // chunks)))
-                slabs = torch.zeros(2 * B, nsplit, c, c, dtype=torch.float32, device=dev)
-                for j, b in enumerate(list(range(B)) + list(range(2 * B, 3 * B))):
+                slabs = torch.zeros(len(gram_imgs), nsplit, c, c, dtype=torch.float32, device=dev)
+                for j, b in enumerate(gram_imgs):
                     wg = capi.Wgrad()
                     wg.dtype, wg.B, wg.Hi, wg.Wi, wg.Ci, wg.Ho, wg.Wo, wg.Co, wg.ks, wg.stride = dt, 1, h, w, c, h, w, c, 1, 1
                     wg.TH, wg.TW, wg.nsplit = th, tw, nsplit
@@ -120,6 +158,122 @@ class _Plan:
                     self.keep.append(wg)
                     self.ops.append(("stl_conv_wgrad", (C.byref(wg),)))
                 self.grams.append((slabs, 1.0 / (c * h * w)))
+        if grad:
+            self._plan_backward(mod, dev, tdt, boffs)
+
+    def _conv(self, B, h, w, ci, co, ks, src, wptr, out, addend=0, mask_z=0) -> None:
+        p = capi.Conv()
+        p.dtype, p.B, p.Hi, p.Wi, p.Ci, p.Ho, p.Wo, p.Co = self.dt, B, h, w, ci, h, w, co
+        p.ks, p.stride, p.shape = ks, 1, -1
+        p.src.x, p.src.mode = src, capi.SRC_PLAIN
+        p.w, p.out = wptr, out
+        if addend:
+            p.addend = addend
+        if mask_z:
+            p.mask_z = mask_z
+        capi.call("stl_conv_plan", C.byref(p))
+        self.keep.append(p)
+        self.bwd_ops.append(("stl_conv_forward", (C.byref(p),)))
+
+    def _plan_backward(self, mod, dev, tdt, boffs) -> None:
+        """Image gradient of images [0, B): the 13 data gradients (stl_conv_forward on the transposed weights, ReLU masks from
+        the stored outputs as mask_z), the max-pool adjoints, the Gram terms (a 1x1 conv per image and tap with the weight
+        ks * (G_b - A_b), the gradient from deeper layers as addend), the content term (stl_l2_backward, in place) and the patch
+        adjoint.  Gradients ping-pong between two buffers per resolution."""
+        B, dt, esz = self.B, self.dt, self.esz
+        self.bwd_ops = []
+        self.cscale = torch.zeros((), dtype=torch.float32, device=dev)   # 2 wc / n, set by backward()
+        self.gw = {}                                                     # style tap -> [B, C, C] weight ks * (G_b - A_b)
+        self.dimg = torch.zeros(B, 3, self.H, self.W, dtype=torch.float32, device=dev)
+        bufs = self.gbufs = {}   # (h, w) -> two buffers; held by the plan: the ops keep raw pointers into them
+
+        def other(h, w, g):   # a gradient buffer of resolution (h, w) that is not g; two per resolution, sized for its widest use
+            if (h, w) not in bufs:
+                cmax = max(max(ci, co) for (hh, ww, _), (_, ci, co, _) in zip(self.dims, VGG19_LAYOUT) if (hh, ww) == (h, w))
+                bufs[(h, w)] = [torch.empty(B * h * w * max(cmax, 32) * esz, dtype=torch.uint8, device=dev) for _ in range(2)]
+            a, b = (t.data_ptr() for t in bufs[(h, w)])
+            return b if g == a else a
+
+        g = None   # gradient w.r.t. the output F_i of layer i; ReLU mask applied unless layer i is a style or the content tap
+        for i in range(len(VGG19_LAYOUT) - 1, -1, -1):
+            h, w, c = self.dims[i]
+            f, pix = self.acts[i].data_ptr(), h * w * c * esz
+            if i in STYLE_TAPS:   # (gF_i + ks (G_b - A_b) F_b) * (F_b > 0): a 1x1 conv per image, gF_i from layer i + 1 as addend
+                wgt = torch.zeros(B, c, c, dtype=tdt, device=dev)
+                self.gw[i] = wgt
+                out = other(h, w, g)
+                for b in range(B):
+                    self._conv(1, h, w, c, c, 1, f + b * pix, wgt[b].data_ptr(), out + b * pix,
+                               addend=(g + b * pix) if g is not None else 0, mask_z=f + b * pix)
+                g = out
+            elif i == CONTENT_TAP:   # + wc * 2 (F_x - F_c) / n, then the ReLU mask, in place
+                self.bwd_ops.append(("stl_l2_backward", (dt, f, self.ctarget_ptr, g, B * h * w * c, self.cscale.data_ptr(), 1)))
+            _, ci, co, pool = VGG19_LAYOUT[i]
+            out = other(h, w, g)
+            if i == 0:   # conv1_1: 1x1 onto the 32-wide patches, then the patch adjoint (with 1 / std) to the NCHW image
+                self._conv(B, h, w, co, 32, 1, g, self.wk.data_ptr() + boffs[0] * esz, out)
+                self.bwd_ops.append(("stl_patch3x3_backward", (dt, out, self.dimg.data_ptr(), B, self.H, self.W, 1, mod.std.data_ptr())))
+                break
+            hp, wp, cp = self.dims[i - 1]
+            fp = self.acts[i - 1].data_ptr()
+            masked = i - 1 not in STYLE_TAPS and i - 1 != CONTENT_TAP   # else the tap masks after adding its own term
+            self._conv(B, h, w, co, ci, 3, g, self.wk.data_ptr() + boffs[i] * esz, out, mask_z=fp if masked and not pool else 0)
+            if pool:
+                dst = other(hp, wp, None)
+                self.bwd_ops.append(("stl_maxpool2x2_backward", (dt, fp, out, dst, B, hp, wp, cp, int(masked))))
+                out = dst
+            g = out
+
+    def backward(self, grams, wc, ws) -> torch.Tensor:
+        """Image gradient [B, 3, H, W] fp32 for loss weights wc (content) and ws (style): floats or device scalars.
+        grams: per style tap (G [B, C, C], A [B or 1, C, C]) fp64 from the forward pass."""
+        B = self.B
+        for i, (G, A) in zip(STYLE_TAPS, grams):
+            h, w, c = self.dims[i]
+            ks = 4.0 / (B * float(c) ** 3 * h * w)
+            self.gw[i].copy_((G - A) * (ws * ks))
+        h, w, c = self.dims[CONTENT_TAP]
+        if isinstance(wc, torch.Tensor):
+            self.cscale.copy_(wc * (2.0 / (B * h * w * c)))
+        else:
+            self.cscale.fill_(wc * 2.0 / (B * h * w * c))
+        _run(self.bwd_ops, torch.cuda.current_stream().cuda_stream)
+        return self.dimg
+
+
+def effective_weights(g_total, g_c, g_s, content_weight: float, style_weight: float):
+    """Loss weights (wc, ws) of the content and style terms for the incoming gradients of (total, content, style), with
+    total = content_weight * content + style_weight * style: c_loss.backward() alone and total.backward() both come out right."""
+    return g_total * content_weight + g_c, g_total * style_weight + g_s
+
+
+class _Backward:
+    """What the backward pass of one forward call needs: the plan (its stored activations), the Gram matrices, the loss weights."""
+
+    def __init__(self, mod, plan, gen, grams):
+        self.plan, self.gen, self.grams = plan, gen, grams
+        self.cw, self.sw = mod.content_weight, mod.style_weight
+
+    def __call__(self, g_total, g_c, g_s) -> torch.Tensor:
+        if self.plan.generation != self.gen:
+            raise RuntimeError("VGG19StyleLoss: the module ran forward again on this geometry before this backward; "
+                               "call backward() before the next forward")
+        wc, ws = effective_weights(g_total, g_c, g_s, self.cw, self.sw)
+        return self.plan.backward(self.grams, wc, ws).clone()
+
+
+class _StyleLossFn(torch.autograd.Function):
+    """x -> (total, content, style) with the native image gradient; the losses are computed by the caller's forward launch."""
+
+    @staticmethod
+    def forward(ctx, x, losses, bwd):
+        ctx.bwd = bwd
+        ctx.xdtype = x.dtype
+        return tuple(t.detach().clone() for t in losses)
+
+    @staticmethod
+    def backward(ctx, g_total, g_c, g_s):
+        return ctx.bwd(g_total, g_c, g_s).to(ctx.xdtype), None, None
 
 
 class VGG19StyleLoss(nn.Module):
@@ -157,35 +311,44 @@ class VGG19StyleLoss(nn.Module):
         self._flat_dev = dev
         self._plans.clear()
 
-    def forward(self, x: torch.Tensor, content: torch.Tensor, style: torch.Tensor):
-        if not x.is_cuda:
-            raise RuntimeError("stlpose_amd.VGG19StyleLoss runs only on an MI355X (cuda/HIP device); there is no CPU path")
-        dev = x.device
+    def _ready(self, dev) -> None:
         if self.mean.device != dev:
             self.to(dev)
         if self._flat_dev != dev:
             self._pack(dev)
+
+    def forward(self, x: torch.Tensor, content: torch.Tensor, style: torch.Tensor):
+        if not x.is_cuda:
+            raise RuntimeError("stlpose_amd.VGG19StyleLoss runs only on an MI355X (cuda/HIP device); there is no CPU path")
+        dev = x.device
+        self._ready(dev)
         st = torch.cuda.current_stream().cuda_stream
-        xin = torch.cat([x, content.to(dev), style.to(dev)], 0).contiguous().float()
+        grad = torch.is_grad_enabled() and x.requires_grad
+        if grad and (content.requires_grad or style.requires_grad):
+            raise NotImplementedError("VGG19StyleLoss differentiates the stylised images only: content and style must not require grad")
+        xin = torch.cat([x.detach(), content.detach().to(dev), style.detach().to(dev)], 0).contiguous().float()
         B3, ch, H, W = xin.shape
         if ch != 3 or B3 % 3 or H < 16 or W < 16:
             raise RuntimeError(f"VGG19StyleLoss needs three equal batches of (B, 3, H >= 16, W >= 16) images, got {tuple(xin.shape)}")
-        plan = self._plans.get((B3, H, W))
+        B = B3 // 3
+        key = (B3, H, W, grad)
+        plan = self._plans.get(key)
         if plan is None:
-            plan = self._plans[(B3, H, W)] = _Plan(self, B3, H, W, dev)
+            plan = self._plans[key] = _Plan(self, B3, H, W, dev, B, "batch", list(range(B)) + list(range(2 * B, 3 * B)), grad)
         plan.img.copy_(xin)
         capi.call("stl_weight_prep", self.dtype, self.w_flat.data_ptr(), plan.wk.data_ptr(), plan.wtab.data_ptr(), plan.nconv, plan.wblocks, st)
-        lib = capi.lib()
-        for name, args in plan.ops:
-            rc = getattr(lib, name)(*args, st)
-            if rc != 0:
-                raise RuntimeError(f"{name}: {lib.stl_last_error().decode()}")
+        _run(plan.ops, st)
         # C x C Gram matrices: split-K slabs -> sum, scale, squared distance (a few hundred KB of bookkeeping)
-        B = B3 // 3
         s_loss = torch.zeros((), dtype=torch.float64, device=dev)
+        grams = []
         for slabs, scale in plan.grams:
             g = slabs.double().sum(1) * scale
             s_loss = s_loss + ((g[:B] - g[B:]) ** 2).mean()
+            grams.append((g[:B], g[B:]))
         s_loss = s_loss.float()
         c_loss = plan.content.clone()
-        return self.content_weight * c_loss + self.style_weight * s_loss, c_loss, s_loss
+        total = self.content_weight * c_loss + self.style_weight * s_loss
+        if not grad:
+            return total, c_loss, s_loss
+        plan.generation = gen = getattr(plan, "generation", 0) + 1
+        return _StyleLossFn.apply(x, (total, c_loss, s_loss), _Backward(self, plan, gen, grams))
