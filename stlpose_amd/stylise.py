@@ -14,8 +14,8 @@ from typing import Dict, List, Optional
 
 import torch
 
-from . import capi
-from .vgg19_style import CONTENT_TAP, VGG19StyleLoss, _Plan, _run
+from .vgg import ready
+from .vgg19_style import CONTENT_TAP, StylePlan, VGG19StyleLoss
 
 OPTIMIZERS = ("adam", "lbfgs", "sgd")
 
@@ -35,18 +35,13 @@ class GatysStylizer:
         self.losses: List[float] = []
 
     # ---------------------------------------------------------------- plans and targets
-    def _plan(self, dev, nb, H, W, content: Optional[str], grad: bool) -> _Plan:
+    def _plan(self, dev, nb, H, W, content: Optional[str], grad: bool) -> StylePlan:
         key = (nb, H, W, content, grad)
         plan = self._plans.get(key)
         if plan is None:
-            plan = self._plans[key] = _Plan(self.loss, nb, H, W, dev, nb, content, list(range(nb)), grad)
-            capi.call("stl_weight_prep", self.loss.dtype, self.loss.w_flat.data_ptr(), plan.wk.data_ptr(), plan.wtab.data_ptr(),
-                      plan.nconv, plan.wblocks, torch.cuda.current_stream().cuda_stream)
+            plan = self._plans[key] = StylePlan(self.loss, nb, H, W, dev, nb, content, list(range(nb)), grad)
+            plan.trunk.prep_weights(torch.cuda.current_stream().cuda_stream)
         return plan
-
-    @staticmethod
-    def _grams(plan: _Plan) -> List[torch.Tensor]:
-        return [slabs.double().sum(1) * scale for slabs, scale in plan.grams]
 
     def targets(self, content: torch.Tensor, style: torch.Tensor):
         """(iteration plan with the relu4_2 features of `content` cached in it, style Grams [Bs, C, C] fp64 per tap)."""
@@ -54,28 +49,28 @@ class GatysStylizer:
         B, _, H, W = content.shape
         st = torch.cuda.current_stream().cuda_stream
         it = self._plan(dev, B, H, W, "buffer", True)
-        it.img.copy_(content)
-        _run(it.ops, st)
-        it.ctarget.view(torch.uint8).copy_(it.acts[CONTENT_TAP])
+        it.trunk.img.copy_(content)
+        it.trunk.run(st)
+        it.ctarget.view(torch.uint8).copy_(it.trunk.acts[CONTENT_TAP])
         Bs, _, Hs, Ws = style.shape
         sp = self._plan(dev, Bs, Hs, Ws, None, False)
-        sp.img.copy_(style)
-        _run(sp.ops, st)
-        return it, self._grams(sp)
+        sp.trunk.img.copy_(style)
+        sp.trunk.run(st)
+        return it, sp.grams()
 
     # ---------------------------------------------------------------- one iteration, in two halves (tools/stylise_bench.py times them)
-    def forward_loss(self, it: _Plan, img: torch.Tensor, style_grams):
+    def forward_loss(self, it: StylePlan, img: torch.Tensor, style_grams):
         """Forward of the B images `img` against the cached targets: (total loss, per-tap (G, A)) on device."""
-        it.img.copy_(img)
-        _run(it.ops, torch.cuda.current_stream().cuda_stream)
+        it.trunk.img.copy_(img)
+        it.trunk.run(torch.cuda.current_stream().cuda_stream)
         s_loss = torch.zeros((), dtype=torch.float64, device=img.device)
         grams = []
-        for G, A in zip(self._grams(it), style_grams):
+        for G, A in zip(it.grams(), style_grams):
             s_loss = s_loss + ((G - A) ** 2).mean()
             grams.append((G, A))
         return self.content_weight * it.content + self.style_weight * s_loss.float(), grams
 
-    def image_grad(self, it: _Plan, grams) -> torch.Tensor:
+    def image_grad(self, it: StylePlan, grams) -> torch.Tensor:
         """d total / d img [B, 3, H, W] fp32 of the last forward_loss (a buffer of the plan, overwritten by the next call)."""
         return it.backward(grams, self.content_weight, self.style_weight)
 
@@ -98,7 +93,7 @@ class GatysStylizer:
             raise RuntimeError(f"GatysStylizer: content must be (B, 3, H >= 16, W >= 16), got {tuple(content.shape)}")
         if style.shape[1] != 3 or style.shape[0] not in (1, B) or min(style.shape[2:]) < 16:
             raise RuntimeError(f"GatysStylizer: style must be 1 or {B} images (3, H >= 16, W >= 16), got {tuple(style.shape)}")
-        self.loss._ready(dev)
+        ready(self.loss, dev)
         it, style_grams = self.targets(content, style)
         img = (content.clone() if init == "content" else torch.rand_like(content)).requires_grad_(True)
         img.grad = torch.zeros_like(img)

@@ -9,7 +9,8 @@ MI355X-first: input and target run as ONE batch of 2B through the implicit-GEMM 
 (bias + ReLU fused in its epilogue), conv1_1's 3 input channels are fed as 3x3 patches (normalise
 fused into the patch kernel) so that it is a 1x1 conv with K = 32, and each slice's L1 is a
 two-level fp64 reduction.  Forward only, like the reference (its VGG is frozen and never
-back-propagated through in-tree).
+back-propagated through in-tree).  The trunk's weight packing (``ready``) and launch plan (``Trunk``)
+serve the VGG19 losses of ``vgg19_style.py`` as well.
 
 The reference takes the weights from ``torchvision.models.vgg16(pretrained=True)`` (a download);
 here they come from a state_dict with the reference module's own key names
@@ -39,69 +40,117 @@ VGG16_LAYOUT = [
 SLICE_END = {1: 0, 3: 1, 6: 2, 9: 3}  # conv position (0-based) -> slice that ends after it
 
 
-def _dtype_code(name: str) -> int:
+def dtype_code(name: str) -> int:
     return capi.BF16 if name.lower() in ("bf16", "bfloat16") else capi.F32
 
 
-class _Plan:
-    """Static launch list for one (2B, H, W) shape."""
+def add_conv(parent: nn.Module, idx: int, ci: int, co: int) -> nn.Module:
+    """Register a frozen 3x3 conv's ``weight`` and ``bias`` as ``parent.<idx>``; returns the leaf."""
+    leaf = nn.Module()
+    leaf.register_parameter("weight", nn.Parameter(torch.zeros(co, ci, 3, 3), requires_grad=False))
+    leaf.register_parameter("bias", nn.Parameter(torch.zeros(co), requires_grad=False))
+    parent.add_module(str(idx), leaf)
+    return leaf
 
-    def __init__(self, mod: "VGGPerceptualLoss", B2: int, H: int, W: int, dev):
-        self.ops = []
-        self.keep = []
-        dt, esz = mod.dtype, (2 if mod.dtype == capi.BF16 else 4)
-        tdt = torch.bfloat16 if dt == capi.BF16 else torch.float32
-        self.img = torch.zeros(B2, 3, H, W, device=dev)
-        # weights in kernel layout + table
-        nconv = len(VGG16_LAYOUT)
-        tab = (capi.WPrep * nconv)()
-        src = fwd = blk = 0
-        offs = []
-        for i, (_, _, ci, co, _) in enumerate(VGG16_LAYOUT):
+
+def ready(mod: nn.Module, dev) -> None:
+    """Move a VGG loss to `dev` and pack the convs of ``mod._convs`` there in layout order: ``w_flat`` and ``bias_flat``
+    (fp32), ``bias_off`` (each conv's first bias).  A repack drops ``mod._plans``: their launches point into the old buffers."""
+    if mod.mean.device != dev:
+        mod.to(dev)
+    if mod._flat_dev != dev:
+        ws, bs, mod.bias_off = [], [], []
+        off = 0
+        for leaf in mod._convs:
+            ws.append(leaf.weight.detach().reshape(-1).float())
+            bs.append(leaf.bias.detach().float())
+            mod.bias_off.append(off)
+            off += leaf.bias.numel()
+        mod.w_flat = torch.cat(ws).to(dev).contiguous()
+        mod.bias_flat = torch.cat(bs).to(dev).contiguous()
+        mod._flat_dev = dev
+        mod._plans.clear()
+
+
+class Trunk:
+    """Static launch list of a VGG trunk for one batch geometry: nb images of H x W through the 3x3 convs
+    ``rows`` = [(cin, cout, 2x2 max-pool in front)] of a module packed by ``ready``, each with bias + ReLU.
+
+    ``hook(trunk, i)`` runs right after conv i is listed and may list launches of its own behind it.  grad: ``wk`` also
+    holds the data-gradient layouts of the convs behind the forward ones (``tab[i].bwd_off``).  The plan holds every
+    buffer its launches point into (``keep``)."""
+
+    def __init__(self, mod: nn.Module, rows, nb: int, H: int, W: int, dev, hook, grad: bool = False):
+        self.ops, self.keep, self.acts, self.dims = [], [], [], []   # acts, dims: per conv its output [nb, h, w, co], (h, w, co)
+        self.dt, self.esz = mod.dtype, (2 if mod.dtype == capi.BF16 else 4)
+        self.tdt = torch.bfloat16 if self.dt == capi.BF16 else torch.float32
+        self.w_flat = mod.w_flat
+        self.img = torch.zeros(nb, 3, H, W, device=dev)
+        # weights in kernel layout + table; conv1_1 is a 1x1 conv on 32-wide 3x3 patches ([Co][32], data gradient [32][Co])
+        self.nconv = len(rows)
+        self.tab = tab = (capi.WPrep * self.nconv)()
+        src = off = blk = 0
+        for i, (ci, co, _) in enumerate(rows):
             patch = i == 0
             cip, kk = (32, 1) if patch else (ci, 9)
             e = tab[i]
-            e.src_off, e.fwd_off, e.bwd_off = src, fwd, -1
+            e.src_off, e.fwd_off, e.bwd_off = src, off, -1
             e.Co, e.Ci, e.ks, e.Cip, e.patch, e.blk0 = co, ci, 3, cip, int(patch), blk
-            offs.append(fwd)
             src += co * ci * 9
-            fwd += co * kk * cip
+            off += co * kk * cip
             blk += math.ceil(co * ci * 9 / 1024)
-        self.wk = torch.zeros(fwd, dtype=tdt, device=dev)
+        if grad:   # [Ci][flipped tap][Co]: the forward layouts' sizes, in the same order, behind them
+            for e in tab:
+                e.bwd_off = off + e.fwd_off
+            off *= 2
+        self.wk = torch.zeros(off, dtype=self.tdt, device=dev)
         self.wtab = torch.frombuffer(bytearray(bytes(tab)), dtype=torch.uint8).clone().to(dev)
-        self.wblocks, self.nconv = blk, nconv
-        self.partial = torch.zeros(4, 1024, dtype=torch.float64, device=dev)
-        self.loss = torch.zeros((), dtype=torch.float32, device=dev)
+        self.wblocks = blk
 
         def act(b, h, w, c):
-            t = torch.empty(b * h * w * c * esz, dtype=torch.uint8, device=dev)
+            t = torch.empty(b * h * w * c * self.esz, dtype=torch.uint8, device=dev)
             self.keep.append(t)
             return t
 
-        x = act(B2, H, W, 32)
-        self.ops.append(("stl_patch3x3", (dt, self.img.data_ptr(), x.data_ptr(), B2, H, W, 1, mod.mean.data_ptr(), mod.std.data_ptr())))
+        x = act(nb, H, W, 32)
+        self.ops.append(("stl_patch3x3", (self.dt, self.img.data_ptr(), x.data_ptr(), nb, H, W, 1, mod.mean.data_ptr(), mod.std.data_ptr())))
         h, w, c = H, W, 32
-        for i, (_, _, ci, co, pool) in enumerate(VGG16_LAYOUT):
+        for i, (_, co, pool) in enumerate(rows):
             if pool:
-                y = act(B2, h // 2, w // 2, c)
-                self.ops.append(("stl_maxpool2x2", (dt, x.data_ptr(), y.data_ptr(), B2, h, w, c)))
+                y = act(nb, h // 2, w // 2, c)
+                self.ops.append(("stl_maxpool2x2", (self.dt, x.data_ptr(), y.data_ptr(), nb, h, w, c)))
                 x, h, w = y, h // 2, w // 2
-            p = capi.Conv()
-            p.dtype, p.B, p.Hi, p.Wi, p.Ci, p.Ho, p.Wo, p.Co = dt, B2, h, w, c, h, w, co
-            p.ks, p.stride, p.shape = (1 if i == 0 else 3), 1, -1
-            p.src.x, p.src.mode = x.data_ptr(), capi.SRC_PLAIN
-            y = act(B2, h, w, co)
-            p.w = self.wk.data_ptr() + offs[i] * esz
-            p.out, p.bias, p.out_relu = y.data_ptr(), mod.bias_flat.data_ptr() + 4 * mod.bias_off[i], 1
-            capi.call("stl_conv_plan", C.byref(p))
-            self.keep.append(p)
-            self.ops.append(("stl_conv_forward", (C.byref(p),)))
+            y = act(nb, h, w, co)
+            self.conv(self.ops, nb, h, w, c, co, 1 if i == 0 else 3, x.data_ptr(), self.wk.data_ptr() + tab[i].fwd_off * self.esz,
+                      y.data_ptr(), bias=mod.bias_flat.data_ptr() + 4 * mod.bias_off[i], out_relu=1)
             x, c = y, co
-            if i in SLICE_END:
-                s = SLICE_END[i]
-                half = (B2 // 2) * h * w * c
-                self.ops.append(("stl_l1_partial", (dt, x.data_ptr(), x.data_ptr() + half * esz, half, self.partial[s].data_ptr(), 1024)))
-                self.ops.append(("stl_sum_partials", (self.partial[s].data_ptr(), 1024, 1.0 / half, self.loss.data_ptr(), int(s > 0))))
+            self.acts.append(y)
+            self.dims.append((h, w, c))
+            hook(self, i)
+
+    def conv(self, ops, B, h, w, ci, co, ks, src, wptr, out, bias=0, out_relu=0, addend=0, mask_z=0) -> None:
+        """List a stride-1 'same' conv of the NHWC map at `src` onto `out`."""
+        p = capi.Conv()
+        p.dtype, p.B, p.Hi, p.Wi, p.Ci, p.Ho, p.Wo, p.Co = self.dt, B, h, w, ci, h, w, co
+        p.ks, p.stride, p.shape = ks, 1, -1
+        p.src.x, p.src.mode = src, capi.SRC_PLAIN
+        p.w, p.out, p.bias, p.out_relu, p.addend, p.mask_z = wptr, out, bias, out_relu, addend, mask_z
+        capi.call("stl_conv_plan", C.byref(p))
+        self.keep.append(p)
+        ops.append(("stl_conv_forward", (C.byref(p),)))
+
+    def prep_weights(self, st) -> None:
+        """``w_flat`` -> the kernel layouts in ``wk``."""
+        capi.call("stl_weight_prep", self.dt, self.w_flat.data_ptr(), self.wk.data_ptr(), self.wtab.data_ptr(), self.nconv,
+                  self.wblocks, st)
+
+    def run(self, st, ops=None) -> None:
+        """Launch `ops` (default: the forward list) on stream `st`."""
+        lib = capi.lib()
+        for name, args in self.ops if ops is None else ops:
+            rc = getattr(lib, name)(*args, st)
+            if rc != 0:
+                raise RuntimeError(f"{name}: {lib.stl_last_error().decode()}")
 
 
 class VGGPerceptualLoss(nn.Module):
@@ -109,13 +158,9 @@ class VGGPerceptualLoss(nn.Module):
                  compute_dtype: str = "fp32"):
         super().__init__()
         self.resize = resize
-        self.dtype = _dtype_code(compute_dtype)
+        self.dtype = dtype_code(compute_dtype)
         self.blocks = nn.ModuleList([nn.Module() for _ in range(4)])  # reference: self.blocks[s][features idx]
-        for s, idx, ci, co, _ in VGG16_LAYOUT:
-            leaf = nn.Module()
-            leaf.register_parameter("weight", nn.Parameter(torch.zeros(co, ci, 3, 3), requires_grad=False))
-            leaf.register_parameter("bias", nn.Parameter(torch.zeros(co), requires_grad=False))
-            self.blocks[s].add_module(str(idx), leaf)
+        self._convs = [add_conv(self.blocks[s], idx, ci, co) for s, idx, ci, co, _ in VGG16_LAYOUT]
         self.mean = nn.Parameter(torch.tensor([0.485, 0.456, 0.406]).view(1, 3, 1, 1))   # loss.py:37
         self.std = nn.Parameter(torch.tensor([0.229, 0.224, 0.225]).view(1, 3, 1, 1))    # loss.py:38
         self._plans: Dict = {}
@@ -126,8 +171,7 @@ class VGGPerceptualLoss(nn.Module):
     def load_vgg_weights(self, sd: Dict[str, torch.Tensor]):
         """Accepts torchvision's ``features.<idx>.*`` keys or the reference module's ``blocks.<s>.<idx>.*``."""
         with torch.no_grad():
-            for s, idx, _, _, _ in VGG16_LAYOUT:
-                leaf = getattr(self.blocks[s], str(idx))
+            for (s, idx, _, _, _), leaf in zip(VGG16_LAYOUT, self._convs):
                 for name in ("weight", "bias"):
                     t = sd.get(f"features.{idx}.{name}", sd.get(f"blocks.{s}.{idx}.{name}"))
                     if t is None:
@@ -135,19 +179,22 @@ class VGGPerceptualLoss(nn.Module):
                     getattr(leaf, name).copy_(t)
         self._flat_dev = None
 
-    def _pack(self, dev):
-        ws, bs, self.bias_off = [], [], []
-        off = 0
-        for s, idx, _, co, _ in VGG16_LAYOUT:
-            leaf = getattr(self.blocks[s], str(idx))
-            ws.append(leaf.weight.detach().reshape(-1).float())
-            bs.append(leaf.bias.detach().float())
-            self.bias_off.append(off)
-            off += co
-        self.w_flat = torch.cat(ws).to(dev).contiguous()
-        self.bias_flat = torch.cat(bs).to(dev).contiguous()
-        self._flat_dev = dev
-        self._plans.clear()
+    def _plan(self, B2: int, H: int, W: int, dev):
+        """(trunk plan for one (2B, H, W) shape with each slice's L1 term behind its last conv, the loss it sums into)."""
+        partial = torch.zeros(4, 1024, dtype=torch.float64, device=dev)
+        loss = torch.zeros((), dtype=torch.float32, device=dev)
+
+        def l1(t, i):
+            if i in SLICE_END:
+                s, x = SLICE_END[i], t.acts[i].data_ptr()
+                h, w, c = t.dims[i]
+                half = (B2 // 2) * h * w * c
+                t.ops.append(("stl_l1_partial", (t.dt, x, x + half * t.esz, half, partial[s].data_ptr(), 1024)))
+                t.ops.append(("stl_sum_partials", (partial[s].data_ptr(), 1024, 1.0 / half, loss.data_ptr(), int(s > 0))))
+
+        trunk = Trunk(self, [row[2:] for row in VGG16_LAYOUT], B2, H, W, dev, l1)
+        trunk.keep.append(partial)
+        return trunk, loss
 
     def forward(self, input: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
         if not input.is_cuda:
@@ -155,10 +202,7 @@ class VGGPerceptualLoss(nn.Module):
         if input.shape[1] != 3:  # loss.py:43-45
             input, target = input.repeat(1, 3, 1, 1), target.repeat(1, 3, 1, 1)
         dev = input.device
-        if self.mean.device != dev:
-            self.to(dev)
-        if self._flat_dev != dev:
-            self._pack(dev)
+        ready(self, dev)
         st = torch.cuda.current_stream().cuda_stream
         x = torch.cat([input, target.to(dev)], 0).contiguous().float()
         B2, _, H, W = x.shape
@@ -171,13 +215,9 @@ class VGGPerceptualLoss(nn.Module):
         key = (B2, H, W)
         plan = self._plans.get(key)
         if plan is None:
-            plan = self._plans[key] = _Plan(self, B2, H, W, dev)
-        plan.img.copy_(x)
-        capi.call("stl_weight_prep", self.dtype, self.w_flat.data_ptr(), plan.wk.data_ptr(), plan.wtab.data_ptr(),
-                  plan.nconv, plan.wblocks, st)
-        lib = capi.lib()
-        for name, args in plan.ops:
-            rc = getattr(lib, name)(*args, st)
-            if rc != 0:
-                raise RuntimeError(f"{name}: {lib.stl_last_error().decode()}")
-        return plan.loss.clone()
+            plan = self._plans[key] = self._plan(B2, H, W, dev)
+        trunk, loss = plan
+        trunk.img.copy_(x)
+        trunk.prep_weights(st)
+        trunk.run(st)
+        return loss.clone()

@@ -24,12 +24,13 @@ from __future__ import annotations
 
 import ctypes as C
 import math
-from typing import Dict, Optional
+from typing import Dict, List, Optional
 
 import torch
 import torch.nn as nn
 
 from . import capi
+from .vgg import Trunk, add_conv, dtype_code, ready
 
 # (features index, cin, cout, 2x2 max-pool in front): torchvision VGG19 "E" up to conv5_1
 VGG19_LAYOUT = [(0, 3, 64, False), (2, 64, 64, False), (5, 64, 128, True), (7, 128, 128, False), (10, 128, 256, True),
@@ -49,16 +50,8 @@ def vgg19_flops_per_image(H: int, W: int) -> float:
     return fl
 
 
-def _run(ops, st) -> None:
-    lib = capi.lib()
-    for name, args in ops:
-        rc = getattr(lib, name)(*args, st)
-        if rc != 0:
-            raise RuntimeError(f"{name}: {lib.stl_last_error().decode()}")
-
-
-class _Plan:
-    """The native launches of one batch geometry.
+class StylePlan:
+    """The native launches of one batch geometry: the VGG19 trunk (``self.trunk``) with the content and Gram terms at their taps.
 
     nb images of H x W run as one batch.  content = "batch": the content term compares images [0, B) with [B, 2B) of the batch
     (VGG19StyleLoss: stylised, content, style); "buffer": with the relu4_2 features in ``self.ctarget`` (the stylisation driver's
@@ -67,76 +60,25 @@ class _Plan:
 
     def __init__(self, mod: "VGG19StyleLoss", nb: int, H: int, W: int, dev, B: int, content: Optional[str], gram_imgs,
                  grad: bool = False):
-        self.ops, self.keep = [], []
         self.B, self.H, self.W = B, H, W
-        dt, esz = mod.dtype, (2 if mod.dtype == capi.BF16 else 4)
-        self.dt, self.esz = dt, esz
-        tdt = torch.bfloat16 if dt == capi.BF16 else torch.float32
-        self.img = torch.zeros(nb, 3, H, W, device=dev)
-        nconv = len(VGG19_LAYOUT)
-        tab = (capi.WPrep * nconv)()
-        src = fwd = blk = 0
-        offs, boffs = [], []
-        for i, (_, ci, co, _) in enumerate(VGG19_LAYOUT):
-            patch = i == 0
-            cip, kk = (32, 1) if patch else (ci, 9)
-            e = tab[i]
-            e.src_off, e.fwd_off, e.bwd_off = src, fwd, -1
-            e.Co, e.Ci, e.ks, e.Cip, e.patch, e.blk0 = co, ci, 3, cip, int(patch), blk
-            offs.append(fwd)
-            src += co * ci * 9
-            fwd += co * kk * cip
-            blk += math.ceil(co * ci * 9 / 1024)
-        if grad:   # data-gradient layouts behind the forward ones: [Ci][flipped tap][Co], conv1_1 [kk][Co] over 32 patch rows
-            for i, (_, ci, co, _) in enumerate(VGG19_LAYOUT):
-                cip, kk = (32, 1) if i == 0 else (ci, 9)
-                tab[i].bwd_off = fwd
-                boffs.append(fwd)
-                fwd += co * kk * cip
-        self.wk = torch.zeros(fwd, dtype=tdt, device=dev)
-        self.wtab = torch.frombuffer(bytearray(bytes(tab)), dtype=torch.uint8).clone().to(dev)
-        self.wblocks, self.nconv = blk, nconv
         self.cpartial = torch.zeros(1024, dtype=torch.float64, device=dev)
         self.content = torch.zeros((), dtype=torch.float32, device=dev)
-        self.grams = []   # per style tap: (slabs [len(gram_imgs), nsplit, C, C] fp32, 1 / (C H W))
-        self.acts, self.dims = [], []   # per conv: post-ReLU output [nb, h, w, co], (h, w, co)
+        self.slabs = []   # per style tap: (slabs [len(gram_imgs), nsplit, C, C] fp32, 1 / (C H W))
 
-        def act(b, h, w, c):
-            t = torch.empty(b * h * w * c * esz, dtype=torch.uint8, device=dev)
-            self.keep.append(t)
-            return t
-
-        x = act(nb, H, W, 32)
-        self.ops.append(("stl_patch3x3", (dt, self.img.data_ptr(), x.data_ptr(), nb, H, W, 1, mod.mean.data_ptr(), mod.std.data_ptr())))
-        h, w, c = H, W, 32
-        for i, (_, ci, co, pool) in enumerate(VGG19_LAYOUT):
-            if pool:
-                y = act(nb, h // 2, w // 2, c)
-                self.ops.append(("stl_maxpool2x2", (dt, x.data_ptr(), y.data_ptr(), nb, h, w, c)))
-                x, h, w = y, h // 2, w // 2
-            p = capi.Conv()
-            p.dtype, p.B, p.Hi, p.Wi, p.Ci, p.Ho, p.Wo, p.Co = dt, nb, h, w, c, h, w, co
-            p.ks, p.stride, p.shape = (1 if i == 0 else 3), 1, -1
-            p.src.x, p.src.mode = x.data_ptr(), capi.SRC_PLAIN
-            y = act(nb, h, w, co)
-            p.w = self.wk.data_ptr() + offs[i] * esz
-            p.out, p.bias, p.out_relu = y.data_ptr(), mod.bias_flat.data_ptr() + 4 * mod.bias_off[i], 1
-            capi.call("stl_conv_plan", C.byref(p))
-            self.keep.append(p)
-            self.ops.append(("stl_conv_forward", (C.byref(p),)))
-            x, c = y, co
-            self.acts.append(y)
-            self.dims.append((h, w, c))
+        def taps(t, i):
+            dt, esz = t.dt, t.esz
+            h, w, c = t.dims[i]
+            x = t.acts[i].data_ptr()
             img_elems = h * w * c
             if i == CONTENT_TAP and content is not None:   # images [0, B) = stylised; target: images [B, 2B) or the cached buffer
                 n = B * img_elems
                 if content == "batch":
-                    tgt = x.data_ptr() + n * esz
+                    tgt = x + n * esz
                 else:
-                    self.ctarget = torch.zeros(n, dtype=tdt, device=dev)
+                    self.ctarget = torch.zeros(n, dtype=t.tdt, device=dev)
                     tgt = self.ctarget.data_ptr()
-                self.ops.append(("stl_l2_partial", (dt, x.data_ptr(), tgt, n, self.cpartial.data_ptr(), 1024)))
-                self.ops.append(("stl_sum_partials", (self.cpartial.data_ptr(), 1024, 1.0 / n, self.content.data_ptr(), 0)))
+                t.ops.append(("stl_l2_partial", (dt, x, tgt, n, self.cpartial.data_ptr(), 1024)))
+                t.ops.append(("stl_sum_partials", (self.cpartial.data_ptr(), 1024, 1.0 / n, self.content.data_ptr(), 0)))
                 self.ctarget_ptr = tgt
             if i in STYLE_TAPS and len(gram_imgs):
                 from .engine import choose_tile
@@ -152,35 +94,28 @@ class _Plan:
                     wg = capi.Wgrad()
                     wg.dtype, wg.B, wg.Hi, wg.Wi, wg.Ci, wg.Ho, wg.Wo, wg.Co, wg.ks, wg.stride = dt, 1, h, w, c, h, w, c, 1, 1
                     wg.TH, wg.TW, wg.nsplit = th, tw, nsplit
-                    ptr = x.data_ptr() + b * img_elems * esz
+                    ptr = x + b * img_elems * esz
                     wg.h.x, wg.h.mode, wg.g.x, wg.g.mode = ptr, capi.SRC_PLAIN, ptr, capi.SRC_PLAIN
                     wg.partial = slabs[j].data_ptr()
-                    self.keep.append(wg)
-                    self.ops.append(("stl_conv_wgrad", (C.byref(wg),)))
-                self.grams.append((slabs, 1.0 / (c * h * w)))
+                    t.keep.append(wg)
+                    t.ops.append(("stl_conv_wgrad", (C.byref(wg),)))
+                self.slabs.append((slabs, 1.0 / (c * h * w)))
+
+        self.trunk = Trunk(mod, [row[1:] for row in VGG19_LAYOUT], nb, H, W, dev, taps, grad)
         if grad:
-            self._plan_backward(mod, dev, tdt, boffs)
+            self._plan_backward(mod, dev)
 
-    def _conv(self, B, h, w, ci, co, ks, src, wptr, out, addend=0, mask_z=0) -> None:
-        p = capi.Conv()
-        p.dtype, p.B, p.Hi, p.Wi, p.Ci, p.Ho, p.Wo, p.Co = self.dt, B, h, w, ci, h, w, co
-        p.ks, p.stride, p.shape = ks, 1, -1
-        p.src.x, p.src.mode = src, capi.SRC_PLAIN
-        p.w, p.out = wptr, out
-        if addend:
-            p.addend = addend
-        if mask_z:
-            p.mask_z = mask_z
-        capi.call("stl_conv_plan", C.byref(p))
-        self.keep.append(p)
-        self.bwd_ops.append(("stl_conv_forward", (C.byref(p),)))
+    def grams(self) -> List[torch.Tensor]:
+        """Per style tap the Gram matrices [len(gram_imgs), C, C] fp64 of the last forward run: its split-K slabs summed."""
+        return [slabs.double().sum(1) * scale for slabs, scale in self.slabs]
 
-    def _plan_backward(self, mod, dev, tdt, boffs) -> None:
+    def _plan_backward(self, mod, dev) -> None:
         """Image gradient of images [0, B): the 13 data gradients (stl_conv_forward on the transposed weights, ReLU masks from
         the stored outputs as mask_z), the max-pool adjoints, the Gram terms (a 1x1 conv per image and tap with the weight
         ks * (G_b - A_b), the gradient from deeper layers as addend), the content term (stl_l2_backward, in place) and the patch
         adjoint.  Gradients ping-pong between two buffers per resolution."""
-        B, dt, esz = self.B, self.dt, self.esz
+        t, B = self.trunk, self.B
+        dt, esz = t.dt, t.esz
         self.bwd_ops = []
         self.cscale = torch.zeros((), dtype=torch.float32, device=dev)   # 2 wc / n, set by backward()
         self.gw = {}                                                     # style tap -> [B, C, C] weight ks * (G_b - A_b)
@@ -189,35 +124,36 @@ class _Plan:
 
         def other(h, w, g):   # a gradient buffer of resolution (h, w) that is not g; two per resolution, sized for its widest use
             if (h, w) not in bufs:
-                cmax = max(max(ci, co) for (hh, ww, _), (_, ci, co, _) in zip(self.dims, VGG19_LAYOUT) if (hh, ww) == (h, w))
+                cmax = max(max(ci, co) for (hh, ww, _), (_, ci, co, _) in zip(t.dims, VGG19_LAYOUT) if (hh, ww) == (h, w))
                 bufs[(h, w)] = [torch.empty(B * h * w * max(cmax, 32) * esz, dtype=torch.uint8, device=dev) for _ in range(2)]
             a, b = (t.data_ptr() for t in bufs[(h, w)])
             return b if g == a else a
 
         g = None   # gradient w.r.t. the output F_i of layer i; ReLU mask applied unless layer i is a style or the content tap
         for i in range(len(VGG19_LAYOUT) - 1, -1, -1):
-            h, w, c = self.dims[i]
-            f, pix = self.acts[i].data_ptr(), h * w * c * esz
+            h, w, c = t.dims[i]
+            f, pix = t.acts[i].data_ptr(), h * w * c * esz
             if i in STYLE_TAPS:   # (gF_i + ks (G_b - A_b) F_b) * (F_b > 0): a 1x1 conv per image, gF_i from layer i + 1 as addend
-                wgt = torch.zeros(B, c, c, dtype=tdt, device=dev)
+                wgt = torch.zeros(B, c, c, dtype=t.tdt, device=dev)
                 self.gw[i] = wgt
                 out = other(h, w, g)
                 for b in range(B):
-                    self._conv(1, h, w, c, c, 1, f + b * pix, wgt[b].data_ptr(), out + b * pix,
-                               addend=(g + b * pix) if g is not None else 0, mask_z=f + b * pix)
+                    t.conv(self.bwd_ops, 1, h, w, c, c, 1, f + b * pix, wgt[b].data_ptr(), out + b * pix,
+                           addend=(g + b * pix) if g is not None else 0, mask_z=f + b * pix)
                 g = out
             elif i == CONTENT_TAP:   # + wc * 2 (F_x - F_c) / n, then the ReLU mask, in place
                 self.bwd_ops.append(("stl_l2_backward", (dt, f, self.ctarget_ptr, g, B * h * w * c, self.cscale.data_ptr(), 1)))
             _, ci, co, pool = VGG19_LAYOUT[i]
             out = other(h, w, g)
             if i == 0:   # conv1_1: 1x1 onto the 32-wide patches, then the patch adjoint (with 1 / std) to the NCHW image
-                self._conv(B, h, w, co, 32, 1, g, self.wk.data_ptr() + boffs[0] * esz, out)
+                t.conv(self.bwd_ops, B, h, w, co, 32, 1, g, t.wk.data_ptr() + t.tab[0].bwd_off * esz, out)
                 self.bwd_ops.append(("stl_patch3x3_backward", (dt, out, self.dimg.data_ptr(), B, self.H, self.W, 1, mod.std.data_ptr())))
                 break
-            hp, wp, cp = self.dims[i - 1]
-            fp = self.acts[i - 1].data_ptr()
+            hp, wp, cp = t.dims[i - 1]
+            fp = t.acts[i - 1].data_ptr()
             masked = i - 1 not in STYLE_TAPS and i - 1 != CONTENT_TAP   # else the tap masks after adding its own term
-            self._conv(B, h, w, co, ci, 3, g, self.wk.data_ptr() + boffs[i] * esz, out, mask_z=fp if masked and not pool else 0)
+            t.conv(self.bwd_ops, B, h, w, co, ci, 3, g, t.wk.data_ptr() + t.tab[i].bwd_off * esz, out,
+                   mask_z=fp if masked and not pool else 0)
             if pool:
                 dst = other(hp, wp, None)
                 self.bwd_ops.append(("stl_maxpool2x2_backward", (dt, fp, out, dst, B, hp, wp, cp, int(masked))))
@@ -229,15 +165,15 @@ class _Plan:
         grams: per style tap (G [B, C, C], A [B or 1, C, C]) fp64 from the forward pass."""
         B = self.B
         for i, (G, A) in zip(STYLE_TAPS, grams):
-            h, w, c = self.dims[i]
+            h, w, c = self.trunk.dims[i]
             ks = 4.0 / (B * float(c) ** 3 * h * w)
             self.gw[i].copy_((G - A) * (ws * ks))
-        h, w, c = self.dims[CONTENT_TAP]
+        h, w, c = self.trunk.dims[CONTENT_TAP]
         if isinstance(wc, torch.Tensor):
             self.cscale.copy_(wc * (2.0 / (B * h * w * c)))
         else:
             self.cscale.fill_(wc * 2.0 / (B * h * w * c))
-        _run(self.bwd_ops, torch.cuda.current_stream().cuda_stream)
+        self.trunk.run(torch.cuda.current_stream().cuda_stream, self.bwd_ops)
         return self.dimg
 
 
@@ -283,13 +219,9 @@ class VGG19StyleLoss(nn.Module):
                  compute_dtype: str = "fp32"):
         super().__init__()
         self.content_weight, self.style_weight = float(content_weight), float(style_weight)
-        self.dtype = capi.BF16 if compute_dtype.lower() in ("bf16", "bfloat16") else capi.F32
+        self.dtype = dtype_code(compute_dtype)
         self.features = nn.Module()
-        for idx, ci, co, _ in VGG19_LAYOUT:
-            leaf = nn.Module()
-            leaf.register_parameter("weight", nn.Parameter(torch.zeros(co, ci, 3, 3), requires_grad=False))
-            leaf.register_parameter("bias", nn.Parameter(torch.zeros(co), requires_grad=False))
-            self.features.add_module(str(idx), leaf)
+        self._convs = [add_conv(self.features, idx, ci, co) for idx, ci, co, _ in VGG19_LAYOUT]
         self.mean = nn.Parameter(torch.tensor([0.485, 0.456, 0.406]).view(1, 3, 1, 1), requires_grad=False)
         self.std = nn.Parameter(torch.tensor([0.229, 0.224, 0.225]).view(1, 3, 1, 1), requires_grad=False)
         self._plans: Dict = {}
@@ -297,31 +229,11 @@ class VGG19StyleLoss(nn.Module):
         if state_dict is not None:
             self.load_state_dict({k: v for k, v in state_dict.items() if k.startswith("features.")}, strict=False)
 
-    def _pack(self, dev):
-        ws, bs, self.bias_off = [], [], []
-        off = 0
-        for idx, _, co, _ in VGG19_LAYOUT:
-            leaf = getattr(self.features, str(idx))
-            ws.append(leaf.weight.detach().reshape(-1).float())
-            bs.append(leaf.bias.detach().float())
-            self.bias_off.append(off)
-            off += co
-        self.w_flat = torch.cat(ws).to(dev).contiguous()
-        self.bias_flat = torch.cat(bs).to(dev).contiguous()
-        self._flat_dev = dev
-        self._plans.clear()
-
-    def _ready(self, dev) -> None:
-        if self.mean.device != dev:
-            self.to(dev)
-        if self._flat_dev != dev:
-            self._pack(dev)
-
     def forward(self, x: torch.Tensor, content: torch.Tensor, style: torch.Tensor):
         if not x.is_cuda:
             raise RuntimeError("stlpose_amd.VGG19StyleLoss runs only on an MI355X (cuda/HIP device); there is no CPU path")
         dev = x.device
-        self._ready(dev)
+        ready(self, dev)
         st = torch.cuda.current_stream().cuda_stream
         grad = torch.is_grad_enabled() and x.requires_grad
         if grad and (content.requires_grad or style.requires_grad):
@@ -334,15 +246,14 @@ class VGG19StyleLoss(nn.Module):
         key = (B3, H, W, grad)
         plan = self._plans.get(key)
         if plan is None:
-            plan = self._plans[key] = _Plan(self, B3, H, W, dev, B, "batch", list(range(B)) + list(range(2 * B, 3 * B)), grad)
-        plan.img.copy_(xin)
-        capi.call("stl_weight_prep", self.dtype, self.w_flat.data_ptr(), plan.wk.data_ptr(), plan.wtab.data_ptr(), plan.nconv, plan.wblocks, st)
-        _run(plan.ops, st)
+            plan = self._plans[key] = StylePlan(self, B3, H, W, dev, B, "batch", list(range(B)) + list(range(2 * B, 3 * B)), grad)
+        plan.trunk.img.copy_(xin)
+        plan.trunk.prep_weights(st)
+        plan.trunk.run(st)
         # C x C Gram matrices: split-K slabs -> sum, scale, squared distance (a few hundred KB of bookkeeping)
         s_loss = torch.zeros((), dtype=torch.float64, device=dev)
         grams = []
-        for slabs, scale in plan.grams:
-            g = slabs.double().sum(1) * scale
+        for g in plan.grams():
             s_loss = s_loss + ((g[:B] - g[B:]) ** 2).mean()
             grams.append((g[:B], g[B:]))
         s_loss = s_loss.float()

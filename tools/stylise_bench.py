@@ -72,8 +72,9 @@ def time_halves(fwd, bwd, reps, warm):
 
 def native(dt, content, style, w, reps):
     from stlpose_amd import GatysStylizer
+    from stlpose_amd.vgg import ready
     st = GatysStylizer(w, 1.0, 1e5, dt)
-    st.loss._ready(content.device)
+    ready(st.loss, content.device)
     it, grams = st.targets(content, style)
     img = content.clone()
     f, b = time_halves(lambda: st.forward_loss(it, img, grams)[1], lambda g: st.image_grad(it, g), reps, 2)
