@@ -3,8 +3,12 @@
 fwd + masked-MSE + bwd + Adam (+ RCCL gradient all-reduce when N > 1), bf16 storage / fp32
 accumulate, batch 32 per GPU, synthetic inputs already resident in HBM.
 
-  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 (N > 1: launched by torch.distributed.run, one rank per GPU.)  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the headline line, nothing else.
+--full adds what takes runs of its own: the per-kernel-family roofline (and --dump-ops), the multi-GPU communication
+breakdown, the extra legs (other sizes and precisions, the evaluation path, VGG) and the CPU baselines.
 """
 from __future__ import annotations
 
@@ -147,6 +151,39 @@ def family_roofline(f):
     else:
         out.update(bound="hbm", achieved=round(gbs, 1), peak=HBM_PEAK, unit="GB/s", frac=round(gbs / HBM_PEAK, 4))
     return out
+
+
+def kernel_rooflines(ts, a):
+    """--full: roofline entries of the dominant kernel family (the one with the largest summed duration, measured by
+    time_kernel_families) and of the next five."""
+    fams, _progs = time_kernel_families(ts)
+    if not fams:
+        return None, None
+    roof = family_roofline(fams[0])
+    # HBM bytes per launch of THAT kernel from the committed rocprofv3 --pmc passes of this same command
+    # (tools/pmc_traffic.py -> profiles/r*_pmc_dominant.json); used only if it was taken on these kernel sources
+    # (build id) for this kernel and launch count, else null
+    traffic = traffic_src = None
+    import glob
+    for f in sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_pmc_dominant.json"))):
+        try:
+            rec = json.load(open(f))
+            if rec.get("kernel") == roof["kernel"] and rec.get("launches") == roof["launches_per_step"] and rec.get("build_id") == csrc_hash() \
+                    and (a.arch, a.height, a.width, a.batch, a.dtype) == ("w32", 384, 288, 32, rec.get("dtype", "mixed")):
+                traffic, traffic_src = round(rec["traffic_bytes_per_launch"]), "profiles/" + os.path.basename(f)
+        except Exception:
+            pass
+    roof.update(traffic=traffic, traffic_unit="HBM bytes per launch (2 x FETCH_SIZE + WRITE_SIZE)",
+                traffic_source=(traffic_src + " (rocprofv3 --pmc passes of this command on this build id, committed; not measured in this run)") if traffic_src else None,
+                chosen_by="largest summed duration over one forward + backward pass (per kernel instantiation, its launches replayed back to back between HIP events in this run)")
+    others = [family_roofline(f) for f in fams[1:6]]
+    # the dominant family's launches once more, back to back, as the LAST dispatches of the process: what tools/pmc_traffic.py reads
+    lib_ = __import__("stlpose_amd.capi", fromlist=["lib"]).lib()
+    streams_ = (C.c_void_p * 1)(torch.cuda.current_stream().cuda_stream)
+    for h in fams[0]["replay"]:
+        lib_.stl_program_run(h, streams_)
+    torch.cuda.synchronize()
+    return roof, others
 
 
 DUMP_FULL_MAX = 1 << 22   # elements an array may have to be written whole (16 MB in float32)
@@ -444,12 +481,17 @@ def main():
     ap.add_argument("--batch", type=int, default=32, help="per-GPU batch")
     ap.add_argument("--dtype", default="mixed", help="mixed (forward tensors f16, gradients bf16: the default 16-bit mode), bf16 or fp32")
     ap.add_argument("--no-graph", action="store_true")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the fp32-path and VGG cfg4 legs")
-    ap.add_argument("--dump-ops", default="", help="write the isolated duration of every launch of one step to this file")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline line's steps also measure the kernel-family rooflines, the communication breakdown (N > 1), "
+                         "the extra legs and the CPU baselines")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the extra legs (other sizes and precisions, evaluation, VGG)")
+    ap.add_argument("--dump-ops", default="", help="with --full: write the isolated duration of every launch of one step to this file")
     ap.add_argument("--dump-outputs", default="", metavar="DIR",
                     help="write what the last timed step computed (loss, heat maps, BatchNorm buffers, parameters, gradients) to DIR/<name>.npy")
     a = ap.parse_args()
+    if a.dump_ops and not a.full:
+        ap.error("--dump-ops is written by the kernel-family timing of --full")
     global DUMP_OPS
     DUMP_OPS = a.dump_ops
 
@@ -527,7 +569,7 @@ def main():
         dump_outputs(ts, a.dump_outputs)
     loss = float(ts.loss.item())
     comm = None
-    if world > 1 or ts._force_dp:
+    if a.full and (world > 1 or ts._force_dp):
         # Self-describing multi-GPU line: what the communicator reports, each gradient bucket's all-reduce alone
         # (HIP events around the collective, nothing else in flight), and the step with the collectives switched off
         # -- exposed communication = ms_per_step - ms_per_step_no_comm.  Every rank runs the same sequence.
@@ -573,33 +615,6 @@ def main():
 
     if rank == 0:
         flops_img = FLOPS_PER_IMG.get((a.arch, a.height, a.width))
-        fams, progs = time_kernel_families(ts)
-        roof = others = None
-        if fams:
-            roof = family_roofline(fams[0])
-            # HBM bytes per launch of THAT kernel from the committed rocprofv3 --pmc passes of this same command
-            # (tools/pmc_traffic.py -> profiles/r*_pmc_dominant.json); used only if it was taken on these kernel sources
-            # (build id) for this kernel and launch count, else null
-            traffic = traffic_src = None
-            import glob
-            for f in sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_pmc_dominant.json"))):
-                try:
-                    rec = json.load(open(f))
-                    if rec.get("kernel") == roof["kernel"] and rec.get("launches") == roof["launches_per_step"] and rec.get("build_id") == csrc_hash() \
-                            and (a.arch, a.height, a.width, a.batch, a.dtype) == ("w32", 384, 288, 32, rec.get("dtype", "mixed")):
-                        traffic, traffic_src = round(rec["traffic_bytes_per_launch"]), "profiles/" + os.path.basename(f)
-                except Exception:
-                    pass
-            roof.update(traffic=traffic, traffic_unit="HBM bytes per launch (2 x FETCH_SIZE + WRITE_SIZE)",
-                        traffic_source=(traffic_src + " (rocprofv3 --pmc passes of this command on this build id, committed; not measured in this run)") if traffic_src else None,
-                        chosen_by="largest summed duration over one forward + backward pass (per kernel instantiation, its launches replayed back to back between HIP events in this run)")
-            others = [family_roofline(f) for f in fams[1:6]]
-            # the dominant family's launches once more, back to back, as the LAST dispatches of the process: what tools/pmc_traffic.py reads
-            lib_ = __import__("stlpose_amd.capi", fromlist=["lib"]).lib()
-            streams_ = (C.c_void_p * 1)(torch.cuda.current_stream().cuda_stream)
-            for h in fams[0]["replay"]:
-                lib_.stl_program_run(h, streams_)
-            torch.cuda.synchronize()
         out = dict(metric=f"images/sec/GPU HRNet-{a.arch.upper()} {a.height}x{a.width} train step; PCKh@0.5 parity", value=round(value, 2),
                    unit="images/sec", n_gpus=world, steps=a.steps, warmup=a.warmup, ms_per_step=round(ms, 3),
                    higher_is_better=True, scaling="weak", vs_baseline=None, dtype=DTYPE_LABEL.get(a.dtype, a.dtype), data="synthetic",
@@ -608,11 +623,13 @@ def main():
                                global_batch=a.batch * world, parallelism=f"dp{world}"),
                    loss=loss,
                    step_tflops=round(value * flops_img / 1e12, 2) if flops_img else None,
-                   step_mfma_frac=round(value / world * flops_img / 1e12 / MFMA_PEAK_BF16, 4) if flops_img else None,
-                   roofline=roof, roofline_next=others)
+                   step_mfma_frac=round(value / world * flops_img / 1e12 / MFMA_PEAK_BF16, 4) if flops_img else None)
+        if a.full:
+            roof, others = kernel_rooflines(ts, a)
+            out.update(roofline=roof, roofline_next=others)
         if comm is not None:
             out["comm"] = comm
-        if world == 1 and not a.no_extras:
+        if a.full and world == 1 and not a.no_extras:
             del ts, model
             torch.cuda.empty_cache()
             extras = {}
@@ -627,7 +644,7 @@ def main():
                 except Exception as e:   # an extra leg must never take the headline line down
                     extras[name] = dict(error=f"{type(e).__name__}: {e}")
             out["extras"] = extras
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(a.arch, a.height, a.width)
             if not a.no_extras:
                 out["cpu_baseline"]["cfg1"] = cpu_baseline_cfg1()

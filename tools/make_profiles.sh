@@ -6,9 +6,9 @@ ROOT=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$ROOT/gpurun_out/profiles_$R
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-B="python $ROOT/bench.py --no-cpu-baseline --no-extras"
-# 1. the bench line itself (default flags, with extras and CPU baselines)
-timeout -k 10 700 python $ROOT/bench.py --dump-ops $OUT/${R}_ops_isolated.txt > $OUT/${R}_bench.json 2> $OUT/${R}_bench.stderr || exit 1
+B="python $ROOT/bench.py --full --no-cpu-baseline --no-extras"
+# 1. the whole bench line (--full: rooflines, extras and CPU baselines)
+timeout -k 10 700 python $ROOT/bench.py --full --dump-ops $OUT/${R}_ops_isolated.txt > $OUT/${R}_bench.json 2> $OUT/${R}_bench.stderr || exit 1
 echo bench done
 # 2. kernel traces: default multi-stream run and one stream (per-kernel durations not stretched by overlap)
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_default -- $B --steps 5 --warmup 3 > $OUT/trace_default.log 2>&1 || exit 2
