@@ -16,11 +16,12 @@ Data flow choices:
 """
 from __future__ import annotations
 
+import bisect
 import ctypes as C
 import math
 import os
 from dataclasses import dataclass, field
-from typing import Dict, List, Optional, Tuple
+from typing import Dict, List, NamedTuple, Optional, Tuple, Union
 
 import torch
 
@@ -80,6 +81,29 @@ class ConvInfo:
     Cik: int = 0     # input channels as the kernel sees them (32 for the patch conv)
 
 
+class Launch(NamedTuple):
+    """One op of a program: a kernel launch with its descriptor, its stream and the dependency tokens it reads and writes
+    (device pointers of tensors, ``C.addressof`` of descriptors whose results have no tensor of their own)."""
+    name: str
+    desc: C.Structure
+    stream: int
+    reads: list
+    writes: list
+
+
+class Bucket(NamedTuple):
+    """A gradient bucket: a contiguous suffix [lo, hi) of the flat gradient buffer, closed as soon as every parameter in it
+    has its slabs / BatchNorm reductions complete (backward finishes the last layers first).  Each bucket gets one ranged
+    slab reduction + BN-gradient launch inside the program, so the step has no serial tail, and an event a data-parallel
+    all-reduce can wait on: its last op, bwd_ops[op]."""
+    lo: int
+    hi: int
+    op: int
+
+    def __getitem__(self, key):   # b["lo"] as well as b.lo and b[0]: callers read buckets by field name
+        return getattr(self, key) if isinstance(key, str) else tuple.__getitem__(self, key)
+
+
 @dataclass
 class Act:
     kind: str            # 'plain' | 'bn'
@@ -91,16 +115,69 @@ class Act:
     bn: Optional[BNInfo] = None
     relu: bool = False
     needs_grad: bool = True
+    consumers: int = 0
+    producer: Optional[FuseNode] = None                      # plain: the sum that wrote it (None: the patch tensor)
+    # ---- state of the backward builder (_build_backward)
     grads: List[torch.Tensor] = field(default_factory=list)  # plain: gradient contributions
     dt: Optional[torch.Tensor] = None                        # bn: grad wrt BN output (masked)
-    consumers: int = 0
     bwd_seen: int = 0                                        # consumers already handled by the backward builder
     fused_du: Optional[torch.Tensor] = None                  # plain: masked gradient produced by a fused dgrad
-    pending: Optional[Tuple] = None                          # plain block-end sum not consumed yet: (forward op, BN term, skip term)
 
     @property
     def ptr(self) -> int:
         return self.t.data_ptr()
+
+
+# ---- the tape: forward nodes in forward order, walked in reverse by the backward builder
+@dataclass
+class ConvNode:
+    x: Act
+    y: Act
+    conv: ConvInfo
+    ks: int       # as launched (the patch conv is a 1x1 conv over 32-wide patches)
+    stride: int
+    stream: int
+
+
+@dataclass
+class FuseNode:
+    terms: List[Tuple[Act, int, bool]]   # (input, upsample shift, ReLU of its BN applied on load)
+    z: Act
+    relu: bool
+    op: Launch   # its forward launch
+
+    @property
+    def block_end(self) -> bool:
+        """z = ReLU(BN(y) + skip), BN term first (same summation order as the sum kernel): a block end that its first
+        consumer may form itself (STL_SRC_BNADD)."""
+        return self.relu and [(a.kind, s) for a, s, _ in self.terms] == [("bn", 0), ("plain", 0)]
+
+    @property
+    def same_bn(self) -> List[Act]:
+        """BN terms at the output's resolution: their BatchNorm-backward sums are reduced with the sum's gradient."""
+        return [a for a, s, _ in self.terms if a.kind == "bn" and s == 0]
+
+
+@dataclass
+class HeadNode:
+    x: Act
+    key: str
+    joints: int
+
+
+@dataclass
+class _OpenBucket:
+    """The gradient bucket under construction (_bucket_close): the suffix [lo, hi) of the flat gradient buffer."""
+    lo: int
+    hi: int
+    slab0: int = 0    # its first slab
+    done: int = 0     # parameter elements of [lo, hi) whose gradient launches are planned
+    reads: list = field(default_factory=list)   # tokens of the launches that write its slabs
+    stream: int = 0                             # (unplaced) stream of its last weight gradient
+
+    def add(self, off: int, size: int):   # the gradient launches of parameters [off, off + size) are planned
+        self.done += size
+        self.lo = min(self.lo, off)
 
 
 class ParamStore:
@@ -160,13 +237,14 @@ class Engine:
         self.esz = _esz(dtype)
         self.tdtype = torch.float32 if self.dtype == capi.F32 else torch.bfloat16   # kernel-layout weights: just a byte container in the 16-bit modes
         self.lib = capi.lib()
-        self.fwd_ops: List[Tuple] = []
-        self.bwd_ops: List[Tuple] = []
-        self.tape: List[Tuple] = []
+        self.fwd_ops: List[Launch] = []
+        self.bwd_ops: List[Launch] = []
+        self.tape: List[Union[ConvNode, FuseNode, HeadNode]] = []
         self.convs: List[ConvInfo] = []
         self.bns: List[BNInfo] = []
         self._keep: List = []  # keep ctypes structs / tensors alive
-        self._progs: Dict[int, Tuple] = {}
+        self._progs: Dict[str, C.c_void_p] = {}   # "fwd" / "bwd" -> native program
+        self._fixups: Dict[str, List[Tuple]] = {}   # arena -> (descriptor, field, byte offset): see _fix
         self.act_bytes = 0
         self.generation = 0   # forward passes through this plan (hrnet._Fn stale-backward check)
         # static I/O
@@ -211,13 +289,13 @@ class Engine:
         self._side = None
         self._stats_used = 0
         self._wk_elems = 0
-        self._wk_fix: List[Tuple] = []
         walk(self, arch)
         self._check_stats_arena(nstat)
         self._finalize_weights()
         self._build_tables()
         if training or input_grad:
             self._build_backward()
+        assert not self._fixups, "descriptor fields left pointing into arenas that were never allocated"
 
     def _check_stats_arena(self, nstat: int):
         """every layer's [NSHARD][2C] slice must lie inside the arenas: kernels add to them through raw pointers"""
@@ -238,8 +316,16 @@ class Engine:
     def _act_tensor(self, B, H, W, C) -> torch.Tensor:
         return self._alloc(B * H * W * C * self.esz)
 
+    def _fix(self, desc, attr: str, arena: str, off: int):
+        """desc.attr = base of `arena` + off bytes, set by _resolve once the arena exists (the kernel-layout weights "wk",
+        the split-K slabs "slab" and their table "slab_tab" are sized only when the plan is complete)."""
+        self._fixups.setdefault(arena, []).append((desc, attr, off))
+
+    def _resolve(self, arena: str, t: torch.Tensor):
+        for desc, attr, off in self._fixups.pop(arena, []):
+            setattr(desc, attr, t.data_ptr() + off)
+
     def _src(self, a: Act, relu: Optional[bool] = None) -> capi.Src:
-        a.pending = None
         s = capi.Src()
         s.x = a.ptr
         if a.kind == "plain":
@@ -280,7 +366,7 @@ class Engine:
         pd = capi.Patch()
         pd.dtype, pd.B, pd.H, pd.W, pd.stride = self.fdtype, B, H, W, 2
         pd.img, pd.out = self.img.data_ptr(), t.data_ptr()
-        self.fwd_ops.append(("stl_patch3x3", pd, 0, [], [t.data_ptr()]))
+        self.fwd_ops.append(Launch("stl_patch3x3", pd, 0, [], [t.data_ptr()]))
         self._patches = Act("plain", t, B, Ho, Wo, 32, needs_grad=self.input_grad)
         return self._patches
 
@@ -310,29 +396,28 @@ class Engine:
         p.TH, p.TW, p.shape = 0, 0, -1
         capi.call("stl_conv_plan", C.byref(p))  # block shape + pixel tile, searched once
         reads, writes = [x.ptr], [y.ptr]
-        pend = x.pending
-        if (pend is not None and kstride == 1 and kks in (1, 3) and pend[0][2] == self._stream and self.merge_minc <= x.C
-                and capi.lib().stl_conv_bnadd_ok(C.byref(p)) == 1):
+        pend = x.producer
+        if (pend is not None and pend.block_end and x.consumers == 0 and kstride == 1 and kks in (1, 3)
+                and pend.op.stream == self._stream and self.merge_minc <= x.C and capi.lib().stl_conv_bnadd_ok(C.byref(p)) == 1):
             # Residual block end z = ReLU(BN(y2) + skip) whose FIRST consumer is this convolution (the next unit's conv1: 3x3
             # in the branches, 1x1 in layer1 -- round 5): the sum is formed while the conv stages its tiles and written out once
             # (STL_SRC_BNADD + src_out) -- the stand-alone sum launch and one pass over the tensor go (HRnet.py:58-59, 88-100).
-            fop, ybn, skip = pend
-            self.fwd_ops.remove(fop)
+            (ybn, _, _), (skip, _, _) = pend.terms   # BN term first (see fuse)
+            self.fwd_ops.remove(pend.op)
             p.src = self._src(ybn, relu=True)
             p.src.mode = capi.SRC_BNADD
             p.src.y = skip.ptr
             p.src_out = x.ptr
             reads, writes = [ybn.ptr, skip.ptr], [y.ptr, x.ptr]
-            x.pending = None
         else:
             p.src = self._src(x)
         p.out = y.ptr
         if self.training:
             p.out_stats = self.stats.data_ptr() + 8 * bn.stats_off
-        self._wk_fix.append((p, "w", ci.fwd_off))
-        self.fwd_ops.append(("stl_conv_forward", p, self._stream, reads, writes))
+        self._fix(p, "w", "wk", ci.fwd_off * self.esz)
+        self.fwd_ops.append(Launch("stl_conv_forward", p, self._stream, reads, writes))
         x.consumers += 1
-        self.tape.append(("conv", x, y, ci, (kks, kstride), self._stream))
+        self.tape.append(ConvNode(x, y, ci, kks, kstride, self._stream))
         return y
 
     def fuse(self, terms, relu) -> Act:
@@ -351,14 +436,10 @@ class Engine:
             p.t[i].shift = s
             a.consumers += 1
         p.out = z.ptr
-        op = ("stl_fuse_forward", p, self._stream, [a.ptr for a, _, _ in terms], [z.ptr])
+        op = Launch("stl_fuse_forward", p, self._stream, [a.ptr for a, _, _ in terms], [z.ptr])
+        z.producer = FuseNode(terms, z, relu, op)
         self.fwd_ops.append(op)
-        self.tape.append(("fuse", terms, z, relu, self._stream))
-        if relu and len(terms) == 2 and all(s == 0 for _, s, _ in terms):
-            bns = [a for a, _, tr in terms if a.kind == "bn" and not tr]
-            pls = [a for a, _, _ in terms if a.kind == "plain"]
-            if len(bns) == 1 and len(pls) == 1 and terms[0][0] is bns[0]:   # BN term first: same summation order as the sum kernel
-                z.pending = (op, bns[0], pls[0])
+        self.tape.append(z.producer)
         return z
 
     def head(self, key, x: Act, joints) -> torch.Tensor:
@@ -369,26 +450,21 @@ class Engine:
         hd = capi.Head()
         hd.dtype, hd.B, hd.H, hd.W, hd.Ci, hd.J = self.fdtype, x.B, x.H, x.W, x.C, joints
         hd.x, hd.w, hd.bias, hd.out = x.ptr, self.head_w, self.head_b, self.out.data_ptr()
-        self.fwd_ops.append(("stl_head_forward", hd, 0, [x.ptr], [self.out.data_ptr()]))
+        self.fwd_ops.append(Launch("stl_head_forward", hd, 0, [x.ptr], [self.out.data_ptr()]))
         x.consumers += 1
-        self.tape.append(("head", x, key, joints))
+        self.tape.append(HeadNode(x, key, joints))
         return self.out
 
     # ------------------------------------------------------------------ weights in kernel layout
     def _finalize_weights(self):
         self.wk = torch.zeros(max(self._wk_elems, 1), dtype=self.tdtype, device=self.dev)
-        base = self.wk.data_ptr()
-        for p, attr, off in self._wk_fix:
-            setattr(p, attr, base + off * self.esz)
-        tab = (capi.WPrep * len(self.convs))()
-        blk = 0
-        for i, c in enumerate(self.convs):
-            e = tab[i]
-            e.src_off, e.fwd_off, e.bwd_off = c.master_off, c.fwd_off, c.bwd_off
-            e.Co, e.Ci, e.ks, e.Cip, e.patch, e.blk0 = c.Co, c.Ci, c.ks, c.Cik, int(c.patch), blk
+        self._resolve("wk", self.wk)
+        tab, blk = [], 0
+        for c in self.convs:
+            tab.append(capi.WPrep(c.master_off, c.fwd_off, c.bwd_off, c.Co, c.Ci, c.ks, c.Cik, int(c.patch), blk))
             blk += math.ceil(c.Co * c.Ci * c.ks * c.ks / 1024)
         self._wprep_blocks = blk
-        self._wprep_tab = _to_device(tab, self.dev)
+        self._wprep_tab = _to_device((capi.WPrep * len(tab))(*tab), self.dev)
         self._wprep_n = len(self.convs)
 
     def _active_of(self, key: str) -> int:
@@ -403,231 +479,157 @@ class Engine:
     def _new_grad(self, a: Act) -> torch.Tensor:
         return self._act_tensor(a.B, a.H, a.W, a.C)
 
+    def _red(self, bn: BNInfo) -> int:
+        """Where a BatchNorm's backward reductions go: rstats, or the sink of an eval plan."""
+        return self._red_arena.data_ptr() + 8 * bn.stats_off
+
     def _build_backward(self):
-        st = self.store
-        ops = self.bwd_ops
-        self.slabs: List[Tuple] = []  # (struct_or_None, nelem, entry dict)
-        self._slab_elems = 0
-        J = self.out.shape[1]
+        self.slabs: List[capi.Slab] = []   # the slab reduction's table, one entry per weight-gradient partial sum
+        self._slab_elems = 0               # fp32 elements of the slab arena
+        self._slab_blocks = 0              # blocks of the slab reduction
         self.dout = torch.zeros_like(self.out)
-        producer = {id(n[2]): n for n in self.tape if n[0] == "fuse"}
-        wgrads = self.training   # eval plans (input_grad) compute data gradients only
-        red_arena = self.rstats if self.training else self.sink
-
-        def red(bn: BNInfo) -> int:   # where a BatchNorm's backward reductions go
-            return red_arena.data_ptr() + 8 * bn.stats_off
-        # ---- gradient buckets: contiguous suffixes of the flat gradient buffer, closed as soon as every
-        # parameter in them has its slabs / BatchNorm reductions complete (backward finishes the last
-        # layers first).  Each bucket gets one ranged slab reduction + BN-gradient launch inside the
-        # program, so the step has no serial tail, and an event a data-parallel all-reduce can wait on.
-        self.buckets: List[dict] = []
-        bucket_min = int(self.bucket_mb * (1 << 20) / 4)
-        bk = dict(done=0, lo=st.nparam, hi=st.nparam, slab0=0, reads=[], strm=0)
-        # The serial tail of backward (layer1 + stem: one branch, 113 MB tensors) finishes last.  Close a bucket
-        # where it begins, whatever its size, so that the final slab reduction (the only work left after the last
-        # weight gradient, in front of the optimiser) covers just the stem / layer1 slabs instead of every layer
-        # since the last 16 MB boundary.
-        tail_keys = ["transition1.0.0.weight", "layer1.1.conv1.weight"]
-        force_at = {st.param_off[k] for k in tail_keys if k in st.param_off}
-
-        def bucket_add(off: int, size: int):
-            bk["done"] += size
-            bk["lo"] = min(bk["lo"], off)
-
-        self._wg_pending: Dict[Tuple, List] = {}   # grouped weight gradients waiting for their group to fill
-        def bucket_close(force: bool = False):
-            complete = bk["done"] == bk["hi"] - bk["lo"]          # suffix [lo, hi) fully covered
-            force = force or (complete and bk["lo"] in force_at)
-            if not complete or bk["done"] == 0 or (bk["done"] < bucket_min and not force):
-                return
-            assert complete
-            for key in list(self._wg_pending):                     # the bucket's slab reduction reads every member's slabs
-                self._flush_wgrad_group(ops, key)
-            rr, br = capi.ReduceRange(), capi.BNRange()
-            b = dict(lo=bk["lo"], hi=bk["hi"], slab0=bk["slab0"], slab1=len(self.slabs), rr=rr, br=br)
-            wstrm = bk["strm"]
-            ops.append(("stl_reduce_slabs_range", rr, wstrm, list(bk["reads"]), [("bucket", len(self.buckets))]))
-            ops.append(("stl_bn_grads_range", br, wstrm, [("bucket", len(self.buckets))], [("bucketbn", len(self.buckets))]))
-            b["op"] = len(ops) - 1
-            self.buckets.append(b)
-            bk.update(done=0, hi=bk["lo"], slab0=len(self.slabs), reads=[])
-        self._nactive: Dict[int, int] = {}   # id(desc) -> branch streams busy with the data-gradient chain around that op
-        cur_active = self.nstreams
-
-        active_of = self._active_of
-        n_before = 0
+        self._red_arena = self.rstats if self.training else self.sink   # eval plans (input_grad) compute data gradients only
+        self._wg_pending: Dict[Tuple, List[Launch]] = {}   # grouped weight gradients waiting for their group to fill
+        self.sched_estimate_us = [0.0] * self.nstreams     # per stream: estimated time of its launches so far (_emit)
+        self._active = self.nstreams   # branch streams busy with the data-gradient chain around the node being walked
+        self.buckets: List[Bucket] = []
+        self._bucket = _OpenBucket(self.store.nparam, self.store.nparam)
+        node_backward = {HeadNode: self._head_backward, FuseNode: self._fuse_backward, ConvNode: self._conv_backward}
         for node in reversed(self.tape):
-            kind = node[0]
-            for o in ops[n_before:]:
-                self._nactive.setdefault(id(o[1]), cur_active)
-            n_before = len(ops)
-            if kind == "conv":
-                cur_active = min(self.nstreams, active_of(node[3].key))
-            bucket_close()   # after the previous node's ops: closes a bucket when a complete suffix is large enough
-            if kind == "head":
-                _, x, key, joints = node
-                x.bwd_seen += 1
-                nblk = max(1, min(256, math.ceil(x.B * x.H * x.W / 256)))   # <= one 256-pixel chunk per block
-                dx = self._new_grad(x)
-                nel = joints * x.C + joints
-                part_off = self._slab_elems
-                self._slab_elems += (nblk * nel + 3) // 4 * 4   # keep every entry 16-byte aligned
-                hb = capi.HeadBwd()
-                hb.dtype, hb.B, hb.H, hb.W, hb.Ci, hb.J, hb.nblk = capi.dt2(self.dtype, self.fdtype), x.B, x.H, x.W, x.C, joints, nblk
-                hb.x, hb.w, hb.dout, hb.dx = x.ptr, self.head_w, self.dout.data_ptr(), dx.data_ptr()
-                self._head_bwd_args = (hb, part_off)
-                ops.append(("stl_head_backward", hb, 0, [self.dout.data_ptr(), x.ptr], [dx.data_ptr(), id(hb)]))
-                x.grads.append(dx)
-                if not wgrads:   # the kernel still writes its weight-gradient partials: into the slab arena, unreduced
-                    continue
-                bk["reads"].append(id(hb))
-                bucket_add(st.param_off[key + ".weight"], joints * x.C)
-                bucket_add(st.param_off[key + ".bias"], joints)
-                self.slabs.append(dict(part_off=part_off, grad_off=st.param_off[key + ".weight"], nsplit=nblk,
-                                       Co=joints, Ci=x.C, ks=1, Cip=x.C, patch=0, stride=nel))
-                self.slabs.append(dict(part_off=part_off + joints * x.C, grad_off=st.param_off[key + ".bias"],
-                                       nsplit=nblk, Co=joints, Ci=1, ks=1, Cip=1, patch=0, stride=nel))
-            elif kind == "fuse":
-                _, terms, z, relu, strm = node
-                for a, _s, _ in terms:
-                    a.bwd_seen += 1
-                if z.fused_du is not None:
-                    # the ReLU mask, the BatchNorm reductions and the sum of contributions were done in the
-                    # epilogue of the data gradient that produced the last contribution (mask_z)
-                    assert not z.grads
-                    z.grads.append(z.fused_du)
-                assert 1 <= len(z.grads) <= 4, f"fuse output has {len(z.grads)} gradient contributions"
-                p = capi.FuseBwd()
-                p.dtype, p.B, p.H, p.W, p.C = self.dtype, z.B, z.H, z.W, z.C
-                p.ydtype = self.ydtype
-                p.ngrads, p.relu = len(z.grads), int(relu)
-                for i, gt in enumerate(z.grads):
-                    p.dz[i] = gt.data_ptr()
-                p.z = z.ptr
-                same_bn = [a for a, s, _ in terms if a.kind == "bn" and s == 0]
-                p.nbn = len(same_bn)
-                for i, a in enumerate(same_bn):
-                    p.bn[i] = self._src(a)
-                    p.rstats[i] = red(a.bn)
-                trivial = (len(z.grads) == 1 and not relu and not same_bn) or z.fused_du is not None
-                du = z.grads[0] if trivial else self._new_grad(z)
-                p.du = du.data_ptr()
-                if not trivial:
-                    ops.append(("stl_fuse_backward", p, strm, [gt.data_ptr() for gt in z.grads], [du.data_ptr()]))
-                for a, s, _ in terms:
-                    if a.kind == "plain":
-                        assert s == 0, "upsampled plain terms do not occur in this network"
-                        if a.needs_grad:
-                            a.grads.append(du)
-                    elif s == 0:
-                        a.dt = du
-                    else:
-                        u = capi.UpBwd()
-                        u.dtype, u.B, u.H, u.W, u.C, u.shift = self.dtype, a.B, a.H, a.W, a.C, s
-                        u.ydtype = self.ydtype
-                        u.du = du.data_ptr()
-                        a.dt = self._new_grad(a)
-                        u.dt = a.dt.data_ptr()
-                        u.bn = self._src(a)
-                        u.rstats = red(a.bn)
-                        ops.append(("stl_upsample_backward", u, strm, [du.data_ptr()], [a.dt.data_ptr()]))
-            else:  # conv
-                _, x, y, ci, (kks, kstride), strm = node
-                x.bwd_seen += 1
-                assert y.consumers == 1 and y.dt is not None, f"{ci.key}: BN activation must have exactly one consumer"
-                g = self._gsrc(y)
-                if wgrads:
-                    self._emit_wgrad(ops, bk, x, y, ci, g, kks, kstride, strm)
-                    bucket_add(ci.master_off, ci.Co * ci.Ci * ci.ks * ci.ks)
-                    bucket_add(y.bn.param_off, 2 * y.bn.C)   # gamma, beta of the BatchNorm behind this conv
-                # ---- data gradient
-                if not x.needs_grad:
-                    continue
-                d = capi.Conv()
-                d.dtype, d.ydtype = self.dtype, self.ydtype
-                d.B, d.Hi, d.Wi, d.Ci = y.B, y.H, y.W, y.C
-                d.Ho, d.Wo, d.Co = x.H, x.W, x.C
-                d.ks, d.stride, d.stuff = kks, 1, int(kstride == 2)
-                d.TH, d.TW, d.shape = 0, 0, -1
-                d.src = g   # (before the plan: data gradients get a block shape of their own)
-                capi.call("stl_conv_plan", C.byref(d))
-                d.w = self.wk.data_ptr() + ci.bwd_off * self.esz
-                dreads = [y.dt.data_ptr()]
-                if x.kind == "plain":
-                    out = self._new_grad(x)
-                    if x.grads:
-                        ad = x.grads.pop()
-                        d.addend = ad.data_ptr()
-                        dreads.append(ad.data_ptr())
-                    # Residual block end z = ReLU(BN(y) + skip): when this data gradient is the LAST
-                    # contribution to dz, its epilogue also applies the ReLU mask and reduces the
-                    # BatchNorm-backward sums, so no separate pass over dz / z / y is needed.
-                    F = producer.get(id(x))
-                    same_bn = [a for a, s_, _ in F[1] if a.kind == "bn" and s_ == 0] if F else []
-                    if (F is not None and F[3] and len(same_bn) == 1 and not x.grads
-                            and x.bwd_seen == x.consumers):
-                        ybn = same_bn[0]
-                        d.mask_z = x.ptr
-                        d.mask_y = ybn.ptr
-                        d.mask_bn = self._src(ybn, relu=False)
-                        d.red = red(ybn.bn)
-                        dreads += [x.ptr, ybn.ptr]
-                        x.fused_du = out
-                    else:
-                        x.grads.append(out)
-                else:
-                    assert x.dt is None
-                    out = self._new_grad(x)
-                    x.dt = out
-                    d.mask_y = x.ptr
-                    d.mask_bn = self._src(x)
-                    d.red = red(x.bn)
-                d.out = out.data_ptr()
-                ops.append(("stl_conv_forward", d, strm, dreads, [out.data_ptr()]))
-        if wgrads:
-            bucket_close(force=True)
+            if isinstance(node, ConvNode):
+                self._active = min(self.nstreams, self._active_of(node.conv.key))
+            if self.training:
+                self._bucket_close()   # after the previous node's ops: closes a bucket when a complete suffix is large enough
+            node_backward[type(node)](node)
+        if self.training:
+            self._bucket_close(force=True)
+            assert self._bucket.done == 0 and self._bucket.hi == 0, "gradient buckets do not cover the parameter buffer"
         if self.input_grad:
-            self._emit_patch_backward(ops)
-        for o in ops[n_before:]:
-            self._nactive.setdefault(id(o[1]), cur_active)
-        # slab arena + reduce table
+            self._emit_patch_backward()
         self.slab_arena = torch.zeros(max(self._slab_elems, 1), dtype=torch.float32, device=self.dev)
-        base = self.slab_arena.data_ptr()
-        hb, off = self._head_bwd_args
-        hb.partial = base + 4 * off
-        if not wgrads:
-            self.bwd_ops = self._balance_streams(ops)
-            return
-        assert bk["done"] == 0 and bk["hi"] == 0, "gradient buckets do not cover the parameter buffer"
-        for s in self.slabs:
-            if "struct" in s:
-                s["struct"].partial = base + 4 * s["part_off"]
-        tab = (capi.Slab * len(self.slabs))()
-        blk = 0
-        for i, s in enumerate(self.slabs):
-            e = tab[i]
-            e.part_off, e.grad_off, e.nsplit = s["part_off"], s["grad_off"], s["nsplit"]
-            e.Co, e.Ci, e.ks, e.Cip, e.patch, e.blk0, e.pad = s["Co"], s["Ci"], s["ks"], s["Cip"], s["patch"], blk, s["stride"]
-            blk += math.ceil(s["Co"] * s["Ci"] * s["ks"] * s["ks"] / 1024)
-        self._slab_blocks, self._slab_n = blk, len(self.slabs)
-        self._slab_tab = _to_device(tab, self.dev)
-        blk0 = [tab[i].blk0 for i in range(len(self.slabs))] + [blk]
-        bn_off = [b_.param_off for b_ in self.bns]            # forward (= ascending offset) order
-        assert bn_off == sorted(bn_off)
-        import bisect
-        for b in self.buckets:
-            rr, br = b["rr"], b["br"]
-            rr.partials, rr.grads = self.slab_arena.data_ptr(), st.grads.data_ptr()
-            rr.tab = self._slab_tab.data_ptr() + b["slab0"] * C.sizeof(capi.Slab)
-            rr.n, rr.blk_base, rr.nblocks = b["slab1"] - b["slab0"], blk0[b["slab0"]], blk0[b["slab1"]] - blk0[b["slab0"]]
-            i0, i1 = bisect.bisect_left(bn_off, b["lo"]), bisect.bisect_left(bn_off, b["hi"])
-            br.rstats, br.grads = self.rstats.data_ptr(), st.grads.data_ptr()
-            br.tab, br.n = self._bn_tab.data_ptr() + i0 * C.sizeof(capi.BNRec), i1 - i0
-        self.bwd_ops = self._balance_streams(ops)
-        for b in self.buckets:   # bucket events are addressed by op index
-            b["op"] = next(i for i, o in enumerate(self.bwd_ops) if o[1] is b["br"])
+        self._resolve("slab", self.slab_arena)
+        if self.training:
+            self._slab_tab = _to_device((capi.Slab * len(self.slabs))(*self.slabs), self.dev)
+            self._resolve("slab_tab", self._slab_tab)
 
-    def _emit_patch_backward(self, ops):
+    def _head_backward(self, n: HeadNode):
+        x, J, st = n.x, n.joints, self.store
+        x.bwd_seen += 1
+        nblk = max(1, min(256, math.ceil(x.B * x.H * x.W / 256)))   # <= one 256-pixel chunk per block
+        dx = self._new_grad(x)
+        nel = J * x.C + J
+        hb = capi.HeadBwd()
+        hb.dtype, hb.B, hb.H, hb.W, hb.Ci, hb.J, hb.nblk = capi.dt2(self.dtype, self.fdtype), x.B, x.H, x.W, x.C, J, nblk
+        hb.x, hb.w, hb.dout, hb.dx = x.ptr, self.head_w, self.dout.data_ptr(), dx.data_ptr()
+        part_off = self._slab_alloc(hb, nblk * nel)
+        self._emit("stl_head_backward", hb, 0, [self.dout.data_ptr(), x.ptr], [dx.data_ptr(), C.addressof(hb)])
+        x.grads.append(dx)
+        if not self.training:   # the kernel still writes its weight-gradient partials: into the slab arena, unreduced
+            return
+        w_off, b_off = st.param_off[n.key + ".weight"], st.param_off[n.key + ".bias"]
+        self._bucket.reads.append(C.addressof(hb))
+        self._bucket.add(w_off, J * x.C + J)   # the bias follows the weight
+        self._add_slab(part_off, w_off, nblk, J, x.C, 1, x.C, 0, stride=nel)
+        self._add_slab(part_off + J * x.C, b_off, nblk, J, 1, 1, 1, 0, stride=nel)
+
+    def _fuse_backward(self, n: FuseNode):
+        z = n.z
+        for a, _s, _ in n.terms:
+            a.bwd_seen += 1
+        if z.fused_du is not None:
+            # the ReLU mask, the BatchNorm reductions and the sum of contributions were done in the
+            # epilogue of the data gradient that produced the last contribution (mask_z)
+            assert not z.grads
+            z.grads.append(z.fused_du)
+        grads, same_bn = z.grads, n.same_bn
+        assert 1 <= len(grads) <= 4, f"fuse output has {len(grads)} gradient contributions"
+        if (len(grads) == 1 and not n.relu and not same_bn) or z.fused_du is not None:
+            du = grads[0]   # nothing left to do: the gradient passes through
+        else:
+            du = self._new_grad(z)
+            p = capi.FuseBwd()
+            p.dtype, p.B, p.H, p.W, p.C = self.dtype, z.B, z.H, z.W, z.C
+            p.ydtype = self.ydtype
+            p.ngrads, p.relu = len(grads), int(n.relu)
+            for i, gt in enumerate(grads):
+                p.dz[i] = gt.data_ptr()
+            p.z = z.ptr
+            p.nbn = len(same_bn)
+            for i, a in enumerate(same_bn):
+                p.bn[i] = self._src(a)
+                p.rstats[i] = self._red(a.bn)
+            p.du = du.data_ptr()
+            self._emit("stl_fuse_backward", p, n.op.stream, [gt.data_ptr() for gt in grads], [du.data_ptr()])
+        for a, s, _ in n.terms:
+            if a.kind == "plain":
+                assert s == 0, "upsampled plain terms do not occur in this network"
+                if a.needs_grad:
+                    a.grads.append(du)
+            elif s == 0:
+                a.dt = du
+            else:   # the adjoint of the nearest upsample, with the BatchNorm-backward sums of the term
+                u = capi.UpBwd()
+                u.dtype, u.B, u.H, u.W, u.C, u.shift = self.dtype, a.B, a.H, a.W, a.C, s
+                u.ydtype = self.ydtype
+                u.du = du.data_ptr()
+                a.dt = self._new_grad(a)
+                u.dt = a.dt.data_ptr()
+                u.bn = self._src(a)
+                u.rstats = self._red(a.bn)
+                self._emit("stl_upsample_backward", u, n.op.stream, [du.data_ptr()], [a.dt.data_ptr()])
+
+    def _conv_backward(self, n: ConvNode):
+        """Weight gradient (training plans) and data gradient of one convolution."""
+        x, y, ci = n.x, n.y, n.conv
+        x.bwd_seen += 1
+        assert y.consumers == 1 and y.dt is not None, f"{ci.key}: BN activation must have exactly one consumer"
+        g = self._gsrc(y)
+        if self.training:
+            self._emit_wgrad(n, g)
+            self._bucket.add(ci.master_off, ci.Co * ci.Ci * ci.ks * ci.ks)
+            self._bucket.add(y.bn.param_off, 2 * y.bn.C)   # gamma, beta of the BatchNorm behind this conv
+        if not x.needs_grad:
+            return
+        d = capi.Conv()
+        d.dtype, d.ydtype = self.dtype, self.ydtype
+        d.B, d.Hi, d.Wi, d.Ci = y.B, y.H, y.W, y.C
+        d.Ho, d.Wo, d.Co = x.H, x.W, x.C
+        d.ks, d.stride, d.stuff = n.ks, 1, int(n.stride == 2)
+        d.TH, d.TW, d.shape = 0, 0, -1
+        d.src = g   # (before the plan: data gradients get a block shape of their own)
+        capi.call("stl_conv_plan", C.byref(d))
+        d.w = self.wk.data_ptr() + ci.bwd_off * self.esz
+        reads = [y.dt.data_ptr()]
+        out = self._new_grad(x)
+        if x.kind == "bn":
+            assert x.dt is None
+            x.dt = out
+            d.mask_y = x.ptr
+            d.mask_bn = self._src(x)
+            d.red = self._red(x.bn)
+        else:
+            if x.grads:
+                ad = x.grads.pop()
+                d.addend = ad.data_ptr()
+                reads.append(ad.data_ptr())
+            # Residual block end z = ReLU(BN(y) + skip): when this data gradient is the LAST
+            # contribution to dz, its epilogue also applies the ReLU mask and reduces the
+            # BatchNorm-backward sums, so no separate pass over dz / z / y is needed.
+            F = x.producer
+            if F is not None and F.relu and len(F.same_bn) == 1 and not x.grads and x.bwd_seen == x.consumers:
+                ybn = F.same_bn[0]
+                d.mask_z = x.ptr
+                d.mask_y = ybn.ptr
+                d.mask_bn = self._src(ybn, relu=False)
+                d.red = self._red(ybn.bn)
+                reads += [x.ptr, ybn.ptr]
+                x.fused_du = out
+            else:
+                x.grads.append(out)
+        d.out = out.data_ptr()
+        self._emit("stl_conv_forward", d, n.stream, reads, [out.data_ptr()])
+
+    def _emit_patch_backward(self):
         """Image gradient: the adjoint of the stem's patch gather (stl_patch3x3_backward) over the patch tensor's data gradient,
         which the stem conv's data-gradient launch (a 1x1 conv onto 32-wide patches, weights [kk][Co]) has just written."""
         x = self._patches
@@ -636,12 +638,50 @@ class Engine:
         pb = capi.PatchBwd()
         pb.dtype, pb.B, pb.H, pb.W, pb.stride = self.dtype, self.B, self.H, self.W, 2
         pb.dpatch, pb.dimg = x.grads[0].data_ptr(), self.dimg.data_ptr()
-        ops.append(("stl_patch3x3_backward", pb, 0, [x.grads[0].data_ptr()], [self.dimg.data_ptr()]))
+        self._emit("stl_patch3x3_backward", pb, 0, [pb.dpatch], [pb.dimg])
 
-    def _op_cost_us(self, op) -> float:
+    def _slab_alloc(self, desc, nelem: int) -> int:
+        """Room for `nelem` weight-gradient partial sums of `desc` in the slab arena: their offset (fp32 elements), where
+        desc.partial points once the arena exists."""
+        off = self._slab_elems
+        self._fix(desc, "partial", "slab", 4 * off)
+        self._slab_elems += (nelem + 3) // 4 * 4   # keep every entry 16-byte aligned
+        return off
+
+    def _add_slab(self, part_off, grad_off, nsplit, Co, Ci, ks, Cip, patch, stride=0):
+        self.slabs.append(capi.Slab(part_off, grad_off, nsplit, Co, Ci, ks, Cip, patch, self._slab_blocks, stride))
+        self._slab_blocks += math.ceil(Co * Ci * ks * ks / 1024)
+
+    def _bucket_close(self, force: bool = False):
+        """Emit the open bucket's slab reduction and BatchNorm gradients, every field final, if the bucket is complete and
+        large enough (or forced); the next bucket opens below it."""
+        bk, st = self._bucket, self.store
+        complete = bk.done == bk.hi - bk.lo          # suffix [lo, hi) fully covered
+        # The serial tail of backward (layer1 + stem: one branch, 113 MB tensors) finishes last.  Close a bucket
+        # where it begins, whatever its size, so that the final slab reduction (the only work left after the last
+        # weight gradient, in front of the optimiser) covers just the stem / layer1 slabs instead of every layer
+        # since the last 16 MB boundary.
+        force = force or (complete and bk.lo in {st.param_off.get(k) for k in ("transition1.0.0.weight", "layer1.1.conv1.weight")})
+        if not complete or bk.done == 0 or (bk.done < int(self.bucket_mb * (1 << 20) / 4) and not force):
+            return
+        for key in list(self._wg_pending):            # the bucket's slab reduction reads every member's slabs
+            self._flush_wgrad_group(key)
+        grads = st.grads.data_ptr()
+        blk0 = self.slabs[bk.slab0].blk0   # (done > 0: the bucket has slabs)
+        rr = capi.ReduceRange(grads=grads, n=len(self.slabs) - bk.slab0, blk_base=blk0, nblocks=self._slab_blocks - blk0)
+        self._fix(rr, "partials", "slab", 0)
+        self._fix(rr, "tab", "slab_tab", bk.slab0 * C.sizeof(capi.Slab))
+        i0, i1 = bisect.bisect_left(self._bn_offs, bk.lo), bisect.bisect_left(self._bn_offs, bk.hi)
+        br = capi.BNRange(rstats=self.rstats.data_ptr(), grads=grads, tab=self._bn_tab.data_ptr() + i0 * C.sizeof(capi.BNRec),
+                          n=i1 - i0)
+        self._emit("stl_reduce_slabs_range", rr, bk.stream, bk.reads, [C.addressof(rr)])
+        self._emit("stl_bn_grads_range", br, bk.stream, [C.addressof(rr)], [C.addressof(br)])
+        self.buckets.append(Bucket(bk.lo, bk.hi, len(self.bwd_ops) - 1))
+        bk.hi, bk.done, bk.slab0, bk.reads = bk.lo, 0, len(self.slabs), []
+
+    def _op_cost_us(self, name: str, d) -> float:
         """Rough duration of a backward launch for the list scheduler: a fixed launch + latency-chain part plus its
         bytes at ~2 TB/s (what these launches achieve)."""
-        name, d = op[0], op[1]
         esz = self.esz
         if name == "stl_conv_forward":
             src = d.B * d.Hi * d.Wi * d.Ci * (2 if d.src.mode == capi.SRC_BNBWD else 1)
@@ -664,9 +704,9 @@ class Engine:
             return 20.0 + 80.0 * d.nblocks / 1100.0
         return 5.0
 
-    def _balance_streams(self, ops):
-        """Static placement of the off-chain backward launches (weight gradients, slab reductions, BatchNorm
-        gradients) onto the branch streams -- one hardware queue each.  (With extra weight-gradient streams two
+    def _emit(self, name: str, desc, stream: int, reads: list, writes: list):
+        """Append a backward launch; an off-chain one (weight gradient, slab reduction, BatchNorm gradients) is placed here,
+        statically, onto the branch streams -- one hardware queue each.  (With extra weight-gradient streams two
         streams share a queue and every switch between them costs ~6 us: 475 such gaps per step in
         profiles/r02_trace_default_summary.txt; on its own branch stream a weight gradient delays the
         data-gradient chain.)  Where the network has fewer branches than streams -- stage 3, stage 2, and the
@@ -676,26 +716,20 @@ class Engine:
         weight gradients beside the data-gradient chain slow every one of them down by more than the overlap
         buys (round 2, tail queues 3 / 2 / 1 / 0: 16.98 / 16.86 / 16.82 / 17.33 ms per step; round 3 with ungrouped
         tail launches 3 / 2 / 1: 14.87 / 14.72 / 14.82)."""
-        acc = [0.0] * self.nstreams
-        out = []
-        for op in ops:
-            name, desc, strm, reads, writes = op
-            cost = self._op_cost_us(op)
-            if name in ("stl_conv_wgrad", "stl_conv_wgrad_group", "stl_reduce_slabs_range", "stl_bn_grads_range"):
-                active = self._nactive.get(id(desc), self.nstreams)
-                own = strm % self.nstreams
-                cands = list(range(active, self.nstreams)) + [own]
-                if active == 1:   # the single-branch tail: TWO of its three idle queues (see above)
-                    cands = list(range(1, min(3, self.nstreams))) + [own]
-                strm = min(cands, key=lambda s_: (acc[s_], s_ != own))
-            acc[strm] += cost
-            out.append((name, desc, strm, reads, writes))
-        self.sched_estimate_us = list(acc)
-        return out
+        acc = self.sched_estimate_us
+        if name in ("stl_conv_wgrad", "stl_conv_wgrad_group", "stl_reduce_slabs_range", "stl_bn_grads_range"):
+            own = stream % self.nstreams
+            cands = list(range(self._active, self.nstreams)) + [own]
+            if self._active == 1:   # the single-branch tail: TWO of its three idle queues (see above)
+                cands = list(range(1, min(3, self.nstreams))) + [own]
+            stream = min(cands, key=lambda s_: (acc[s_], s_ != own))
+        acc[stream] += self._op_cost_us(name, desc)
+        self.bwd_ops.append(Launch(name, desc, stream, reads, writes))
 
-    def _emit_wgrad(self, ops, bk, x: Act, y: Act, ci: ConvInfo, g, kks: int, kstride: int, strm: int):
+    def _emit_wgrad(self, n: ConvNode, g: capi.Src):
         """Weight-gradient launch of one convolution (split-K slabs): off the critical path (only the data-gradient chain
-        is on it); _balance_streams places it on an idle queue where there is one."""
+        is on it); _emit places it on an idle queue where there is one."""
+        x, y, ci, kks, kstride = n.x, n.y, n.conv, n.ks, n.stride
         wg = capi.Wgrad()
         wg.dtype, wg.ydtype = self.dtype, self.ydtype
         wg.B, wg.Hi, wg.Wi, wg.Ci, wg.Ho, wg.Wo, wg.Co = x.B, x.H, x.W, x.C, y.H, y.W, y.C
@@ -723,112 +757,116 @@ class Engine:
         wg.nsplit = min(range(1, top + 1), key=lambda ns: (math.ceil(npt / ns) + 0.004 * ns * chunks / 8, ns))
         wg.h = self._src(x)
         wg.g = g
-        nel = y.C * kks * kks * x.C
-        part_off = self._slab_elems
-        self._slab_elems += (wg.nsplit * nel + 3) // 4 * 4
-        self.slabs.append(dict(part_off=part_off, grad_off=ci.master_off, nsplit=wg.nsplit, Co=ci.Co, Ci=ci.Ci,
-                               ks=ci.ks, Cip=ci.Cik, patch=int(ci.patch), stride=0, struct=wg))
-        bk["reads"].append(id(wg))
-        bk["strm"] = strm
-        if gsize == 1:
-            ops.append(("stl_conv_wgrad", wg, strm, [y.dt.data_ptr(), x.ptr], [id(wg)]))
-            return
+        part_off = self._slab_alloc(wg, wg.nsplit * y.C * kks * kks * x.C)
+        self._add_slab(part_off, ci.master_off, wg.nsplit, ci.Co, ci.Ci, ci.ks, ci.Cik, int(ci.patch))
+        self._bucket.reads.append(C.addressof(wg))
+        self._bucket.stream = n.stream
         key = (x.C, y.C, kks, kstride, x.H, x.W, wg.TH, wg.TW, wg.nsplit, int(g.mode), gsize)
         pend = self._wg_pending.setdefault(key, [])
-        pend.append((wg, [y.dt.data_ptr(), x.ptr], strm))
+        pend.append(Launch("stl_conv_wgrad", wg, n.stream, [y.dt.data_ptr(), x.ptr], [C.addressof(wg)]))
         if len(pend) >= gsize:
-            self._flush_wgrad_group(ops, key)
+            self._flush_wgrad_group(key)
 
-    def _flush_wgrad_group(self, ops, key):
-        pend = self._wg_pending.pop(key, [])
-        if not pend:
-            return
+    def _flush_wgrad_group(self, key):
+        pend = self._wg_pending.pop(key)
         if len(pend) == 1:
-            wg, reads, wstrm = pend[0]
-            ops.append(("stl_conv_wgrad", wg, wstrm, reads, [id(wg)]))
+            self._emit(*pend[0])
             return
+        members = [op.desc for op in pend]
         grp = capi.WgradGroup()
-        grp.n = len(pend)
-        for i, (wg, _r, _s) in enumerate(pend):
+        grp.n = len(members)
+        for i, wg in enumerate(members):
             grp.p[i] = C.pointer(wg)
-        self._keep.append([wg for wg, _r, _s in pend])
-        grp.members = [wg for wg, _r, _s in pend]   # python-side view (bench, tools)
-        ops.append(("stl_conv_wgrad_group", grp, pend[-1][2], [r for _w, rs, _s in pend for r in rs], [id(wg) for wg, _r, _s in pend]))
+        grp.members = members   # python-side view (bench, tools); keeps the members alive
+        self._emit("stl_conv_wgrad_group", grp, pend[-1].stream, [r for op in pend for r in op.reads],
+                   [w for op in pend for w in op.writes])
 
     def _build_tables(self):
-        tab = (capi.BNRec * len(self.bns))()
-        for i, b in enumerate(self.bns):
-            e = tab[i]
-            e.stats_off, e.param_off, e.buf_off, e.C, e.inv_count = b.stats_off, b.param_off, b.buf_off, b.C, b.inv_count
-        self._bn_tab = _to_device(tab, self.dev)
+        tab = [capi.BNRec(b.stats_off, b.param_off, b.buf_off, b.C, b.inv_count) for b in self.bns]
+        self._bn_tab = _to_device((capi.BNRec * len(tab))(*tab), self.dev)
         # num_batches_tracked entries are in registry (state_dict) order == self.bns order
         assert len(self.bns) == self.store.nnbt
+        self._bn_offs = [b.param_off for b in self.bns]   # ascending: a bucket's BatchNorm range is found by bisection
+        assert self._bn_offs == sorted(self._bn_offs)
 
     # ------------------------------------------------------------------ execution
-    def _schedule(self, ops):
-        """Cross-stream RAW dependencies: op index -> indices it must wait for / whether it records.  A wait is
-        dropped when the consumer's stream already knows the producer to be complete -- directly (an earlier wait on
-        the same or a later op of that stream) or transitively (vector clocks: 41 of 183 waits of the W32 backward)."""
-        last, waits, need = {}, [], set()
-        ns = max(o[2] for o in ops) + 1 if ops else 1
+    def _schedule(self, ops: List[Launch], recorded) -> Tuple[List[List[int]], set]:
+        """Cross-stream RAW dependencies: op index -> indices it must wait for / whether it records (a waited-for op, or
+        one of `recorded`).  A wait is dropped when the consumer's stream already knows the producer to be complete --
+        directly (an earlier wait on the same or a later op of that stream) or transitively (vector clocks: 41 of 183
+        waits of the W32 backward)."""
+        last, waits, need = {}, [], set(recorded)
+        ns = max(o.stream for o in ops) + 1 if ops else 1
         clock = [[-1] * ns for _ in range(ns)]   # clock[s][t]: latest op of stream t known complete at this point of stream s
         snap = {}
-        for i, (_, _, st_, reads, writes) in enumerate(ops):
+        for i, op in enumerate(ops):
+            s = op.stream
             w = set()
-            for r in reads:
+            for r in op.reads:
                 j = last.get(r)
-                if j is not None and ops[j][2] != st_:
+                if j is not None and ops[j].stream != s:
                     w.add(j)
             latest = {}
             for j in w:                      # streams are in-order: the latest producer per stream covers the others
-                latest[ops[j][2]] = max(latest.get(ops[j][2], -1), j)
+                latest[ops[j].stream] = max(latest.get(ops[j].stream, -1), j)
             w = set()
             for t, j in latest.items():
-                if clock[st_][t] >= j:
+                if clock[s][t] >= j:
                     continue                 # already ordered behind it
                 w.add(j)
                 for u in range(ns):
-                    clock[st_][u] = max(clock[st_][u], snap[j][u])
-            clock[st_][st_] = i
-            snap[i] = list(clock[st_])
+                    clock[s][u] = max(clock[s][u], snap[j][u])
+            clock[s][s] = i
+            snap[i] = list(clock[s])
             need.update(w)
             waits.append(sorted(w))
-            for t in writes:
+            for t in op.writes:
                 last[t] = i
-        need.update(b["op"] for b in getattr(self, "buckets", []) if ops is self.bwd_ops)
         return waits, need
 
-    def _program(self, ops):
-        """Compile an op list into a native program (csrc/program.hip), once."""
-        key = id(ops)
-        prog = self._progs.get(key)
-        if prog is None:
-            waits, need = self._schedule(ops)
-            arr = (capi.Op * max(len(ops), 1))()
-            for i, (name, desc, st_, _, _) in enumerate(ops):
-                o = arr[i]
-                o.kind, o.stream, o.desc = capi.OP_KIND[name], st_, C.addressof(desc)
-                assert len(waits[i]) <= 8, "op waits on more than 8 producers"
-                o.nwait = len(waits[i])
-                for j, wv in enumerate(waits[i]):
-                    o.wait[j] = wv
-                o.record = int(i in need)
-            h = C.c_void_p()
-            capi.call("stl_program_create", arr, len(ops), self.nstreams, C.byref(h))
-            prog = self._progs[key] = (h, arr)
-        return prog[0]
+    def _compile(self, ops: List[Launch], recorded) -> C.c_void_p:
+        """Compile an op list into a native program (csrc/program.hip)."""
+        waits, need = self._schedule(ops, recorded)
+        arr = (capi.Op * max(len(ops), 1))()
+        for i, op in enumerate(ops):
+            o = arr[i]
+            o.kind, o.stream, o.desc = capi.OP_KIND[op.name], op.stream, C.addressof(op.desc)
+            assert len(waits[i]) <= 8, "op waits on more than 8 producers"
+            o.nwait = len(waits[i])
+            for j, wv in enumerate(waits[i]):
+                o.wait[j] = wv
+            o.record = int(i in need)
+        h = C.c_void_p()
+        capi.call("stl_program_create", arr, len(ops), self.nstreams, C.byref(h))
+        self._keep.append(arr)
+        return h
 
-    def _run(self, ops, stream: int):
-        """Replay a program natively.  With several streams the independent branches of each
-        exchange module (and, in backward, the weight gradients) run concurrently; fork/join and
-        cross-stream dependencies are HIP events inside stl_program_run."""
-        h = self._program(ops)
+    def _program(self, which: str) -> C.c_void_p:
+        """The forward ("fwd") or backward ("bwd") program, compiled once; the backward one records an event at the last
+        op of every gradient bucket (bucket_wait)."""
+        if which not in self._progs:
+            self._progs[which] = (self._compile(self.fwd_ops, ()) if which == "fwd" else
+                                  self._compile(self.bwd_ops, [b.op for b in self.buckets]))
+        return self._progs[which]
+
+    def _run(self, h, stream: int, on_bucket=None):
+        """Replay a native program on `stream` and the side streams.  With several streams the independent branches of
+        each exchange module (and, in backward, the weight gradients) run concurrently; fork/join and cross-stream
+        dependencies are HIP events inside stl_program_run.  on_bucket (the backward program): issue it range by range
+        (stl_program_run_range) and call on_bucket(i) right after gradient bucket i's last op has been enqueued."""
         if self._side is None:
             self._make_streams()
         self._stream_arr[0] = stream
-        rc = self.lib.stl_program_run(h, self._stream_arr)
-        if rc != 0:
-            raise RuntimeError(f"stl_program_run: {self.lib.stl_last_error().decode()}")
+        if on_bucket is None:
+            if self.lib.stl_program_run(h, self._stream_arr) != 0:
+                raise RuntimeError(f"stl_program_run: {self.lib.stl_last_error().decode()}")
+            return
+        first = 0
+        for i, b in enumerate(self.buckets):   # in op order: buckets are emitted as they close
+            capi.call("stl_program_run_range", h, self._stream_arr, first, b.op + 1)
+            first = b.op + 1
+            on_bucket(i)
+        capi.call("stl_program_run_range", h, self._stream_arr, first, len(self.bwd_ops))
 
     def _make_streams(self):
         """HIP streams of the program: index 0 is the caller's stream, 1 .. nstreams-1 the other branch streams.
@@ -860,7 +898,7 @@ class Engine:
         self.prep_weights(stream)
         if self.training:
             self.stats.zero_()
-        self._run(self.fwd_ops, stream)
+        self._run(self._program("fwd"), stream)
         if self.training and update_running:
             st = self.store
             capi.call("stl_bn_running_update", self.stats.data_ptr(), st.bufs.data_ptr(), st.nbt.data_ptr(),
@@ -893,28 +931,15 @@ class Engine:
         data-parallel path enqueues the bucket's all-reduce there, so that in every in-order hardware queue it sits directly
         behind the bucket instead of behind the rest of backward."""
         assert self.training or self.input_grad
-        if not self.training:   # eval + input_grad: dimg only; rstats stays zero, the reductions go to the sink
-            self._run(self.bwd_ops, stream)
-            return
-        self.rstats.zero_()
-        if on_bucket is not None and self.buckets:
-            h = self._program(self.bwd_ops)
-            if self._side is None:
-                self._make_streams()
-            self._stream_arr[0] = stream
-            first = 0
-            for op_idx, i in sorted((b["op"], i) for i, b in enumerate(self.buckets)):
-                capi.call("stl_program_run_range", h, self._stream_arr, first, op_idx + 1)
-                first = op_idx + 1
-                on_bucket(i)
-            capi.call("stl_program_run_range", h, self._stream_arr, first, len(self.bwd_ops))
-            return
-        self._run(self.bwd_ops, stream)   # includes the per-bucket slab reductions and BatchNorm gradients
+        if self.training:   # (eval + input_grad: dimg only; rstats stays zero, the reductions go to the sink)
+            self.rstats.zero_()
+        # includes the per-bucket slab reductions and BatchNorm gradients
+        self._run(self._program("bwd"), stream, on_bucket if self.buckets else None)
 
     def bucket_wait(self, i: int, stream: int):
         """Make `stream` wait until gradient bucket i (self.buckets[i]: flat slice [lo, hi)) of the
         backward pass enqueued last is final."""
-        capi.call("stl_program_wait_op", self._program(self.bwd_ops), self.buckets[i]["op"], stream)
+        capi.call("stl_program_wait_op", self._program("bwd"), self.buckets[i].op, stream)
 
 
 _STREAM_POOL: Dict[int, Dict] = {}   # device index -> {stream index: (owner object, hipStream_t)}

@@ -43,7 +43,7 @@ class TrainStep:
         # buckets = the engine's own gradient buckets (contiguous slices, final at known points of backward)
         if bf16_buckets is None:
             bf16_buckets = os.environ.get("STLPOSE_BF16_BUCKETS", "0") != "0"
-        self.dp = (FlatAllReduce(self.store.grads, process_group, bucket_mb, bounds=[(b["lo"], b["hi"]) for b in self.eng.buckets],
+        self.dp = (FlatAllReduce(self.store.grads, process_group, bucket_mb, bounds=[(b.lo, b.hi) for b in self.eng.buckets],
                                  bf16_buckets=bf16_buckets)
                    if process_group is not None else None)
         self._comm: Optional[torch.cuda.Stream] = None

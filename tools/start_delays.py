@@ -12,7 +12,7 @@ from stlpose_amd.engine import Engine
 f = sys.argv[1]; thr = float(sys.argv[2]) if len(sys.argv) > 2 else 25.0
 m = PoseHighResolutionNet("w32", "bf16"); m._pack(torch.device("cpu"))
 e = Engine(m.arch, m._store, 32, 384, 288, capi.BF16, True)
-ops = e.bwd_ops; waits, _ = e._schedule(ops)
+ops = e.bwd_ops; waits, _ = e._schedule(ops, ())
 rows = []
 for line in (gzip.open(f, 'rt') if f.endswith('.gz') else open(f)):
     if not line.startswith('"KERNEL_DISPATCH"'): continue
