@@ -405,6 +405,30 @@ int stl_pose_rank(const float* q, const float* conf, const float* db, int Q, int
                   int64_t* idx, float* dist, const int32_t* labels, const int32_t* qlabels, int L, int k_eff, double* scores,
                   void* stream);
 
+/* ---- top-down pose extraction (stlpose_amd/csrc/topdown.hip): person boxes -> crops -> HRNet -> poses, the glue of
+ * src/04_evaluate_vases_qualitatively.py:184-250 and src/05_create_archdata_retrieval_db.py:114-171. */
+#define STL_BOX_MAX 4096           /* boxes per image of stl_box_select: one workgroup sorts them in LDS (~100 KiB) */
+#define STL_RESIZE_SRC_MAX 16384   /* H * W of a source map of stl_heatmap_resize_argmax: staged in LDS (64 KiB) */
+#define STL_RESIZE_DST_MAX 2048    /* each output side of stl_heatmap_resize_argmax (per-row / per-column taps in LDS) */
+
+/* Per-image filter + greedy NMS for a ragged batch, one workgroup per image.  boxes fp32 [N, 4] (x1, y1, x2, y2), scores [N],
+ * labels int64 [N] (NULL: no label test), offsets int64 [I + 1]: image i owns rows offsets[i] .. offsets[i+1]-1 (at most max_n <=
+ * STL_BOX_MAX of them; an image above max_n gets count -1 and no output).
+ * Filter (bbox_filtering, lib/bounding_box.py:127-168): a row passes when labels == label and (score_test) score > score_thr.
+ * iou_thr < 0: filter only, the passing rows in input order.  Otherwise torchvision.ops.nms (as bbox_nms, :171-206, calls it) on
+ * the passing rows: stable descending score order (NaN first), area = (x2-x1)*(y2-y1), iou = inter / (area_i + area_j - inter)
+ * in fp32 left to right, a row suppressed when (double)iou > iou_thr; the survivors in score order.
+ * keep int32 [N]: per image segment the image-local row indices of the kept rows, then -1; count int32 [I]. */
+int stl_box_select(const float* boxes, const float* scores, const int64_t* labels, const int64_t* offsets, int num_images,
+                   int64_t N, int max_n, int64_t label, int score_test, float score_thr, double iou_thr, int32_t* keep,
+                   int32_t* count, void* stream);
+/* F.interpolate(hm, (Ho, Wo), mode="bilinear", align_corners=True) followed by get_max_preds_hrnet (lib/pose_parsing.py:16-55),
+ * fused: the upsampled maps are never written.  hm fp32 [BJ, H, W]; idx int32 [BJ] (flat index into Ho x Wo, may be NULL),
+ * maxval [BJ], preds [BJ, 2] = (idx % Wo, idx / Wo) * (maxval > 0).  Torch's sample rule (scale = float(H-1)/(Ho-1), W first
+ * within a row, then the rows) and stl_heatmap_argmax's order (NaN first, then larger, ties to the smaller index). */
+int stl_heatmap_resize_argmax(const float* hm, int BJ, int H, int W, int Ho, int Wo, int32_t* idx, float* maxval, float* preds,
+                              void* stream);
+
 const char* stl_last_error(void);
 int stl_version(void);
 /* Hash (16 hex digits) of the kernel and header sources this library was compiled from (stlpose_amd/build.py). */

@@ -10,3 +10,7 @@ from .stylise import GatysStylizer  # noqa: F401,E402
 from .pose_database import (PoseIndex, process_pose_vector, process_pose_vectors, get_neighbors_idxs,  # noqa: F401,E402
                             get_penalization_metric, fit_knn_structure, load_knn)
 from .retrieval import score_retrievals, retrieval_experiment, process_retrieval_results  # noqa: F401,E402
+from .pose_parsing import create_pose_entries, create_pose_from_outputs  # noqa: F401,E402
+from .bounding_box import (bbox_filtering, bbox_nms, get_detections, reshape_detection,  # noqa: F401,E402
+                           bbox_to_image_keypoints)
+from .topdown import TransformDetection, PoseExtractor, extract_retrieval_db  # noqa: F401,E402

@@ -25,6 +25,8 @@ POSE_DIM = {"all_kpts": 34, "full_body": 26, "upper_body": 18}
 POSE_METHOD = {"euclidean": 0, "cosine": 1, "manhattan": 2, "confidence": 3, "oks": 4, "l2sq": 5, "cos_normalised": 6}
 POSE_PEN = {"zero_coord": 0, "none": 1, "mean": 2, "max": 3}
 POSE_TOPK_MAX, POSE_RANK_MAX, POSE_RANK_LABELS_MAX, POSE_NSCORES = 1024, 16384, 4, 10
+# top-down extraction (STL_BOX_MAX, STL_RESIZE_SRC_MAX, STL_RESIZE_DST_MAX)
+BOX_MAX, RESIZE_SRC_MAX, RESIZE_DST_MAX = 4096, 16384, 2048
 
 MIXED = dt2(BF16, F16)   # the mixed 16-bit mode: forward tensors f16, gradients bf16
 NSHARD = 2
@@ -175,6 +177,8 @@ SIGNATURES = {
     "stl_pose_topk_workspace": [i32, i32, i32, i32],
     "stl_pose_topk": [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, i64, vp],
     "stl_pose_rank": [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, i32, i32, vp, vp],
+    "stl_box_select": [vp, vp, vp, vp, i32, i64, i32, i64, i32, f32, C.c_double, vp, vp, vp],
+    "stl_heatmap_resize_argmax": [vp, i32, i32, i32, i32, i32, vp, vp, vp, vp],
     "stl_version": [],
 }
 

@@ -332,6 +332,37 @@ __device__ __forceinline__ double wave_sum_d(double v) {
     return v;
 }
 
+// ---------------------------------------------------------------- heatmap argmax (elementwise.hip decode, topdown.hip)
+__device__ __forceinline__ bool better(float v, int i, float bv, int bi) {
+    // np.argmax order: NaN beats everything, then larger value, ties -> smaller index
+    const bool vn = v != v, bn = bv != bv;
+    if (vn != bn) return vn;
+    if (vn) return i < bi;
+    return v > bv || (v == bv && i < bi);
+}
+// Fold one candidate into a thread's running (bv, bi); bi == 0x7fffffff: none yet.
+__device__ __forceinline__ void argmax_take(float v, int i, float& bv, int& bi) {
+    if (bi == 0x7fffffff || better(v, i, bv, bi)) bv = v, bi = i;
+}
+// Block-wide reduction of the threads' (bv, bi); every thread gets the result.  sv / si: one slot per wave of LDS.
+__device__ __forceinline__ void block_argmax_reduce(float& bv, int& bi, float* sv, int* si) {
+    for (int o = 32; o > 0; o >>= 1) {
+        const float ov = __shfl_xor(bv, o);
+        const int oi = __shfl_xor(bi, o);
+        if (oi != 0x7fffffff && (bi == 0x7fffffff || better(ov, oi, bv, bi))) bv = ov, bi = oi;
+    }
+    if ((threadIdx.x & 63) == 0) sv[threadIdx.x >> 6] = bv, si[threadIdx.x >> 6] = bi;
+    __syncthreads();
+    bv = sv[0], bi = si[0];
+    for (int w = 1; w < (int)(blockDim.x >> 6); ++w)
+        if (si[w] != 0x7fffffff && (bi == 0x7fffffff || better(sv[w], si[w], bv, bi))) bv = sv[w], bi = si[w];
+}
+__device__ __forceinline__ void block_argmax(const float* row, int n, float& bv, int& bi, float* sv, int* si) {
+    bv = -INFINITY, bi = 0x7fffffff;
+    for (int i = threadIdx.x; i < n; i += blockDim.x) argmax_take(row[i], i, bv, bi);
+    block_argmax_reduce(bv, bi, sv, si);
+}
+
 static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 
 // ---------------------------------------------------------------- launches

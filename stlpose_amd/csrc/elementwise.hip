@@ -618,32 +618,7 @@ __global__ __launch_bounds__(256) void sum_partials_kernel(const double* partial
     }
 }
 
-// ---------------------------------------------------------------- decode
-__device__ __forceinline__ bool better(float v, int i, float bv, int bi) {
-    // np.argmax order: NaN beats everything, then larger value, ties -> smaller index
-    const bool vn = v != v, bn = bv != bv;
-    if (vn != bn) return vn;
-    if (vn) return i < bi;
-    return v > bv || (v == bv && i < bi);
-}
-__device__ __forceinline__ void block_argmax(const float* row, int n, float& bv, int& bi, float* sv, int* si) {
-    bv = -INFINITY, bi = 0x7fffffff;
-    for (int i = threadIdx.x; i < n; i += blockDim.x) {
-        const float v = row[i];
-        if (bi == 0x7fffffff || better(v, i, bv, bi)) bv = v, bi = i;
-    }
-    for (int o = 32; o > 0; o >>= 1) {
-        const float ov = __shfl_xor(bv, o);
-        const int oi = __shfl_xor(bi, o);
-        if (oi != 0x7fffffff && (bi == 0x7fffffff || better(ov, oi, bv, bi))) bv = ov, bi = oi;
-    }
-    if ((threadIdx.x & 63) == 0) sv[threadIdx.x >> 6] = bv, si[threadIdx.x >> 6] = bi;
-    __syncthreads();
-    bv = sv[0], bi = si[0];
-    for (int w = 1; w < (int)(blockDim.x >> 6); ++w)
-        if (si[w] != 0x7fffffff && (bi == 0x7fffffff || better(sv[w], si[w], bv, bi))) bv = sv[w], bi = si[w];
-}
-
+// ---------------------------------------------------------------- decode (better / block_argmax: common.cuh)
 __global__ __launch_bounds__(256) void argmax_kernel(const float* hm, int32_t* idx, float* maxval, float* preds, int H, int W) {
     __shared__ float sv[4];
     __shared__ int si[4];

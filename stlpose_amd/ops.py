@@ -12,7 +12,7 @@ autograd formula (``flip_merge_backward``, the kernel's adjoint).
 from __future__ import annotations
 
 import weakref
-from typing import Tuple
+from typing import Optional, Tuple
 
 import torch
 
@@ -305,5 +305,68 @@ def _pose_rank_fake(q, c, db, m, p, k_out, labels, qlabels, k_eff):
 _define("pose_rank(Tensor query, Tensor? conf, Tensor database, str method, str penalization, int k_out, Tensor? labels, "
         "Tensor? qlabels, int k_eff) -> (Tensor, Tensor, Tensor)", _pose_rank, _pose_rank_fake)
 
+# ------------------------------------------------------------------ top-down extraction (lib/bounding_box.py, lib/pose_parsing.py)
+# Every shape, dtype, device and cap the kernels rely on is checked here, before anything is launched.
+def _box_select(boxes, scores, labels, offsets, label: int, score_thr: Optional[float], iou_thr: float) -> Tuple[torch.Tensor, torch.Tensor]:
+    if boxes.dim() != 2 or boxes.shape[1] != 4 or boxes.dtype != torch.float32:
+        raise ValueError(f"stlpose box_select: boxes must be float32 [N, 4], got {boxes.dtype} {tuple(boxes.shape)}")
+    n = boxes.shape[0]
+    if scores.dim() != 1 or scores.shape[0] != n or scores.dtype != torch.float32:
+        raise ValueError(f"stlpose box_select: scores must be float32 [N={n}], got {scores.dtype} {tuple(scores.shape)}")
+    if labels is not None and (labels.dim() != 1 or labels.shape[0] != n or labels.dtype != torch.int64):
+        raise ValueError(f"stlpose box_select: labels must be int64 [N={n}], got {labels.dtype} {tuple(labels.shape)}")
+    if offsets.dim() != 1 or offsets.shape[0] < 1 or offsets.dtype != torch.int64:
+        raise ValueError(f"stlpose box_select: offsets must be int64 [I + 1], got {offsets.dtype} {tuple(offsets.shape)}")
+    off = offsets.cpu()
+    per = off[1:] - off[:-1]
+    if int(off[0]) != 0 or int(off[-1]) != n or bool((per < 0).any()):
+        raise ValueError(f"stlpose box_select: offsets must rise from 0 to N = {n}")
+    max_n = int(per.max()) if per.numel() else 0
+    if max_n > capi.BOX_MAX:
+        raise ValueError(f"stlpose box_select: an image has {max_n} boxes; the cap is {capi.BOX_MAX} (STL_BOX_MAX) per image")
+    if not boxes.is_cuda:
+        raise RuntimeError("stlpose box_select: boxes must be on the GPU")
+    _same_device((("scores", scores), ("labels", labels)), boxes.device)
+    ni = per.numel()
+    keep = torch.empty(n, dtype=torch.int32, device=boxes.device)
+    count = torch.empty(ni, dtype=torch.int32, device=boxes.device)
+    b, s = boxes.contiguous(), scores.contiguous()
+    lab = labels.contiguous() if labels is not None else None
+    o = off.to(boxes.device)
+    capi.call("stl_box_select", b.data_ptr(), s.data_ptr(), _ptr(lab), o.data_ptr(), ni, n, max_n, int(label),
+              int(score_thr is not None), float(score_thr) if score_thr is not None else 0.0, float(iou_thr), keep.data_ptr(),
+              count.data_ptr(), _st())
+    return keep, count
+
+
+_define("box_select(Tensor boxes, Tensor scores, Tensor? labels, Tensor offsets, int label, float? score_thr, float iou_thr) "
+        "-> (Tensor, Tensor)", _box_select,
+        lambda b, s, l, o, label, st, it: (b.new_empty(b.shape[0], dtype=torch.int32), b.new_empty(o.shape[0] - 1, dtype=torch.int32)))
+
+
+def _resize_argmax(heatmaps: torch.Tensor, ho: int, wo: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    if heatmaps.dim() != 4 or heatmaps.dtype != torch.float32:
+        raise ValueError(f"stlpose heatmap_resize_argmax: heatmaps must be float32 [B, J, H, W], got {heatmaps.dtype} "
+                         f"{tuple(heatmaps.shape)}")
+    b, j, h, w = heatmaps.shape
+    if h * w > capi.RESIZE_SRC_MAX or h < 1 or w < 1:
+        raise ValueError(f"stlpose heatmap_resize_argmax: a {h} x {w} map; the cap is H * W <= {capi.RESIZE_SRC_MAX}")
+    if not (1 <= ho <= capi.RESIZE_DST_MAX and 1 <= wo <= capi.RESIZE_DST_MAX):
+        raise ValueError(f"stlpose heatmap_resize_argmax: output {ho} x {wo}; each side must be in 1 .. {capi.RESIZE_DST_MAX}")
+    if not heatmaps.is_cuda:
+        raise RuntimeError("stlpose heatmap_resize_argmax: heatmaps must be on the GPU")
+    hm = heatmaps.contiguous()
+    idx = torch.empty(b, j, dtype=torch.int32, device=hm.device)
+    mx = torch.empty(b, j, dtype=torch.float32, device=hm.device)
+    preds = torch.empty(b, j, 2, dtype=torch.float32, device=hm.device)
+    capi.call("stl_heatmap_resize_argmax", hm.data_ptr(), b * j, h, w, int(ho), int(wo), idx.data_ptr(), mx.data_ptr(), preds.data_ptr(),
+              _st())
+    return idx, mx, preds
+
+
+_define("heatmap_resize_argmax(Tensor heatmaps, int ho, int wo) -> (Tensor, Tensor, Tensor)", _resize_argmax,
+        lambda hm, ho, wo: (hm.new_empty(hm.shape[:2], dtype=torch.int32), hm.new_empty(hm.shape[:2]), hm.new_empty(*hm.shape[:2], 2)))
+
 OPS = ["person_mse", "heatmap_argmax", "final_preds", "flip_merge", "flip_merge_backward", "gaussian_targets", "affine_crop",
-       "hrnet_forward", "hrnet_backward", "hrnet_backward_input", "pose_vectors", "pose_distances", "pose_topk", "pose_rank"]
+       "hrnet_forward", "hrnet_backward", "hrnet_backward_input", "pose_vectors", "pose_distances", "pose_topk", "pose_rank",
+       "box_select", "heatmap_resize_argmax"]

@@ -72,3 +72,38 @@ def accuracy(output, target, hm_type="gaussian", thr=0.5):
     if cnt:
         acc[0] = avg
     return acc, avg, cnt, pred
+
+
+def create_pose_entries(keypoints, max_vals=None, thr=0.1):
+    """reference lib/pose_parsing.py:107-133, vectorised.  keypoints [n, 17, 2] -> (pose_entries: n arrays of 19 = keypoint row
+    ids 17 * person + joint where x != -1, then the count, then -1; all_keypoints [n * 17, 4] rows (x, y, 1, vis): a row holding
+    a -1 becomes all -1, vis = 0 where max_vals < thr).  The dtype is the reference's: float64 for float input, int64 for int."""
+    if len(keypoints) == 0:
+        return [], []
+    kp = np.asarray(keypoints)
+    n, j = kp.shape[:2]
+    flat = kp.reshape(n * j, -1)
+    all_kp = np.ones((n * j, flat.shape[1] + 2), np.result_type(kp.dtype, np.int64))
+    all_kp[:, :flat.shape[1]] = flat
+    all_kp[(all_kp == -1).any(1)] = -1
+    if max_vals is not None:
+        low = np.argwhere(np.asarray(max_vals)[:, :, 0] < thr)
+        all_kp[low[:, 0] * 17 + low[:, 1], -1] = 0
+    valid = kp[:, :, 0] != -1
+    entries = -np.ones((n, 19))
+    entries[:, :j] = np.where(valid, 17 * np.arange(n)[:, None] + np.arange(j), -1)
+    entries[:, -2] = (entries[:, :-2] != -1).sum(1)
+    return list(entries), all_kp
+
+
+def create_pose_from_outputs(dets, keypoint_thr=0.1):
+    """reference lib/pose_parsing.py:136-153: heat maps [B, 17, h, w] -> (pose_entries, all_keypoints [B * 17, 4] as (y, x, 1,
+    vis)) at 256 x 192.  The upsample and argmax are one fused kernel (stlpose::heatmap_resize_argmax): the 256 x 192 maps are
+    never written, only 17 x 3 numbers per person reach the host.  An empty batch gives ([], an empty [0, 4] array); the
+    reference raises on it."""
+    hm = dets if torch.is_tensor(dets) and dets.is_cuda else _dev(dets)
+    if hm.shape[0] == 0:
+        return [], np.zeros((0, 4))
+    _, mx, preds = torch.ops.stlpose.heatmap_resize_argmax(hm.contiguous().float(), 256, 192)
+    entries, all_kp = create_pose_entries(preds.cpu().numpy(), mx.cpu().numpy()[..., None], thr=keypoint_thr)
+    return entries, all_kp[:, [1, 0, 2, 3]]
