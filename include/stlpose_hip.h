@@ -429,6 +429,83 @@ int stl_box_select(const float* boxes, const float* scores, const int64_t* label
 int stl_heatmap_resize_argmax(const float* hm, int BJ, int H, int W, int Ho, int Wo, int32_t* idx, float* maxval, float* preds,
                               void* stream);
 
+/* ---- EfficientDet person detector (stlpose_amd/csrc/detector.hip): src/models/EfficientDet.py with
+ * models/efficientdet_utils/{model,utils}.py and models/efficientnet/{model,utils,utils_extra}.py, inference only, fp32, NHWC activations. */
+#define STL_DET_NMS_MAX 65536      /* candidates per image of stl_det_nms (all 49104 anchors of a 512 canvas fit) */
+
+/* One source image of stl_det_preprocess.  kind 0: uint8 HWC RGB (divided by 255), 1: float CHW in [0, 1]; new_h / new_w from
+ * aspectaware_resize_padding (efficientdet_utils/utils.py:209-239, computed on the host); scale_* = old / new (cv2's 1 / inv_scale). */
+typedef struct {
+    const void* src;
+    int32_t kind, old_h, old_w, new_h, new_w, pad_;
+    double scale_y, scale_x;
+} StlDetImage;
+
+/* preprocess (efficientdet_utils/utils.py:190-207): transforms.Normalize(mean (0.406, 0.456, 0.485), std (0.225, 0.224, 0.229)),
+ * cv2.resize INTER_LINEAR to new_h x new_w (half-pixel centres, clamped source, no antialias; a copy at the identity size), zero
+ * S x S canvas with the image at the top left.  imgs: B records in device memory; out fp32 [B, S, S, 3]. */
+int stl_det_preprocess(const StlDetImage* imgs, int B, int S, float* out, void* stream);
+/* _conv_stem + _bn0 + swish (efficientnet/model.py:151-153, efficientdet_utils/model.py:405-407): 3 -> Co 3x3 s2, TF same padding
+ * (utils_extra.py:37-50), BN folded into w [3][3][3][Co] and bias [Co].  x [B, H, W, 3] -> out [B, ceil(H/2), ceil(W/2), Co]. */
+int stl_det_stem(const float* x, const float* w, const float* bias, float* out, int B, int H, int W, int Co, void* stream);
+/* Depthwise k x k (k 3 or 5) stride s (1 or 2) conv with TF same padding (MBConvBlock._depthwise_conv + _bn1 + swish,
+ * efficientnet/model.py:80-82; SeparableConvBlock.depthwise_conv, efficientdet_utils/model.py:40).  w [k][k][C] (BN scale folded),
+ * bias [C] or NULL, act 1: swish.  x [B, H, W, C] -> out [B, ceil(H/s), ceil(W/s), C]. */
+int stl_det_dwconv(const float* x, const float* w, const float* bias, float* out, int B, int H, int W, int C, int k, int s, int act,
+                   void* stream);
+/* Squeeze-excitation (efficientnet/model.py:84-89): scale [B, C] = sigmoid(w2 swish(w1 mean_hw(x) + b1) + b2), w1 [Cs][C],
+ * w2 [C][Cs].  partial: stl_det_se_workspace(B) * C floats; the per-channel sums are taken in a fixed order. */
+int stl_det_se(const float* x, int B, int HW, int C, int Cs, const float* w1, const float* b1, const float* w2, const float* b2,
+               float* partial, float* scale, void* stream);
+int stl_det_se_workspace(int B);
+
+/* 1x1 conv as a GEMM on v_mfma_f32_16x16x4_f32: out[img(m) * out_img_stride + pix(m) * out_row_stride + out_off + n] =
+ * act(sum_k x[m, k] * in_scale[img(m), k] * w[k, n] + bias[n]) + residual[m, n], m < M = B * HW.  x [M, Ci] (any Ci), w packed
+ * [Kp][Np] zero-padded (Kp % 16 == 0, Np % 64 == 0), bias [>= Co] or NULL, in_scale [B, Ci] or NULL (the SE scale applied on
+ * load), residual [M, Co] or NULL, act 0 none / 1 swish / 2 sigmoid (after the bias, before the residual). */
+typedef struct {
+    const float* x;
+    const float* w;
+    const float* bias;
+    const float* in_scale;
+    const float* residual;
+    float* out;
+    int64_t M, out_img_stride, out_row_stride, out_off;
+    int32_t HW, Ci, Co, Kp, Np, act;
+} StlDetPointwise;
+int stl_det_pointwise(const StlDetPointwise* p, void* stream);
+
+/* One BiFPN input: x [B, H, W, C] read as mode 0 the same size, 1 nearest 2x upsample (nn.Upsample(scale_factor=2)), 2 the 3x3 s2
+ * max-pool of MaxPool2dStaticSamePadding (TF same padding, padded with zeros by F.pad before the max, utils_extra.py:80-86). */
+typedef struct {
+    const float* x;
+    int32_t mode, H, W, pad_;
+} StlDetTerm;
+/* BiFPN node input (efficientdet_utils/model.py:163-233): out [B, H, W, C] = swish(sum_i w_i * read(t_i)), w = relu(wparam) /
+ * (sum relu(wparam) + 1e-4) normalised on the device from the nterms raw parameters, summed left to right.  wparam NULL (one
+ * term): out = read(t_0), the pooled maps of p5_to_p6 / p6_to_p7. */
+typedef struct {
+    int32_t B, H, W, C, nterms, pad_;
+    StlDetTerm t[3];
+    const float* wparam;
+    float* out;
+} StlDetFuse;
+int stl_det_fuse(const StlDetFuse* f, void* stream);
+
+/* postprocess up to the NMS (efficientdet_utils/utils.py:14-56, 150-168): per image, score = max over the nc classes (first
+ * maximum), kept when score > thr; BBoxTransform (exp) on anchors fp32 [A][4] (y1, x1, y2, x2) and reg [B, A, 4] (dy, dx, dh, dw);
+ * ClipBoxes to [0, xmax] x [0, ymax].  The survivors in anchor order: boxes [B, A, 4] (x1, y1, x2, y2), scores [B, A], classes
+ * [B, A], index [B, A] (the anchor), the first count[b] rows of image b.  One workgroup per image. */
+int stl_det_decode(const float* reg, const float* cls, const float* anchors, int B, int A, int nc, float thr, float xmax, float ymax,
+                   float* boxes, float* scores, int32_t* classes, int32_t* index, int32_t* count, void* stream);
+/* torchvision.ops.batched_nms as torchvision 0.4 runs it (postprocess, efficientdet_utils/utils.py:169): boxes [n, 4] offset by
+ * class * (max coordinate + 1), then nms in the given order (order int32 [n]: descending score, ties to the lower index) -- a
+ * 64 x 64 bitmask IoU matrix and a one-wave greedy sweep, so any n <= STL_DET_NMS_MAX.  keep int32 [n]: the first count kept
+ * candidate indices in score order.  work: stl_det_nms_workspace(n) bytes. */
+int stl_det_nms(const float* boxes, const int32_t* classes, const int32_t* order, int n, double iou_thr, void* work, int32_t* keep,
+                int32_t* count, void* stream);
+int64_t stl_det_nms_workspace(int n);
+
 const char* stl_last_error(void);
 int stl_version(void);
 /* Hash (16 hex digits) of the kernel and header sources this library was compiled from (stlpose_amd/build.py). */

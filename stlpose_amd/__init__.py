@@ -14,3 +14,5 @@ from .pose_parsing import create_pose_entries, create_pose_from_outputs  # noqa:
 from .bounding_box import (bbox_filtering, bbox_nms, get_detections, reshape_detection,  # noqa: F401,E402
                            bbox_to_image_keypoints)
 from .topdown import TransformDetection, PoseExtractor, extract_retrieval_db  # noqa: F401,E402
+from .efficientdet import EfficientDetBackbone, EfficientDet, setup_detector  # noqa: F401,E402
+from .topdown import detect_poses  # noqa: F401,E402

@@ -27,6 +27,8 @@ POSE_PEN = {"zero_coord": 0, "none": 1, "mean": 2, "max": 3}
 POSE_TOPK_MAX, POSE_RANK_MAX, POSE_RANK_LABELS_MAX, POSE_NSCORES = 1024, 16384, 4, 10
 # top-down extraction (STL_BOX_MAX, STL_RESIZE_SRC_MAX, STL_RESIZE_DST_MAX)
 BOX_MAX, RESIZE_SRC_MAX, RESIZE_DST_MAX = 4096, 16384, 2048
+# person detector (STL_DET_NMS_MAX)
+DET_NMS_MAX = 65536
 
 MIXED = dt2(BF16, F16)   # the mixed 16-bit mode: forward tensors f16, gradients bf16
 NSHARD = 2
@@ -111,6 +113,26 @@ class HeadBwd(C.Structure):
                 ("x", vp), ("w", vp), ("dout", vp), ("dx", vp), ("partial", vp)]
 
 
+class DetImage(C.Structure):
+    _fields_ = [("src", vp), ("kind", i32), ("old_h", i32), ("old_w", i32), ("new_h", i32), ("new_w", i32), ("pad_", i32),
+                ("scale_y", C.c_double), ("scale_x", C.c_double)]
+
+
+class DetPointwise(C.Structure):
+    _fields_ = [("x", vp), ("w", vp), ("bias", vp), ("in_scale", vp), ("residual", vp), ("out", vp), ("M", i64),
+                ("out_img_stride", i64), ("out_row_stride", i64), ("out_off", i64), ("HW", i32), ("Ci", i32), ("Co", i32),
+                ("Kp", i32), ("Np", i32), ("act", i32)]
+
+
+class DetTerm(C.Structure):
+    _fields_ = [("x", vp), ("mode", i32), ("H", i32), ("W", i32), ("pad_", i32)]
+
+
+class DetFuse(C.Structure):
+    _fields_ = [("B", i32), ("H", i32), ("W", i32), ("C", i32), ("nterms", i32), ("pad_", i32), ("t", DetTerm * 3), ("wparam", vp),
+                ("out", vp)]
+
+
 class Op(C.Structure):
     _fields_ = [("kind", i32), ("stream", i32), ("desc", vp), ("nwait", i32), ("wait", i32 * 8), ("record", i32)]
 
@@ -179,6 +201,16 @@ SIGNATURES = {
     "stl_pose_rank": [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, i32, i32, vp, vp],
     "stl_box_select": [vp, vp, vp, vp, i32, i64, i32, i64, i32, f32, C.c_double, vp, vp, vp],
     "stl_heatmap_resize_argmax": [vp, i32, i32, i32, i32, i32, vp, vp, vp, vp],
+    "stl_det_preprocess": [vp, i32, i32, vp, vp],
+    "stl_det_stem": [vp, vp, vp, vp, i32, i32, i32, i32, vp],
+    "stl_det_dwconv": [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp],
+    "stl_det_se": [vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp],
+    "stl_det_se_workspace": [i32],
+    "stl_det_pointwise": [C.POINTER(DetPointwise), vp],
+    "stl_det_fuse": [C.POINTER(DetFuse), vp],
+    "stl_det_decode": [vp, vp, vp, i32, i32, i32, f32, f32, f32, vp, vp, vp, vp, vp, vp],
+    "stl_det_nms": [vp, vp, vp, i32, C.c_double, vp, vp, vp, vp],
+    "stl_det_nms_workspace": [i32],
     "stl_version": [],
 }
 
@@ -203,7 +235,7 @@ def lib() -> C.CDLL:
         for name, args in SIGNATURES.items():
             fn = getattr(l, name)  # AttributeError if the ABI and this table disagree
             fn.argtypes = args
-            fn.restype = C.c_int
+            fn.restype = C.c_int64 if name == "stl_det_nms_workspace" else C.c_int
         for name, args in DEBUG_SIGNATURES.items():
             if hasattr(l, name):
                 getattr(l, name).argtypes, getattr(l, name).restype = args, C.c_int

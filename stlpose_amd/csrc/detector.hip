@@ -1,0 +1,567 @@
+// EfficientDet person detector on gfx950, fp32, NHWC (src/models/EfficientDet.py and models/efficientdet_utils/*,
+// models/efficientnet/{model,utils,utils_extra}.py): preprocess, the MBConv backbone, BiFPN and the shared heads, anchor decode and class-aware NMS.
+//
+//   stl_det_preprocess  normalise + aspect-aware bilinear resize + zero canvas (efficientdet_utils/utils.py:190-239)
+//   stl_det_stem        3 -> C 3x3/s2 same-padded conv, folded BN, swish (efficientnet/model.py:151-153)
+//   stl_det_dwconv      depthwise kxk/s same-padded conv, folded BN bias, optional swish (MBConvBlock, SeparableConvBlock)
+//   stl_det_se          squeeze-excitation scale[B, C] (efficientnet/model.py:84-89)
+//   stl_det_pointwise   1x1 conv as a GEMM on v_mfma_f32_16x16x4_f32: SE scale on load, bias, swish / sigmoid, residual,
+//                       strided output (the head headers write straight into the concatenated [B, A, k] outputs)
+//   stl_det_fuse        BiFPN node swish(sum w_i * in_i) with same / nearest-2x / zero-padded 3x3 s2 max-pool inputs, the
+//                       fast-attention weights normalised on the device (efficientdet_utils/model.py:163-233)
+//   stl_det_decode      per-anchor class max, strict threshold, BBoxTransform, ClipBoxes, compaction in anchor order
+//   stl_det_nms         torchvision.ops.batched_nms (0.4: class offsets, then nms) over any number of candidates
+//
+// Every reduction runs in a fixed order (no float atomics): two runs give bitwise equal results.
+#include "common.cuh"
+
+namespace {
+
+__device__ __forceinline__ float swishf(float x) { return x * (1.f / (1.f + __expf(-x))); }
+__device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + expf(-x)); }
+
+// TensorFlow "same" padding before the first row / column: extra = (ceil(n / s) - 1) * s - n + k, before = extra / 2
+__host__ __device__ __forceinline__ int same_pad_before(int n, int k, int s) {
+    const int extra = ((n + s - 1) / s - 1) * s - n + k;
+    return (extra > 0 ? extra : 0) / 2;
+}
+
+// ------------------------------------------------------------------------------------------------ preprocess
+// cv2.resize(INTER_LINEAR) on float32: src = (dst + 0.5) * scale - 0.5 in double, rounded to float, floor; a negative
+// source index takes the first pixel with weight 1, one at or past the last takes the last pixel with weight 1.
+struct LinTap {
+    int i0, i1;
+    float w0, w1;
+};
+__device__ __forceinline__ LinTap lin_tap(int d, double scale, int n) {
+    const float f = (float)(((double)d + 0.5) * scale - 0.5);
+    int i = (int)floorf(f);
+    float a = f - (float)i;
+    if (i < 0) i = 0, a = 0.f;
+    if (i >= n - 1) i = n - 1, a = 0.f;
+    LinTap t;
+    t.i0 = i;
+    t.i1 = min(i + 1, n - 1);
+    t.w0 = 1.f - a;
+    t.w1 = a;
+    return t;
+}
+
+__global__ __launch_bounds__(256) void preprocess_kernel(const StlDetImage* __restrict__ imgs, int S, float* __restrict__ out) {
+    const StlDetImage m = imgs[blockIdx.y];
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    if (p >= S * S) return;
+    const int y = p / S, x = p - y * S;
+    float* o = out + ((size_t)blockIdx.y * S * S + p) * 3;
+    const float mean[3] = {0.406f, 0.456f, 0.485f}, istd[3] = {0.225f, 0.224f, 0.229f};
+    if (y >= m.new_h || x >= m.new_w) {
+        o[0] = o[1] = o[2] = 0.f;
+        return;
+    }
+    const bool same = m.new_h == m.old_h && m.new_w == m.old_w;
+    LinTap ty, tx;
+    if (same) {
+        ty = LinTap{y, y, 1.f, 0.f};
+        tx = LinTap{x, x, 1.f, 0.f};
+    } else {
+        ty = lin_tap(y, m.scale_y, m.old_h);
+        tx = lin_tap(x, m.scale_x, m.old_w);
+    }
+    const int64_t plane = (int64_t)m.old_h * m.old_w;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        float v[4];
+        const int ys[2] = {ty.i0, ty.i1}, xs[2] = {tx.i0, tx.i1};
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int64_t e = (int64_t)ys[q >> 1] * m.old_w + xs[q & 1];
+            const float raw = m.kind == 0 ? (float)reinterpret_cast<const uint8_t*>(m.src)[e * 3 + c] / 255.f
+                                          : reinterpret_cast<const float*>(m.src)[c * plane + e];
+            v[q] = (raw - mean[c]) / istd[c];   // transforms.Normalize: (x - mean) / std, then the resize
+        }
+        const float top = v[0] * tx.w0 + v[1] * tx.w1, bot = v[2] * tx.w0 + v[3] * tx.w1;
+        o[c] = same ? v[0] : top * ty.w0 + bot * ty.w1;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ stem and depthwise
+// one thread per output (pixel, channel); w [3][3][3][Co], out NHWC, always BN-folded bias + swish
+__global__ __launch_bounds__(256) void stem_kernel(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ bias,
+                                                   float* __restrict__ out, int B, int H, int W, int Ho, int Wo, int Co) {
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= (int64_t)B * Ho * Wo * Co) return;
+    const int co = (int)(e % Co);
+    const int64_t pix = e / Co;
+    const int ox = (int)(pix % Wo), oy = (int)((pix / Wo) % Ho), b = (int)(pix / ((int64_t)Wo * Ho));
+    const int py = same_pad_before(H, 3, 2), px = same_pad_before(W, 3, 2);
+    float acc = 0.f;
+    for (int ky = 0; ky < 3; ++ky) {
+        const int iy = oy * 2 - py + ky;
+        if (iy < 0 || iy >= H) continue;
+        for (int kx = 0; kx < 3; ++kx) {
+            const int ix = ox * 2 - px + kx;
+            if (ix < 0 || ix >= W) continue;
+            const float* xp = x + (((int64_t)b * H + iy) * W + ix) * 3;
+            const float* wp = w + ((ky * 3 + kx) * 3) * Co + co;
+            acc += xp[0] * wp[0] + xp[1] * wp[Co] + xp[2] * wp[2 * Co];
+        }
+    }
+    out[e] = swishf(acc + bias[co]);
+}
+
+// one thread per output (pixel, channel); w [k][k][C]; bias null: none; act 1: swish
+template <int K>
+__global__ __launch_bounds__(256) void dwconv_kernel(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ bias,
+                                                     float* __restrict__ out, int B, int H, int W, int C, int s, int Ho, int Wo, int act) {
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= (int64_t)B * Ho * Wo * C) return;
+    const int c = (int)(e % C);
+    const int64_t pix = e / C;
+    const int ox = (int)(pix % Wo), oy = (int)((pix / Wo) % Ho), b = (int)(pix / ((int64_t)Wo * Ho));
+    const int py = same_pad_before(H, K, s), px = same_pad_before(W, K, s);
+    const int y0 = oy * s - py, x0 = ox * s - px;
+    float acc = 0.f;
+#pragma unroll
+    for (int ky = 0; ky < K; ++ky) {
+        const int iy = y0 + ky;
+        if (iy < 0 || iy >= H) continue;
+#pragma unroll
+        for (int kx = 0; kx < K; ++kx) {
+            const int ix = x0 + kx;
+            if (ix < 0 || ix >= W) continue;
+            acc += x[(((int64_t)b * H + iy) * W + ix) * C + c] * w[(ky * K + kx) * C + c];
+        }
+    }
+    if (bias) acc += bias[c];
+    out[e] = act == 1 ? swishf(acc) : acc;
+}
+
+// ------------------------------------------------------------------------------------------------ squeeze-excitation
+constexpr int kSeSplit = 32;   // pixel ranges per image of the pooling pass
+
+// partial[b][split][c] = sum over the split's pixels, in pixel order
+__global__ __launch_bounds__(256) void se_pool_kernel(const float* __restrict__ x, int HW, int C, float* __restrict__ partial) {
+    const int b = blockIdx.y, sp = blockIdx.x;
+    const int per = (HW + kSeSplit - 1) / kSeSplit;
+    const int p0 = sp * per, p1 = min(HW, p0 + per);
+    for (int c = threadIdx.x; c < C; c += 256) {
+        float acc = 0.f;
+        for (int p = p0; p < p1; ++p) acc += x[((int64_t)b * HW + p) * C + c];
+        partial[((int64_t)b * kSeSplit + sp) * C + c] = acc;
+    }
+}
+
+// one workgroup per image: mean -> reduce (w1 [Cs][C] + b1) -> swish -> expand (w2 [C][Cs] + b2) -> sigmoid
+__global__ __launch_bounds__(256) void se_kernel(const float* __restrict__ partial, int HW, int C, int Cs, const float* __restrict__ w1,
+                                                 const float* __restrict__ b1, const float* __restrict__ w2, const float* __restrict__ b2,
+                                                 float* __restrict__ scale) {
+    extern __shared__ float sm[];   // mean [C] | hidden [Cs]
+    float* mean = sm;
+    float* hid = sm + C;
+    const int b = blockIdx.x;
+    for (int c = threadIdx.x; c < C; c += 256) {
+        float acc = 0.f;
+        for (int sp = 0; sp < kSeSplit; ++sp) acc += partial[((int64_t)b * kSeSplit + sp) * C + c];
+        mean[c] = acc / (float)HW;
+    }
+    __syncthreads();
+    // one wave per hidden unit, lanes stride over C, then a fixed-order wave reduction
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    for (int j = wv; j < Cs; j += 4) {
+        float acc = 0.f;
+        for (int c = lane; c < C; c += 64) acc += w1[(int64_t)j * C + c] * mean[c];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
+        if (lane == 0) hid[j] = swishf(acc + b1[j]);
+    }
+    __syncthreads();
+    for (int c = threadIdx.x; c < C; c += 256) {
+        float acc = b2[c];
+        for (int j = 0; j < Cs; ++j) acc += w2[(int64_t)c * Cs + j] * hid[j];
+        scale[(int64_t)b * C + c] = sigmoidf_(acc);
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ pointwise GEMM
+// out[m, n] = act(sum_k x[m, k] * (scale[img(m), k]) * w[k, n] + bias[n]) (+ residual[m, n]), m over B * HW pixels.
+// Workgroup tile 64 x 64, 4 waves, wave w owns rows 16w .. 16w + 15 and all 64 columns (4 accumulators of 16 x 16);
+// K in steps of 16 through LDS.  w is packed [Kp][Np] with zero padding (Kp % 16 == 0, Np % 64 == 0): activations are read
+// with bounds checks, never padded.
+constexpr int kPwM = 64, kPwN = 64, kPwK = 16;
+
+__global__ __launch_bounds__(256) void pointwise_kernel(const StlDetPointwise p) {
+    __shared__ float sa[kPwK][kPwM + 4];   // [k][m]
+    __shared__ float sb[kPwK][kPwN];       // [k][n]
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int64_t m0 = (int64_t)blockIdx.x * kPwM;
+    const int n0 = blockIdx.y * kPwN;
+    f32x4 acc[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    // A staging: thread -> (row am, 4 consecutive k at ak)
+    const int am = tid >> 2, ak = (tid & 3) * 4;
+    const int64_t arow = m0 + am;
+    const bool arow_ok = arow < p.M;
+    const int aimg = arow_ok ? (int)(arow / p.HW) : 0;
+    const float* xrow = p.x + (arow_ok ? arow : 0) * (int64_t)p.Ci;
+    const float* srow = p.in_scale ? p.in_scale + (int64_t)aimg * p.Ci : nullptr;
+    for (int k0 = 0; k0 < p.Ci; k0 += kPwK) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int k = k0 + ak + q;
+            float v = 0.f;
+            if (arow_ok && k < p.Ci) {
+                v = xrow[k];
+                if (srow) v *= srow[k];
+            }
+            sa[ak + q][am] = v;
+        }
+        {   // B: 16 x 64 floats, one float4 per thread
+            const int bk = tid >> 4, bn = (tid & 15) * 4;
+            const float4 wv4 = *reinterpret_cast<const float4*>(p.w + (int64_t)(k0 + bk) * p.Np + n0 + bn);
+            sb[bk][bn] = wv4.x, sb[bk][bn + 1] = wv4.y, sb[bk][bn + 2] = wv4.z, sb[bk][bn + 3] = wv4.w;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int ks = 0; ks < kPwK; ks += 4) {
+            // A[i = lane & 15][k = lane >> 4], B[k = lane >> 4][j = lane & 15]
+            const float a = sa[ks + (lane >> 4)][wv * 16 + (lane & 15)];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const float bv = sb[ks + (lane >> 4)][j * 16 + (lane & 15)];
+                acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, bv, acc[j], 0, 0, 0);
+            }
+        }
+        __syncthreads();
+    }
+    // C/D: col = lane & 15, row = (lane >> 4) * 4 + r
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int n = n0 + j * 16 + (lane & 15);
+        if (n >= p.Co) continue;
+        const float bias = p.bias ? p.bias[n] : 0.f;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int64_t m = m0 + wv * 16 + (lane >> 4) * 4 + r;
+            if (m >= p.M) continue;
+            float v = acc[j][r] + bias;
+            if (p.act == 1) v = swishf(v);
+            else if (p.act == 2) v = sigmoidf_(v);
+            if (p.residual) v += p.residual[m * p.Co + n];
+            const int64_t img = m / p.HW, pix = m - img * p.HW;
+            p.out[img * p.out_img_stride + pix * p.out_row_stride + p.out_off + n] = v;
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ BiFPN node
+__device__ __forceinline__ float fuse_read(const StlDetTerm& t, int b, int y, int x, int c, int C) {
+    if (t.mode == 0) return t.x[(((int64_t)b * t.H + y) * t.W + x) * C + c];
+    if (t.mode == 1) return t.x[(((int64_t)b * t.H + (y >> 1)) * t.W + (x >> 1)) * C + c];
+    // zero-padded (F.pad) 3x3 s2 max-pool with TF same padding: padded taps read 0
+    const int py = same_pad_before(t.H, 3, 2), px = same_pad_before(t.W, 3, 2);
+    float m = -INFINITY;
+    for (int ky = 0; ky < 3; ++ky) {
+        const int iy = y * 2 - py + ky;
+        for (int kx = 0; kx < 3; ++kx) {
+            const int ix = x * 2 - px + kx;
+            const float v = (iy < 0 || iy >= t.H || ix < 0 || ix >= t.W) ? 0.f : t.x[(((int64_t)b * t.H + iy) * t.W + ix) * C + c];
+            m = v > m ? v : m;
+        }
+    }
+    return m;
+}
+
+__global__ __launch_bounds__(256) void fuse_kernel(const StlDetFuse f) {
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= (int64_t)f.B * f.H * f.W * f.C) return;
+    const int c = (int)(e % f.C);
+    const int64_t pix = e / f.C;
+    const int x = (int)(pix % f.W), y = (int)((pix / f.W) % f.H), b = (int)(pix / ((int64_t)f.W * f.H));
+    if (!f.wparam) {   // a plain pooled map (p5_to_p6, p6_to_p7)
+        f.out[e] = fuse_read(f.t[0], b, y, x, c, f.C);
+        return;
+    }
+    // fast attention: w = relu(p) / (sum relu(p) + 1e-4), sums left to right
+    float w[3], s = 0.f;
+    for (int i = 0; i < f.nterms; ++i) {
+        w[i] = f.wparam[i] > 0.f ? f.wparam[i] : 0.f;
+        s += w[i];
+    }
+    s += 1e-4f;
+    float acc = 0.f;
+    for (int i = 0; i < f.nterms; ++i) acc += (w[i] / s) * fuse_read(f.t[i], b, y, x, c, f.C);
+    f.out[e] = swishf(acc);
+}
+
+// ------------------------------------------------------------------------------------------------ decode
+constexpr int kDecThreads = 1024;
+
+__device__ __forceinline__ int scan_block(int v, int* sw, int& total) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    int x = v;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int y = __shfl_up(x, o);
+        if (lane >= o) x += y;
+    }
+    if (lane == 63) sw[w] = x;
+    __syncthreads();
+    int base = 0, tot = 0;
+    for (int k = 0; k < kDecThreads / 64; ++k) {
+        const int s = sw[k];
+        base += k < w ? s : 0;
+        tot += s;
+    }
+    __syncthreads();
+    total = tot;
+    return base + x - v;
+}
+
+// one workgroup per image; anchors [A][4] (y1, x1, y2, x2), reg [B][A][4] (dy, dx, dh, dw), cls [B][A][nc]
+__global__ __launch_bounds__(kDecThreads) void decode_kernel(const float* __restrict__ reg, const float* __restrict__ cls,
+                                                             const float* __restrict__ anchors, int A, int nc, float thr, float xmax,
+                                                             float ymax, float* boxes, float* scores, int32_t* classes,
+                                                             int32_t* index, int32_t* count) {
+#pragma clang fp contract(off)
+    __shared__ int sw[kDecThreads / 64];
+    const int b = blockIdx.x;
+    int base = 0;
+    for (int a0 = 0; a0 < A; a0 += kDecThreads) {
+        const int a = a0 + threadIdx.x;
+        float best = -INFINITY;
+        int bc = 0;
+        bool pass = false;
+        if (a < A) {
+            const float* cp = cls + ((int64_t)b * A + a) * nc;
+            for (int k = 0; k < nc; ++k) {
+                const float v = cp[k];
+                if (v > best || k == 0) best = v, bc = k;
+            }
+            pass = best > thr;
+        }
+        int tot;
+        const int pos = base + scan_block(pass ? 1 : 0, sw, tot);
+        if (pass) {
+            const float4 an = reinterpret_cast<const float4*>(anchors)[a];
+            const float4 r = reinterpret_cast<const float4*>(reg)[(int64_t)b * A + a];
+            const float yca = (an.x + an.z) / 2.f, xca = (an.y + an.w) / 2.f;
+            const float ha = an.z - an.x, wa = an.w - an.y;
+            const float w = expf(r.w) * wa, h = expf(r.z) * ha;
+            const float yc = r.x * ha + yca, xc = r.y * wa + xca;
+            float x1 = xc - w / 2.f, y1 = yc - h / 2.f, x2 = xc + w / 2.f, y2 = yc + h / 2.f;
+            x1 = x1 < 0.f ? 0.f : x1;
+            y1 = y1 < 0.f ? 0.f : y1;
+            x2 = x2 > xmax ? xmax : x2;
+            y2 = y2 > ymax ? ymax : y2;
+            const int64_t o = (int64_t)b * A + pos;
+            reinterpret_cast<float4*>(boxes)[o] = make_float4(x1, y1, x2, y2);
+            scores[o] = best;
+            classes[o] = bc;
+            index[o] = a;
+        }
+        base += tot;
+    }
+    if (threadIdx.x == 0) count[b] = base;
+}
+
+// ------------------------------------------------------------------------------------------------ NMS
+__device__ __forceinline__ float iou_tv(const float4 a, const float4 b) {
+#pragma clang fp contract(off)
+    const float area_a = (a.z - a.x) * (a.w - a.y);
+    const float area_b = (b.z - b.x) * (b.w - b.y);
+    const float xx1 = a.x < b.x ? b.x : a.x;
+    const float yy1 = a.y < b.y ? b.y : a.y;
+    const float xx2 = b.z < a.z ? b.z : a.z;
+    const float yy2 = b.w < a.w ? b.w : a.w;
+    const float dw = xx2 - xx1, dh = yy2 - yy1;
+    const float w = 0.f < dw ? dw : 0.f;
+    const float h = 0.f < dh ? dh : 0.f;
+    const float inter = w * h;
+    return inter / (area_a + area_b - inter);
+}
+
+// one workgroup: max coordinate over all candidate boxes, then sbox[p] = boxes[order[p]] + class * (max + 1)
+__global__ __launch_bounds__(1024) void nms_prep_kernel(const float* __restrict__ boxes, const int32_t* __restrict__ classes,
+                                                        const int32_t* __restrict__ order, int n, float4* __restrict__ sbox) {
+#pragma clang fp contract(off)
+    __shared__ float sm[16];
+    float m = -INFINITY;
+    for (int e = threadIdx.x; e < n * 4; e += 1024) m = fmaxf(m, boxes[e]);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+    if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = m;
+    __syncthreads();
+    float mx = sm[0];
+    for (int k = 1; k < 16; ++k) mx = fmaxf(mx, sm[k]);
+    const float step = mx + 1.f;
+    for (int p = threadIdx.x; p < n; p += 1024) {
+        const int r = order[p];
+        const float off = (float)classes[r] * step;
+        const float4 bx = reinterpret_cast<const float4*>(boxes)[r];
+        sbox[p] = make_float4(bx.x + off, bx.y + off, bx.z + off, bx.w + off);
+    }
+}
+
+// mask[i][cb] bit t: iou(sbox[i], sbox[64 cb + t]) > thr for 64 cb + t > i.  Grid (column blocks, row blocks), 64 threads.
+__global__ __launch_bounds__(64) void nms_mask_kernel(const float4* __restrict__ sbox, int n, int nblk, float thr,
+                                                      unsigned long long* __restrict__ mask) {
+    const int cb = blockIdx.x, rb = blockIdx.y;
+    if (cb < rb) return;
+    __shared__ float4 cols[64];
+    const int c = cb * 64 + threadIdx.x;
+    if (c < n) cols[threadIdx.x] = sbox[c];
+    __syncthreads();
+    const int i = rb * 64 + threadIdx.x;
+    if (i >= n) return;
+    const float4 bi = sbox[i];
+    const int nc = min(64, n - cb * 64);
+    unsigned long long bits = 0;
+    for (int t = 0; t < nc; ++t)
+        if (cb * 64 + t > i && iou_tv(bi, cols[t]) > thr) bits |= 1ull << t;
+    mask[(int64_t)i * nblk + cb] = bits;
+}
+
+// one wave: the greedy sweep in score order; removed bits in LDS; keep[] gets the kept positions (into the sorted order)
+__global__ __launch_bounds__(64) void nms_sweep_kernel(const unsigned long long* __restrict__ mask, const int32_t* __restrict__ order,
+                                                       int n, int nblk, int32_t* __restrict__ keep, int32_t* __restrict__ count) {
+    extern __shared__ unsigned long long removed[];
+    const int lane = threadIdx.x;
+    for (int k = lane; k < nblk; k += 64) removed[k] = 0ull;
+    __syncthreads();
+    int kept = 0;
+    for (int i = 0; i < n; ++i) {
+        const int blk = i >> 6;
+        const bool dead = (removed[blk] >> (i & 63)) & 1ull;   // uniform
+        __syncthreads();
+        if (dead) continue;
+        if (lane == 0) keep[kept] = order[i];
+        ++kept;
+        const unsigned long long* row = mask + (int64_t)i * nblk;
+        for (int k = blk + lane; k < nblk; k += 64) removed[k] |= row[k];
+        __syncthreads();
+    }
+    if (lane == 0) *count = kept;
+}
+
+}  // namespace
+
+#define ST ((hipStream_t)stream)
+
+extern "C" int stl_det_preprocess(const StlDetImage* imgs, int B, int S, float* out, void* stream) {
+    STL_CHECK(B >= 0 && S >= 1 && S <= 4096, "det_preprocess: %d images, canvas %d", B, S);
+    if (B == 0) return 0;
+    STL_CHECK(imgs && out, "det_preprocess: null pointer");
+    STL_LAUNCH(preprocess_kernel, dim3(ceil_div(S * S, 256), B), dim3(256), 0, ST, imgs, S, out);
+    STL_LAUNCH_CHECK("det_preprocess");
+    return 0;
+}
+
+extern "C" int stl_det_stem(const float* x, const float* w, const float* bias, float* out, int B, int H, int W, int Co, void* stream) {
+    STL_CHECK(B >= 1 && H >= 1 && W >= 1 && Co >= 1, "det_stem: B %d, %d x %d, Co %d", B, H, W, Co);
+    STL_CHECK(x && w && bias && out, "det_stem: null pointer");
+    const int Ho = (H + 1) / 2, Wo = (W + 1) / 2;
+    const int64_t n = (int64_t)B * Ho * Wo * Co;
+    STL_CHECK(n < (1ll << 31) * 256, "det_stem: too large");
+    STL_LAUNCH(stem_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ST, x, w, bias, out, B, H, W, Ho, Wo, Co);
+    STL_LAUNCH_CHECK("det_stem");
+    return 0;
+}
+
+extern "C" int stl_det_dwconv(const float* x, const float* w, const float* bias, float* out, int B, int H, int W, int C, int k, int s,
+                              int act, void* stream) {
+    STL_CHECK(B >= 1 && H >= 1 && W >= 1 && C >= 1, "det_dwconv: B %d, %d x %d, C %d", B, H, W, C);
+    STL_CHECK((k == 3 || k == 5) && (s == 1 || s == 2), "det_dwconv: k %d s %d (k in {3, 5}, s in {1, 2})", k, s);
+    STL_CHECK(x && w && out, "det_dwconv: null pointer");
+    const int Ho = (H + s - 1) / s, Wo = (W + s - 1) / s;
+    const int64_t n = (int64_t)B * Ho * Wo * C;
+    const dim3 grid((unsigned)((n + 255) / 256));
+    if (k == 3) STL_LAUNCH(dwconv_kernel<3>, grid, dim3(256), 0, ST, x, w, bias, out, B, H, W, C, s, Ho, Wo, act);
+    else STL_LAUNCH(dwconv_kernel<5>, grid, dim3(256), 0, ST, x, w, bias, out, B, H, W, C, s, Ho, Wo, act);
+    STL_LAUNCH_CHECK("det_dwconv");
+    return 0;
+}
+
+extern "C" int stl_det_se(const float* x, int B, int HW, int C, int Cs, const float* w1, const float* b1, const float* w2,
+                          const float* b2, float* partial, float* scale, void* stream) {
+    STL_CHECK(B >= 1 && HW >= 1 && C >= 1 && C <= 8192 && Cs >= 1 && Cs <= 1024, "det_se: B %d HW %d C %d Cs %d", B, HW, C, Cs);
+    STL_CHECK(x && w1 && b1 && w2 && b2 && partial && scale, "det_se: null pointer");
+    STL_LAUNCH(se_pool_kernel, dim3(kSeSplit, B), dim3(256), 0, ST, x, HW, C, partial);
+    STL_LAUNCH_CHECK("det_se_pool");
+    STL_LAUNCH(se_kernel, dim3(B), dim3(256), (size_t)(C + Cs) * 4, ST, partial, HW, C, Cs, w1, b1, w2, b2, scale);
+    STL_LAUNCH_CHECK("det_se");
+    return 0;
+}
+
+extern "C" int stl_det_se_workspace(int B) { return B * kSeSplit; }
+
+extern "C" int stl_det_pointwise(const StlDetPointwise* p, void* stream) {
+    STL_CHECK(p && p->x && p->w && p->out, "det_pointwise: null pointer");
+    STL_CHECK(p->M >= 1 && p->HW >= 1 && p->Ci >= 1 && p->Co >= 1, "det_pointwise: M %lld HW %d Ci %d Co %d", (long long)p->M, p->HW,
+              p->Ci, p->Co);
+    STL_CHECK(p->Np % kPwN == 0 && p->Np >= p->Co && p->Kp % kPwK == 0 && p->Kp >= p->Ci, "det_pointwise: packed %d x %d for %d x %d",
+              p->Kp, p->Np, p->Ci, p->Co);
+    STL_CHECK(p->act >= 0 && p->act <= 2, "det_pointwise: act %d", p->act);
+    const int64_t mb = (p->M + kPwM - 1) / kPwM;
+    STL_CHECK(mb < (1ll << 31), "det_pointwise: M too large");
+    STL_LAUNCH(pointwise_kernel, dim3((unsigned)mb, p->Np / kPwN), dim3(256), 0, ST, *p);
+    STL_LAUNCH_CHECK("det_pointwise");
+    return 0;
+}
+
+extern "C" int stl_det_fuse(const StlDetFuse* f, void* stream) {
+    STL_CHECK(f && f->out && f->B >= 1 && f->H >= 1 && f->W >= 1 && f->C >= 1, "det_fuse: bad geometry");
+    STL_CHECK(f->nterms >= 1 && f->nterms <= 3 && (f->wparam || f->nterms == 1), "det_fuse: %d terms", f->nterms);
+    for (int i = 0; i < f->nterms; ++i) {
+        const StlDetTerm& t = f->t[i];
+        STL_CHECK(t.x, "det_fuse: term %d null", i);
+        const bool ok = t.mode == 0 ? (t.H == f->H && t.W == f->W)
+                      : t.mode == 1 ? (2 * t.H == f->H && 2 * t.W == f->W)
+                      : t.mode == 2 ? ((t.H + 1) / 2 == f->H && (t.W + 1) / 2 == f->W) : false;
+        STL_CHECK(ok, "det_fuse: term %d mode %d of %d x %d into %d x %d", i, t.mode, t.H, t.W, f->H, f->W);
+    }
+    const int64_t n = (int64_t)f->B * f->H * f->W * f->C;
+    STL_LAUNCH(fuse_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ST, *f);
+    STL_LAUNCH_CHECK("det_fuse");
+    return 0;
+}
+
+extern "C" int stl_det_decode(const float* reg, const float* cls, const float* anchors, int B, int A, int nc, float thr, float xmax,
+                              float ymax, float* boxes, float* scores, int32_t* classes, int32_t* index, int32_t* count, void* stream) {
+    STL_CHECK(B >= 0 && A >= 0 && nc >= 1, "det_decode: B %d A %d nc %d", B, A, nc);
+    if (B == 0 || A == 0) return 0;
+    STL_CHECK(reg && cls && anchors && boxes && scores && classes && index && count, "det_decode: null pointer");
+    STL_LAUNCH(decode_kernel, dim3(B), dim3(kDecThreads), 0, ST, reg, cls, anchors, A, nc, thr, xmax, ymax, boxes, scores, classes,
+               index, count);
+    STL_LAUNCH_CHECK("det_decode");
+    return 0;
+}
+
+extern "C" int64_t stl_det_nms_workspace(int n) {
+    const int64_t nblk = (n + 63) / 64;
+    return (int64_t)n * 16 + (int64_t)n * nblk * 8;
+}
+
+extern "C" int stl_det_nms(const float* boxes, const int32_t* classes, const int32_t* order, int n, double iou_thr, void* work,
+                           int32_t* keep, int32_t* count, void* stream) {
+    STL_CHECK(n >= 0 && n <= STL_DET_NMS_MAX, "det_nms: %d candidates (at most %d)", n, STL_DET_NMS_MAX);
+    STL_CHECK(count, "det_nms: null count");
+    if (n == 0) {
+        (void)hipMemsetAsync(count, 0, 4, ST);
+        return 0;
+    }
+    STL_CHECK(boxes && classes && order && work && keep, "det_nms: null pointer");
+    const int nblk = (n + 63) / 64;
+    // torchvision compares the float IoU with a double threshold: iou > t  <=>  iou > (the largest float <= t)
+    float thr = (float)iou_thr;
+    if ((double)thr > iou_thr) thr = nextafterf(thr, -INFINITY);
+    float4* sbox = reinterpret_cast<float4*>(work);
+    unsigned long long* mask = reinterpret_cast<unsigned long long*>(sbox + n);
+    STL_LAUNCH(nms_prep_kernel, dim3(1), dim3(1024), 0, ST, boxes, classes, order, n, sbox);
+    STL_LAUNCH_CHECK("det_nms_prep");
+    STL_LAUNCH(nms_mask_kernel, dim3(nblk, nblk), dim3(64), 0, ST, (const float4*)sbox, n, nblk, thr, mask);
+    STL_LAUNCH_CHECK("det_nms_mask");
+    STL_LAUNCH(nms_sweep_kernel, dim3(1), dim3(64), (size_t)nblk * 8, ST, (const unsigned long long*)mask, order, n, nblk, keep, count);
+    STL_LAUNCH_CHECK("det_nms_sweep");
+    return 0;
+}

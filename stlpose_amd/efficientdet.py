@@ -1,0 +1,653 @@
+"""EfficientDet person detector on MI355X (mirror of reference ``src/models/EfficientDet.py`` with
+``models/efficientdet_utils/{model,utils}.py`` and ``models/efficientnet/{model,utils,utils_extra}.py``).
+
+``EfficientDetBackbone(num_classes, compound_coef)`` holds the reference's parameters and buffers under the reference's key names
+(a reference checkpoint loads with ``strict=True``, also with the ``module.`` prefix of a DataParallel save).  Its forward is
+inference only and runs every layer through csrc/detector.hip (fp32, NHWC): the preprocess kernel, the stem, depthwise and
+squeeze-excitation kernels, the pointwise GEMM on fp32 MFMA with BN folded into its weights, the BiFPN node kernel, the shared
+heads writing straight into the concatenated outputs, the decode kernel and the class-aware NMS.  BN is folded into packed fp32
+weights on the device and refolded when any parameter or buffer changes; the launches of one batch size are listed once
+(``_Plan``) and replayed; the last MAX_PLANS batch sizes keep their plans.  Only the kept boxes, scores and labels reach the host.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import math
+from typing import Dict, List, Optional
+
+import numpy as np
+import torch
+import torch.nn as nn
+
+from . import capi, ops  # noqa: F401  (ops registers the stlpose:: custom ops)
+
+BN_EPS = 1e-3
+MAX_SIZE = 512   # preprocess canvas; the reference passes 512 for every compound_coef (EfficientDet.py:96)
+MEAN, STD = (0.406, 0.456, 0.485), (0.225, 0.224, 0.229)
+RATIOS = [(1.0, 1.0), (1.4, 0.7), (0.7, 1.4)]
+SCALES = [2 ** 0, 2 ** (1.0 / 3.0), 2 ** (2.0 / 3.0)]
+STRIDES = [8, 16, 32, 64, 128]
+
+# EfficientDet.py:20-40, for the compound coefficients setup_detector allows
+FPN_FILTERS = {0: 64, 3: 160}
+FPN_REPEATS = {0: 3, 3: 6}
+HEAD_REPEATS = {0: 3, 3: 4}
+P345_CHANNELS = {0: (40, 112, 320), 3: (48, 136, 384)}
+ANCHOR_SCALE = {0: 4.0, 3: 4.0}
+# EfficientNet-B0 stages (efficientnet/utils.py:235-240): kernel, repeats, in, out, expand, stride; SE ratio 0.25 everywhere
+STAGES = [(3, 1, 32, 16, 1, 1), (3, 2, 16, 24, 6, 2), (5, 2, 24, 40, 6, 2), (3, 3, 40, 80, 6, 2), (5, 3, 80, 112, 6, 1),
+          (5, 4, 112, 192, 6, 2), (3, 1, 192, 320, 6, 1)]
+WIDTH_DEPTH = {0: (1.0, 1.0), 3: (1.2, 1.4)}   # efficientnet-b0 / -b3
+
+
+def round_filters(f: int, width: float) -> int:
+    x = f * width
+    new = max(8, int(x + 4) // 8 * 8)
+    return int(new + 8 if new < 0.9 * x else new)
+
+
+def block_specs(cc: int) -> List[dict]:
+    """The MBConv blocks of EfficientNet-b{cc}: in / out channels, kernel, stride, expansion, squeezed channels, identity skip.
+    Like the reference, the skip is taken by the repeated blocks of a stage only (their stride is the integer 1)."""
+    w, d = WIDTH_DEPTH[cc]
+    out = []
+    for k, r, i, o, e, s in STAGES:
+        ci, co, rep = round_filters(i, w), round_filters(o, w), int(math.ceil(d * r))
+        for j in range(rep):
+            cin = ci if j == 0 else co
+            out.append(dict(ci=cin, co=co, k=k, s=s if j == 0 else 1, e=e, mid=cin * e, se=max(1, int(cin * 0.25)), skip=j > 0 and cin == co))
+    return out
+
+
+# ------------------------------------------------------------------------------------------------ modules with the reference's keys
+def _bn(c):
+    return nn.BatchNorm2d(c, momentum=0.01, eps=BN_EPS)
+
+
+class _SameConv(nn.Module):
+    """Conv2dStaticSamePadding: the conv sits under ``.conv``."""
+
+    def __init__(self, ci, co, k, stride=1, bias=True, groups=1):
+        super().__init__()
+        self.conv = nn.Conv2d(ci, co, k, stride=stride, bias=bias, groups=groups)
+
+
+class _Pool(nn.Module):
+    """MaxPool2dStaticSamePadding(3, 2): no parameters."""
+
+
+class _MBConv(nn.Module):
+    def __init__(self, b):
+        super().__init__()
+        if b["e"] != 1:
+            self._expand_conv = _SameConv(b["ci"], b["mid"], 1, bias=False)
+            self._bn0 = _bn(b["mid"])
+        self._depthwise_conv = _SameConv(b["mid"], b["mid"], b["k"], stride=b["s"], bias=False, groups=b["mid"])
+        self._bn1 = _bn(b["mid"])
+        self._se_reduce = _SameConv(b["mid"], b["se"], 1)
+        self._se_expand = _SameConv(b["se"], b["mid"], 1)
+        self._project_conv = _SameConv(b["mid"], b["co"], 1, bias=False)
+        self._bn2 = _bn(b["co"])
+
+
+class _EffNet(nn.Module):
+    def __init__(self, cc):
+        super().__init__()
+        self.specs = block_specs(cc)
+        c0 = round_filters(32, WIDTH_DEPTH[cc][0])
+        self._conv_stem = _SameConv(3, c0, 3, stride=2, bias=False)
+        self._bn0 = _bn(c0)
+        self._blocks = nn.ModuleList([_MBConv(b) for b in self.specs])
+
+
+class _Backbone(nn.Module):
+    def __init__(self, cc):
+        super().__init__()
+        self.model = _EffNet(cc)
+
+
+class _SepConv(nn.Module):
+    def __init__(self, ci, co=None, norm=True):
+        super().__init__()
+        co = ci if co is None else co
+        self.depthwise_conv = _SameConv(ci, ci, 3, bias=False, groups=ci)
+        self.pointwise_conv = _SameConv(ci, co, 1)
+        self.norm = norm
+        if norm:
+            self.bn = _bn(co)
+
+
+class _BiFPN(nn.Module):
+    NODES = ("conv6_up", "conv5_up", "conv4_up", "conv3_up", "conv4_down", "conv5_down", "conv6_down", "conv7_down")
+    WEIGHTS = (("p6_w1", 2), ("p5_w1", 2), ("p4_w1", 2), ("p3_w1", 2), ("p4_w2", 3), ("p5_w2", 3), ("p6_w2", 3), ("p7_w2", 2))
+
+    def __init__(self, c, p345, first):
+        super().__init__()
+        for n in self.NODES:
+            setattr(self, n, _SepConv(c))
+        self.first_time = first
+        if first:
+            self.p5_down_channel = nn.Sequential(_SameConv(p345[2], c, 1), _bn(c))
+            self.p4_down_channel = nn.Sequential(_SameConv(p345[1], c, 1), _bn(c))
+            self.p3_down_channel = nn.Sequential(_SameConv(p345[0], c, 1), _bn(c))
+            self.p5_to_p6 = nn.Sequential(_SameConv(p345[2], c, 1), _bn(c), _Pool())
+            self.p6_to_p7 = nn.Sequential(_Pool())
+            self.p4_down_channel_2 = nn.Sequential(_SameConv(p345[1], c, 1), _bn(c))
+            self.p5_down_channel_2 = nn.Sequential(_SameConv(p345[2], c, 1), _bn(c))
+        for n, k in self.WEIGHTS:
+            setattr(self, n, nn.Parameter(torch.ones(k, dtype=torch.float32)))
+
+
+class _Head(nn.Module):
+    def __init__(self, c, co, layers):
+        super().__init__()
+        self.conv_list = nn.ModuleList([_SepConv(c, c, norm=False) for _ in range(layers)])
+        self.bn_list = nn.ModuleList([nn.ModuleList([_bn(c) for _ in range(layers)]) for _ in range(5)])
+        self.header = _SepConv(c, co, norm=False)
+
+
+# ------------------------------------------------------------------------------------------------ host-side reference pieces
+def anchors(cc: int, image_hw=(MAX_SIZE, MAX_SIZE)) -> np.ndarray:
+    """Anchors.forward (efficientdet_utils/utils.py:85-144): [A, 4] (y1, x1, y2, x2), built in float64, cast to float32."""
+    h, w = image_hw
+    out = []
+    for stride in STRIDES:
+        if w % stride:
+            raise ValueError("input size must be divided by the stride.")
+        level = []
+        for scale in SCALES:
+            for r in RATIOS:
+                base = ANCHOR_SCALE[cc] * stride * scale
+                ax, ay = base * r[0] / 2.0, base * r[1] / 2.0
+                xv, yv = np.meshgrid(np.arange(stride / 2, w, stride), np.arange(stride / 2, h, stride))
+                xv, yv = xv.reshape(-1), yv.reshape(-1)
+                level.append(np.stack([yv - ay, xv - ax, yv + ay, xv + ax], 1)[:, None])
+        out.append(np.concatenate(level, 1).reshape(-1, 4))
+    return np.vstack(out).astype(np.float32)
+
+
+def resize_meta(old_h: int, old_w: int, size: int = MAX_SIZE):
+    """aspectaware_resize_padding's sizes (efficientdet_utils/utils.py:209-239), in Python float64: (new_w, new_h, old_w, old_h,
+    padding_w, padding_h)."""
+    if old_w > old_h:
+        new_w, new_h = size, int(size / old_w * old_h)
+    else:
+        new_w, new_h = int(size / old_h * old_w), size
+    return new_w, new_h, old_w, old_h, size - new_w, size - new_h
+
+
+def invert_affine(meta, rois: np.ndarray) -> np.ndarray:
+    """invert_affine (efficientdet_utils/utils.py:242-256): float32 rois divided by the float64 ratios, as numpy does it."""
+    new_w, new_h, old_w, old_h = meta[:4]
+    r = rois.copy()
+    r[:, [0, 2]] = r[:, [0, 2]] / (new_w / old_w)
+    r[:, [1, 3]] = r[:, [1, 3]] / (new_h / old_h)
+    return r
+
+
+def _device(dev) -> torch.device:
+    """torch.device("cuda") -> cuda:<current>: the cached weights and plans compare devices, and "cuda" != "cuda:0"."""
+    dev = torch.device(dev)
+    return torch.device(dev.type, torch.cuda.current_device()) if dev.type == "cuda" and dev.index is None else dev
+
+
+def _strip(sd: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+    if sd and all(k.startswith("module.") for k in sd):
+        return {k[len("module."):]: v for k, v in sd.items()}
+    return sd
+
+
+# ------------------------------------------------------------------------------------------------ weight packing
+def _fold(bn: nn.BatchNorm2d):
+    s = bn.weight.detach().double() / torch.sqrt(bn.running_var.detach().double() + bn.eps)
+    return s, bn.bias.detach().double() - bn.running_mean.detach().double() * s
+
+
+class _Packer:
+    """Packs folded weights into one fp32 device buffer; every piece starts on a 16-float boundary."""
+
+    def __init__(self):
+        self.parts, self.n = [], 0
+
+    def add(self, t: torch.Tensor) -> int:
+        off = self.n
+        flat = t.reshape(-1).double()
+        pad = (-flat.numel()) % 16
+        self.parts.append(torch.cat([flat, flat.new_zeros(pad)]) if pad else flat)
+        self.n += flat.numel() + pad
+        return off
+
+    def pw(self, conv: nn.Conv2d, bn: Optional[nn.BatchNorm2d] = None):
+        """1x1 conv (+ BN) -> (w offset, bias offset or None, Kp, Np): w packed [Kp][Np] zero-padded, bias [Np]."""
+        w = conv.weight.detach().double().reshape(conv.out_channels, conv.in_channels)
+        b = conv.bias.detach().double() if conv.bias is not None else None
+        if bn is not None:
+            s, t = _fold(bn)
+            w = w * s[:, None]
+            b = t if b is None else b * s + t
+        co, ci = w.shape
+        kp, np_ = -(-ci // 16) * 16, -(-co // 64) * 64
+        wp = w.new_zeros(kp, np_)
+        wp[:ci, :co] = w.t()
+        bo = None
+        if b is not None:
+            bp = w.new_zeros(np_)
+            bp[:co] = b
+            bo = self.add(bp)
+        return self.add(wp), bo, kp, np_
+
+    def dw(self, conv: nn.Conv2d, bn: Optional[nn.BatchNorm2d] = None):
+        """depthwise k x k (+ BN) -> (w offset [k][k][C], bias offset or None)."""
+        w = conv.weight.detach().double()[:, 0]   # [C, k, k]
+        bo = None
+        if bn is not None:
+            s, t = _fold(bn)
+            w = w * s[:, None, None]
+            bo = self.add(t)
+        return self.add(w.permute(1, 2, 0).contiguous()), bo
+
+    def done(self, dev) -> torch.Tensor:
+        return torch.cat(self.parts).float().to(dev).contiguous() if self.parts else torch.zeros(1, device=dev)
+
+
+# ------------------------------------------------------------------------------------------------ the launch plan
+class _Plan:
+    """Every launch of one forward at batch B on the 512 canvas, with its buffers: a list of (entry point, arguments) replayed by
+    ``run``; ``canvas`` is the input, ``feats`` the five BiFPN outputs (NHWC), ``reg`` / ``cls`` the head outputs."""
+
+    def __init__(self, m: "EfficientDetBackbone", B: int, dev):
+        self.B, self.dev, self.calls, self._keep = B, dev, [], []
+        self.flops = self.bytes = 0   # from the shapes: multiply-adds x 2, and every tensor each launch reads or writes once
+        self.wbuf = m._wbuf
+        S = MAX_SIZE
+        self.canvas = torch.empty(B, S, S, 3, device=dev)
+        L = m._layout
+        net = m.backbone_net.model
+        H = (S + 1) // 2
+        x = self._buf(B, H, H, net._conv_stem.conv.out_channels)
+        self._call("stl_det_stem", self.canvas, self._w(L["stem"][0]), self._w(L["stem"][1]), x, B, S, S, x.shape[3])
+        self._cost(2 * x.numel() * 27, 4 * (self.canvas.numel() + x.numel()))
+        h = H
+        feats, specs = [], net.specs
+        for i, (b, lay) in enumerate(zip(specs, L["blocks"])):
+            if b["s"] == 2:   # the wrapper keeps the input of every stride-2 block (efficientdet_utils/model.py:413-414)
+                feats.append((x, h))
+            inp = x
+            if b["e"] != 1:
+                y = self._buf(B, h, h, b["mid"])
+                self._pw(x, y, B, h * h, b["ci"], b["mid"], lay["expand"], act=1)
+                x = y
+            ho = (h + b["s"] - 1) // b["s"]
+            y = self._buf(B, ho, ho, b["mid"])
+            self._call("stl_det_dwconv", x, self._w(lay["dw"][0]), self._w(lay["dw"][1]), y, B, h, h, b["mid"], b["k"], b["s"], 1)
+            self._cost(2 * y.numel() * b["k"] ** 2, 4 * (x.numel() + y.numel()))
+            h, x = ho, y
+            part = torch.empty(capi.lib().stl_det_se_workspace(B) * b["mid"], device=dev)
+            scale = torch.empty(B, b["mid"], device=dev)
+            se = lay["se"]
+            self._call("stl_det_se", x, B, h * h, b["mid"], b["se"], self._w(se[0]), self._w(se[1]), self._w(se[2]), self._w(se[3]),
+                       part, scale)
+            self._cost(x.numel() + 4 * B * b["mid"] * b["se"], 4 * x.numel())
+            y = self._buf(B, h, h, b["co"])
+            self._pw(x, y, B, h * h, b["mid"], b["co"], lay["project"], act=0, in_scale=scale, residual=inp if b["skip"] else None)
+            x = y
+        feats.append((x, h))
+        p3, p4, p5 = feats[-3:]
+        self.backbone = [f for f, _ in feats[-3:]]   # P3, P4, P5
+        c = m.fpn_channels
+        levels = None
+        for cell, lay in zip(m.bifpn, L["bifpn"]):
+            levels = self._bifpn(cell, lay, levels, p3, p4, p5, c)
+        self.feats = levels
+        A, nc = m.num_anchors_total, m.num_classes
+        self.reg = torch.empty(B, A, 4, device=dev)
+        self.cls = torch.empty(B, A, nc, device=dev)
+        for head, lay, out, k, act in ((m.regressor, L["regressor"], self.reg, 4, 0), (m.classifier, L["classifier"], self.cls, nc, 2)):
+            aoff = 0
+            for li, (f, hh) in enumerate(levels):
+                t = f
+                for i in range(len(head.conv_list)):
+                    d = self._buf(B, hh, hh, c)
+                    self._call("stl_det_dwconv", t, self._w(lay["dw"][i]), None, d, B, hh, hh, c, 3, 1, 0)
+                    self._cost(2 * d.numel() * 9, 8 * d.numel())
+                    e = self._buf(B, hh, hh, c)
+                    self._pw(d, e, B, hh * hh, c, c, lay["pw"][li][i], act=1)
+                    t = e
+                d = self._buf(B, hh, hh, c)
+                self._call("stl_det_dwconv", t, self._w(lay["hdw"]), None, d, B, hh, hh, c, 3, 1, 0)
+                self._cost(2 * d.numel() * 9, 8 * d.numel())
+                self._pw(d, out, B, hh * hh, c, 9 * k, lay["hpw"], act=act, img_stride=A * k, row_stride=9 * k, off=aoff * k)
+                aoff += hh * hh * 9
+
+    def _buf(self, B, h, w, c):
+        return torch.empty(B, h, w, c, device=self.dev)
+
+    def _w(self, off):
+        return None if off is None else self.wbuf[off:]
+
+    def _cost(self, flops, nbytes):
+        self.flops += int(flops)
+        self.bytes += int(nbytes)
+
+    def _call(self, name, *args):
+        conv = []
+        for a in args:
+            if torch.is_tensor(a):
+                conv.append(C.c_void_p(a.data_ptr()))
+                self._keep.append(a)
+            elif a is None:
+                conv.append(None)
+            else:
+                conv.append(a)
+        self.calls.append((getattr(capi.lib(), name), name, conv))
+
+    def _pw(self, x, out, B, hw, ci, co, pk, act, in_scale=None, residual=None, img_stride=None, row_stride=None, off=0):
+        w, b, kp, np_ = pk
+        p = capi.DetPointwise(x.data_ptr(), self.wbuf[w:].data_ptr(), None if b is None else self.wbuf[b:].data_ptr(),
+                              None if in_scale is None else in_scale.data_ptr(), None if residual is None else residual.data_ptr(),
+                              out.data_ptr(), B * hw, hw * co if img_stride is None else img_stride,
+                              co if row_stride is None else row_stride, off, hw, ci, co, kp, np_, act)
+        self._keep += [x, out] + [t for t in (in_scale, residual) if t is not None]
+        m = B * hw
+        self._cost(2 * m * ci * co, 4 * (m * ci + m * co * (2 if residual is not None else 1) + kp * np_))
+        self.calls.append((capi.lib().stl_det_pointwise, "stl_det_pointwise", [C.byref(p)]))
+        self._keep.append(p)
+
+    def _fuse(self, out, terms, wparam):
+        f = capi.DetFuse()
+        f.B, f.H, f.W, f.C, f.nterms = out.shape[0], out.shape[1], out.shape[2], out.shape[3], len(terms)
+        for i, (t, mode) in enumerate(terms):
+            f.t[i] = capi.DetTerm(t.data_ptr(), mode, t.shape[1], t.shape[2], 0)
+            self._keep.append(t)
+        f.wparam = None if wparam is None else wparam.data_ptr()
+        f.out = out.data_ptr()
+        self._keep += [out, f]
+        self._cost(out.numel() * (2 * len(terms) + 4), 4 * (out.numel() + sum(t.numel() for t, _ in terms)))
+        self.calls.append((capi.lib().stl_det_fuse, "stl_det_fuse", [C.byref(f)]))
+
+    def _sep(self, x, pk, h, c):
+        """SeparableConvBlock: depthwise 3x3 (no bias) then 1x1 with bias and BN folded, no activation."""
+        d = self._buf(self.B, h, h, c)
+        self._call("stl_det_dwconv", x, self._w(pk[0]), None, d, self.B, h, h, c, 3, 1, 0)
+        self._cost(2 * d.numel() * 9, 8 * d.numel())
+        y = self._buf(self.B, h, h, c)
+        self._pw(d, y, self.B, h * h, c, c, pk[1], act=0)
+        return y
+
+    def _bifpn(self, cell, lay, levels, p3, p4, p5, c):
+        B = self.B
+        wp = lay["weights"]
+        if levels is None:
+            (x3, h3), (x4, h4), (x5, h5) = p3, p4, p5
+            t = self._buf(B, h5, h5, c)
+            self._pw(x5, t, B, h5 * h5, x5.shape[3], c, lay["p5_to_p6"], act=0)
+            h6, h7 = (h5 + 1) // 2, (h5 + 3) // 4
+            p6 = self._buf(B, h6, h6, c)
+            self._fuse(p6, [(t, 2)], None)
+            p7 = self._buf(B, h7, h7, c)
+            self._fuse(p7, [(p6, 2)], None)
+            ins = []
+            for (xx, hh), key in ((p3, "p3_down_channel"), (p4, "p4_down_channel"), (p5, "p5_down_channel")):
+                y = self._buf(B, hh, hh, c)
+                self._pw(xx, y, B, hh * hh, xx.shape[3], c, lay[key], act=0)
+                ins.append(y)
+            p3_in, p4_in, p5_in = ins
+            p6_in, p7_in = p6, p7
+        else:
+            (p3_in, _), (p4_in, _), (p5_in, _), (p6_in, _), (p7_in, _) = levels
+        hs = [p.shape[1] for p in (p3_in, p4_in, p5_in, p6_in, p7_in)]
+
+        def node(name, wname, terms, h):
+            f = self._buf(B, h, h, c)
+            self._fuse(f, terms, wp[wname])
+            return self._sep(f, lay[name], h, c)
+        p6_up = node("conv6_up", "p6_w1", [(p6_in, 0), (p7_in, 1)], hs[3])
+        p5_up = node("conv5_up", "p5_w1", [(p5_in, 0), (p6_up, 1)], hs[2])
+        p4_up = node("conv4_up", "p4_w1", [(p4_in, 0), (p5_up, 1)], hs[1])
+        p3_out = node("conv3_up", "p3_w1", [(p3_in, 0), (p4_up, 1)], hs[0])
+        if levels is None:
+            ins = []
+            for (xx, hh), key in ((p4, "p4_down_channel_2"), (p5, "p5_down_channel_2")):
+                y = self._buf(B, hh, hh, c)
+                self._pw(xx, y, B, hh * hh, xx.shape[3], c, lay[key], act=0)
+                ins.append(y)
+            p4_in, p5_in = ins
+        p4_out = node("conv4_down", "p4_w2", [(p4_in, 0), (p4_up, 0), (p3_out, 2)], hs[1])
+        p5_out = node("conv5_down", "p5_w2", [(p5_in, 0), (p5_up, 0), (p4_out, 2)], hs[2])
+        p6_out = node("conv6_down", "p6_w2", [(p6_in, 0), (p6_up, 0), (p5_out, 2)], hs[3])
+        p7_out = node("conv7_down", "p7_w2", [(p7_in, 0), (p6_out, 2)], hs[4])
+        return [(p, p.shape[1]) for p in (p3_out, p4_out, p5_out, p6_out, p7_out)]
+
+    def run(self, stream: int) -> None:
+        st = C.c_void_p(stream)
+        for fn, name, args in self.calls:
+            capi.check(fn(*args, st), name)
+
+
+# ------------------------------------------------------------------------------------------------ the model
+class EfficientDetBackbone(nn.Module):
+    """models.EfficientDet (EfficientDetBackbone, src/models/EfficientDet.py:16-133), inference on the MI355X.
+
+    forward(inputs, preprocess=True, postprocess=True, threshold=None, iou_threshold=None): inputs a float tensor [B, 3, H, W]
+    (04 passes ``img / 255``) or a list of CHW float arrays in [0, 1]; postprocess=False returns (features, regression,
+    classification, anchors) with the reference's shapes (five NCHW maps, [B, A, 4], [B, A, num_classes] after the sigmoid,
+    [1, A, 4]) on the GPU; otherwise one dict per image with CPU tensors ``boxes`` float32 [k, 4] (x1, y1, x2, y2 in original
+    pixels), ``labels`` int32 (class + 1) and ``scores`` float32, in NMS keep order.  Raises in training mode."""
+
+    def __init__(self, num_classes=80, compound_coef=0, load_weights=False, **kwargs):
+        super().__init__()
+        if compound_coef not in FPN_FILTERS:
+            raise NotImplementedError(f"EfficientDet: compound_coef {compound_coef} (supported: 0 and 3, what setup_detector allows)")
+        if load_weights:
+            raise NotImplementedError("EfficientDet: load_weights=True downloads pretrained EfficientNet weights; load a state_dict")
+        if int(num_classes) < 1:
+            raise ValueError(f"EfficientDet: num_classes = {num_classes}")
+        self.compound_coef = cc = compound_coef
+        ratios = kwargs.get("ratios", RATIOS)
+        scales = kwargs.get("scales", SCALES)
+        if [tuple(r) for r in ratios] != RATIOS or len(scales) != 3 or not np.allclose(scales, SCALES):
+            raise NotImplementedError("EfficientDet: only the reference's anchor ratios and scales are supported")
+        self.num_classes = int(num_classes)
+        self.fpn_channels = c = FPN_FILTERS[cc]
+        self.bifpn = nn.Sequential(*[_BiFPN(c, P345_CHANNELS[cc], i == 0) for i in range(FPN_REPEATS[cc])])
+        self.regressor = _Head(c, 9 * 4, HEAD_REPEATS[cc])
+        self.classifier = _Head(c, 9 * self.num_classes, HEAD_REPEATS[cc])
+        self.backbone_net = _Backbone(cc)
+        self.threshold = kwargs.get("threshold", 0.6)
+        self.iou_threshold = kwargs.get("iou_threshold", 0.5)
+        self.anchors_np = anchors(cc)
+        self.num_anchors_total = self.anchors_np.shape[0]
+        self._version, self._plans, self._wbuf, self._anchor_dev = None, {}, None, None
+        self.eval()
+
+    # ---------------------------------------------------------------- state
+    def load_state_dict(self, state_dict, strict=True, assign=False):
+        return super().load_state_dict(_strip(dict(state_dict)), strict=strict, assign=assign)
+
+    def _state_version(self):
+        return tuple((t.data_ptr(), t._version) for t in list(self.parameters()) + list(self.buffers()))
+
+    def ready(self, dev) -> None:
+        """Fold BN and pack every weight into one fp32 device buffer; redone when any parameter or buffer has changed."""
+        dev = _device(dev)
+        if self.backbone_net.model._bn0.weight.device != dev:
+            self.to(dev)
+        v = self._state_version()
+        if v == self._version and self._wbuf is not None and self._wbuf.device == dev:
+            return
+        P = _Packer()
+        net = self.backbone_net.model
+        s, t = _fold(net._bn0)
+        stem = (P.add((net._conv_stem.conv.weight.detach().double() * s[:, None, None, None]).permute(2, 3, 1, 0).contiguous()),
+                P.add(t))
+        blocks = []
+        for blk, b in zip(net._blocks, net.specs):
+            lay = {"dw": P.dw(blk._depthwise_conv.conv, blk._bn1), "project": P.pw(blk._project_conv.conv, blk._bn2)}
+            if b["e"] != 1:
+                lay["expand"] = P.pw(blk._expand_conv.conv, blk._bn0)
+            r, e = blk._se_reduce.conv, blk._se_expand.conv
+            lay["se"] = (P.add(r.weight.detach().reshape(b["se"], b["mid"])), P.add(r.bias.detach()),
+                         P.add(e.weight.detach().reshape(b["mid"], b["se"])), P.add(e.bias.detach()))
+            blocks.append(lay)
+        cells = []
+        for cell in self.bifpn:
+            lay = {}
+            for n in _BiFPN.NODES:
+                sep = getattr(cell, n)
+                lay[n] = (P.dw(sep.depthwise_conv.conv)[0], P.pw(sep.pointwise_conv.conv, sep.bn))
+            if cell.first_time:
+                for key in ("p5_down_channel", "p4_down_channel", "p3_down_channel", "p5_to_p6", "p4_down_channel_2", "p5_down_channel_2"):
+                    seq = getattr(cell, key)
+                    lay[key] = P.pw(seq[0].conv, seq[1])
+            lay["weights"] = {n: P.add(getattr(cell, n).detach()) for n, _ in _BiFPN.WEIGHTS}
+            cells.append(lay)
+        heads = {}
+        for name in ("regressor", "classifier"):
+            hd = getattr(self, name)
+            heads[name] = {"dw": [P.dw(cv.depthwise_conv.conv)[0] for cv in hd.conv_list],
+                           "pw": [[P.pw(cv.pointwise_conv.conv, hd.bn_list[lv][i]) for i, cv in enumerate(hd.conv_list)] for lv in range(5)],
+                           "hdw": P.dw(hd.header.depthwise_conv.conv)[0], "hpw": P.pw(hd.header.pointwise_conv.conv)}
+        self._wbuf = P.done(dev)
+        for cell in cells:   # BiFPN weight offsets -> device views
+            cell["weights"] = {n: self._wbuf[o:] for n, o in cell["weights"].items()}
+        self._layout = {"stem": stem, "blocks": blocks, "bifpn": cells, **heads}
+        self._anchor_dev = torch.from_numpy(self.anchors_np).to(dev)
+        self._plans.clear()
+        self._version = self._state_version()
+
+    MAX_PLANS = 4   # plans own every intermediate (no buffer reuse): D3 at batch 32 holds several GB; least recently used go first
+
+    def plan(self, B: int, dev) -> _Plan:
+        dev = _device(dev)
+        self.ready(dev)
+        p = self._plans.pop(B, None)
+        if p is None:
+            while len(self._plans) >= self.MAX_PLANS:
+                self._plans.pop(next(iter(self._plans)))
+            p = _Plan(self, B, dev)
+        self._plans[B] = p   # most recently used last
+        return p
+
+    # ---------------------------------------------------------------- forward
+    def _check_mode(self):
+        if self.training:
+            raise NotImplementedError("EfficientDet runs in inference mode only (no backward, no training): call .eval() first")
+
+    def _preprocess(self, srcs: List[torch.Tensor], kind: int, dev):
+        """srcs on `dev`: kind 0 uint8 HWC, 1 float32 CHW.  Fills the plan's canvas; returns (plan, metas)."""
+        B = len(srcs)
+        p = self.plan(B, dev)
+        recs = (capi.DetImage * B)()
+        metas = []
+        for i, s in enumerate(srcs):
+            oh, ow = (s.shape[0], s.shape[1]) if kind == 0 else (s.shape[1], s.shape[2])
+            m = resize_meta(int(oh), int(ow))
+            metas.append(m)
+            new_w, new_h = m[0], m[1]
+            recs[i] = capi.DetImage(s.data_ptr(), kind, oh, ow, new_h, new_w, 0, 1.0 / (new_h / oh), 1.0 / (new_w / ow))
+        tab = torch.frombuffer(bytearray(bytes(recs)), dtype=torch.uint8).to(dev)
+        capi.call("stl_det_preprocess", tab.data_ptr(), B, MAX_SIZE, p.canvas.data_ptr(), ops._st())
+        return p, metas, (tab, srcs)
+
+    def _float_sources(self, inputs, dev):
+        if torch.is_tensor(inputs):
+            if inputs.dim() != 4 or inputs.shape[1] != 3:
+                raise ValueError(f"EfficientDet: inputs must be [B, 3, H, W], got {tuple(inputs.shape)}")
+            x = inputs.detach().to(dev, torch.float32).contiguous()
+            return [x[i] for i in range(x.shape[0])]
+        out = []
+        for a in inputs:
+            t = torch.as_tensor(np.asarray(a.detach().cpu() if torch.is_tensor(a) else a, np.float32))
+            if t.dim() != 3 or t.shape[0] != 3:
+                raise ValueError(f"EfficientDet: each image must be CHW with 3 channels, got {tuple(t.shape)}")
+            out.append(t.to(dev).contiguous())
+        return out
+
+    def run_raw(self, srcs, kind: int, dev):
+        """Preprocess + network on `dev`; returns (plan, metas)."""
+        self._check_mode()
+        with torch.no_grad():
+            p, metas, keep = self._preprocess(srcs, kind, dev)
+            p.run(ops._st())
+        p._inflight = keep   # the sources and the record table live until the next call
+        return p, metas
+
+    def forward(self, inputs, preprocess=True, postprocess=True, threshold=None, iou_threshold=None):
+        self._check_mode()
+        if threshold is not None:
+            self.threshold = threshold
+        if iou_threshold is not None:
+            self.iou_threshold = iou_threshold
+        dev = torch.device("cuda", torch.cuda.current_device())
+        if preprocess:
+            p, metas = self.run_raw(self._float_sources(inputs, dev), 1, dev)
+        else:
+            x = inputs.detach().to(dev, torch.float32)
+            if tuple(x.shape[1:]) != (3, MAX_SIZE, MAX_SIZE):
+                raise ValueError(f"EfficientDet: preprocess=False takes [B, 3, {MAX_SIZE}, {MAX_SIZE}], got {tuple(x.shape)}")
+            p = self.plan(x.shape[0], dev)
+            with torch.no_grad():
+                p.canvas.copy_(x.permute(0, 2, 3, 1))
+                p.run(ops._st())
+            metas = None
+        if not postprocess:
+            feats = tuple(f.permute(0, 3, 1, 2).clone() for f, _ in p.feats)
+            return feats, p.reg.clone(), p.cls.clone(), self._anchor_dev[None].clone()
+        return self.detect(p, metas, self.threshold, self.iou_threshold)
+
+    def detect(self, p: _Plan, metas, threshold, iou_threshold) -> List[Dict[str, torch.Tensor]]:
+        """postprocess + invert_affine + the reference's dict format from a plan's head outputs."""
+        dets = detect_from_heads(p.reg, p.cls, self._anchor_dev, threshold, iou_threshold)
+        out = []
+        for i, (boxes, cls, scores) in enumerate(dets):
+            if len(scores) == 0:
+                out.append({"boxes": torch.zeros(0), "labels": torch.zeros(0, dtype=torch.int32), "scores": torch.zeros(0)})
+                continue
+            if metas is not None:
+                boxes = invert_affine(metas[i], boxes)
+            out.append({"boxes": torch.from_numpy(boxes), "labels": torch.from_numpy(cls.astype(np.int32)) + 1,
+                        "scores": torch.from_numpy(scores)})
+        return out
+
+
+EfficientDet = EfficientDetBackbone
+
+
+def detect_from_heads(reg: torch.Tensor, cls: torch.Tensor, anchors_dev: torch.Tensor, threshold: float, iou_threshold: float):
+    """postprocess (efficientdet_utils/utils.py:150-187) on the device from the head outputs reg [B, A, 4] and cls [B, A, nc]:
+    the decode kernel, then per image the class-aware NMS.  Returns per image (boxes float32 [k, 4] on the 512 canvas, classes
+    int64 [k], scores float32 [k]) as numpy arrays, in keep order."""
+    boxes, scores, classes, index, count = torch.ops.stlpose.det_decode(reg, cls, anchors_dev, float(threshold), float(MAX_SIZE - 1),
+                                                                        float(MAX_SIZE - 1))
+    counts = count.cpu().tolist()
+    keeps = []
+    for i, n in enumerate(counts):
+        if n == 0:
+            keeps.append(None)
+            continue
+        order = torch.sort(scores[i, :n], descending=True, stable=True).indices.to(torch.int32)
+        keeps.append(torch.ops.stlpose.det_nms(boxes[i, :n], classes[i, :n], order, float(iou_threshold)))
+    out = []
+    for i, n in enumerate(counts):
+        if keeps[i] is None:
+            out.append((np.zeros((0, 4), np.float32), np.zeros(0, np.int64), np.zeros(0, np.float32)))
+            continue
+        keep, kc = keeps[i]
+        k = keep[:int(kc.item())].long()
+        out.append((boxes[i, k].cpu().numpy(), classes[i, k].long().cpu().numpy(), scores[i, k].cpu().numpy()))
+    return out
+
+
+def setup_detector(model_name="faster_rcnn", model_type="", pretrained=True, num_classes=1, **kwargs):
+    """lib/model_setup.py:60-95.  "efficientdet" with model_type "" / "d0" or "d3" builds the reference's configuration
+    (num_classes, its anchors, threshold 0.5, iou_threshold 0.5); weights come from a state_dict (load_state_dict)."""
+    if model_name not in ("faster_rcnn", "efficientdet"):
+        raise ValueError(f"setup_detector: model_name {model_name!r} (one of 'faster_rcnn', 'efficientdet')")
+    if model_type not in ("", "d0", "d3", None):
+        raise ValueError(f"setup_detector: model_type {model_type!r} (one of '', 'd0', 'd3')")
+    if model_name == "faster_rcnn":
+        raise NotImplementedError("setup_detector: 'faster_rcnn' is torchvision's fasterrcnn_resnet50_fpn, which is not part of the "
+                                  "reference's own code; use 'efficientdet'")
+    cc = 3 if model_type == "d3" else 0
+    return EfficientDetBackbone(compound_coef=cc, num_classes=num_classes, ratios=RATIOS, scales=SCALES, threshold=0.5,
+                                iou_threshold=0.5)

@@ -367,6 +367,59 @@ def _resize_argmax(heatmaps: torch.Tensor, ho: int, wo: int) -> Tuple[torch.Tens
 _define("heatmap_resize_argmax(Tensor heatmaps, int ho, int wo) -> (Tensor, Tensor, Tensor)", _resize_argmax,
         lambda hm, ho, wo: (hm.new_empty(hm.shape[:2], dtype=torch.int32), hm.new_empty(hm.shape[:2]), hm.new_empty(*hm.shape[:2], 2)))
 
+# ------------------------------------------------------------------ detector postprocess (efficientdet_utils/utils.py:150-187)
+def _det_decode(reg, cls, anchors, threshold: float, xmax: float, ymax: float):
+    if reg.dim() != 3 or reg.shape[2] != 4 or reg.dtype != torch.float32:
+        raise ValueError(f"stlpose det_decode: regression must be float32 [B, A, 4], got {reg.dtype} {tuple(reg.shape)}")
+    b, a = reg.shape[:2]
+    if cls.dim() != 3 or tuple(cls.shape[:2]) != (b, a) or cls.shape[2] < 1 or cls.dtype != torch.float32:
+        raise ValueError(f"stlpose det_decode: classification must be float32 [B={b}, A={a}, nc], got {cls.dtype} {tuple(cls.shape)}")
+    if tuple(anchors.shape[-2:]) != (a, 4) or anchors.numel() != a * 4 or anchors.dtype != torch.float32:
+        raise ValueError(f"stlpose det_decode: anchors must be float32 [A={a}, 4], got {anchors.dtype} {tuple(anchors.shape)}")
+    if not reg.is_cuda:
+        raise RuntimeError("stlpose det_decode: regression must be on the GPU")
+    _same_device((("classification", cls), ("anchors", anchors)), reg.device)
+    r, c, an = reg.contiguous(), cls.contiguous(), anchors.contiguous()
+    boxes = torch.empty(b, a, 4, device=reg.device)
+    scores = torch.empty(b, a, device=reg.device)
+    classes = torch.empty(b, a, dtype=torch.int32, device=reg.device)
+    index = torch.empty(b, a, dtype=torch.int32, device=reg.device)
+    count = torch.empty(b, dtype=torch.int32, device=reg.device)
+    capi.call("stl_det_decode", r.data_ptr(), c.data_ptr(), an.data_ptr(), b, a, c.shape[2], float(threshold), float(xmax), float(ymax),
+              boxes.data_ptr(), scores.data_ptr(), classes.data_ptr(), index.data_ptr(), count.data_ptr(), _st())
+    return boxes, scores, classes, index, count
+
+
+_define("det_decode(Tensor regression, Tensor classification, Tensor anchors, float threshold, float xmax, float ymax) "
+        "-> (Tensor, Tensor, Tensor, Tensor, Tensor)", _det_decode,
+        lambda r, c, a, t, xm, ym: (r.new_empty(r.shape), r.new_empty(r.shape[:2]), r.new_empty(r.shape[:2], dtype=torch.int32),
+                                    r.new_empty(r.shape[:2], dtype=torch.int32), r.new_empty(r.shape[0], dtype=torch.int32)))
+
+
+def _det_nms(boxes, classes, order, iou_thr: float):
+    if boxes.dim() != 2 or boxes.shape[1] != 4 or boxes.dtype != torch.float32:
+        raise ValueError(f"stlpose det_nms: boxes must be float32 [n, 4], got {boxes.dtype} {tuple(boxes.shape)}")
+    n = boxes.shape[0]
+    if n > capi.DET_NMS_MAX:
+        raise ValueError(f"stlpose det_nms: {n} candidates; the cap is {capi.DET_NMS_MAX} (STL_DET_NMS_MAX)")
+    for name, t in (("classes", classes), ("order", order)):
+        if t.dim() != 1 or t.shape[0] != n or t.dtype != torch.int32:
+            raise ValueError(f"stlpose det_nms: {name} must be int32 [n={n}], got {t.dtype} {tuple(t.shape)}")
+    if not boxes.is_cuda:
+        raise RuntimeError("stlpose det_nms: boxes must be on the GPU")
+    _same_device((("classes", classes), ("order", order)), boxes.device)
+    keep = torch.empty(n, dtype=torch.int32, device=boxes.device)
+    count = torch.empty(1, dtype=torch.int32, device=boxes.device)
+    work = torch.empty(max(1, int(capi.lib().stl_det_nms_workspace(n))), dtype=torch.uint8, device=boxes.device)
+    b, c, o = boxes.contiguous(), classes.contiguous(), order.contiguous()
+    capi.call("stl_det_nms", b.data_ptr(), c.data_ptr(), o.data_ptr(), n, float(iou_thr), work.data_ptr(), keep.data_ptr(),
+              count.data_ptr(), _st())
+    return keep, count
+
+
+_define("det_nms(Tensor boxes, Tensor classes, Tensor order, float iou_thr) -> (Tensor, Tensor)", _det_nms,
+        lambda b, c, o, t: (b.new_empty(b.shape[0], dtype=torch.int32), b.new_empty(1, dtype=torch.int32)))
+
 OPS = ["person_mse", "heatmap_argmax", "final_preds", "flip_merge", "flip_merge_backward", "gaussian_targets", "affine_crop",
        "hrnet_forward", "hrnet_backward", "hrnet_backward_input", "pose_vectors", "pose_distances", "pose_topk", "pose_rank",
-       "box_select", "heatmap_resize_argmax"]
+       "box_select", "heatmap_resize_argmax", "det_decode", "det_nms"]

@@ -175,3 +175,17 @@ def extract_retrieval_db(model, loader, flip=True, keypoint_thr=0.1, device=None
                                     "center": torch.Tensor(centers[p:p + 1]).float(), "scale": torch.Tensor(scales[p:p + 1]).float(),
                                     "character_name": meta["character_name"][p]}
     return db
+
+
+def detect_poses(detector, extractor: PoseExtractor, images, detector_thr=0.7, nms_thr=None) -> List[Dict]:
+    """04_evaluate_vases_qualitatively.py:184-250 from raw images: uint8 HWC RGB images (tensors or arrays) -> the EfficientDet
+    detector (preprocessed on the device from the same device images) -> bbox_filtering's person boxes (label 1, score >
+    detector_thr) -> ``extractor``.  Returns the extractor's dicts; only the detector's kept boxes and the poses reach the host."""
+    dev = torch.device("cuda", torch.cuda.current_device())
+    src = [_image(im, dev) for im in images]
+    if not src:
+        return []
+    p, metas = detector.run_raw(src, 0, dev)
+    dets = detector.detect(p, metas, detector.threshold, detector.iou_threshold)
+    return extractor(src, [d["boxes"].reshape(-1, 4) for d in dets], [d["scores"] for d in dets], [d["labels"].long() for d in dets],
+                     label=1, det_thr=detector_thr, nms_thr=nms_thr)
