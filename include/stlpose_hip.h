@@ -506,6 +506,36 @@ int stl_det_nms(const float* boxes, const int32_t* classes, const int32_t* order
                 int32_t* count, void* stream);
 int64_t stl_det_nms_workspace(int n);
 
+/* ---- AdaIN feed-forward stylisation (csrc/adain.hip; stlpose_amd/adain.py).  No reference counterpart: the network is the published
+ * one (Huang & Belongie 2017), restated in tests/adain_ref.py.  The 3x3 convs pad by reflection and stl_conv pads with zeros, so every
+ * conv runs as a "same" conv on an explicitly padded (H+2) x (W+2) NHWC map whose output ring is never read.  dtype STL_F32 or STL_BF16
+ * throughout; element indices are 32-bit (every tensor below 2^31 elements). */
+#define STL_GATHER_COPY 0
+#define STL_GATHER_UP 1   /* nn.Upsample(scale_factor=2, mode="nearest") */
+#define STL_GATHER_POOL 2 /* nn.MaxPool2d(2, 2), floor */
+/* img NCHW fp32 [B,3,H,W] -> out [B,H,W,32]: out[b,y,x,(ky*3+kx)*3+c] = img[b,c,reflect(y+ky-1,H),reflect(x+kx-1,W)], 0 for k >= 27
+ * (stl_patch3x3's column order, so conv1_1 is the same 1x1 conv with Ci = 32; no ring: every tap is a real pixel). */
+int stl_adain_input(int dtype, const float* img, void* out, int B, int H, int W, void* stream);
+/* Padded input of the next conv from the interior of the previous output.  src [B, Hs+2*ring, Ws+2*ring, C] whose interior Hs x Ws
+ * starts at (ring, ring), ring 0 or 1; v = op(src interior) is H x W = Hs x Ws (copy), 2Hs x 2Ws (up) or Hs/2 x Ws/2 (pool);
+ * out [B, H+2, W+2, C]: out[b,y,x,c] = v[b, reflect(y-1,H), reflect(x-1,W), c].  scale / offset fp32 [B,C] or both NULL: every
+ * loaded value becomes x * scale[b,c] + offset[b,c] (a multiply, then an add) before the op.  C % 8 == 0; H, W >= 2. */
+int stl_reflect_gather(int dtype, const void* src, void* out, int B, int Hs, int Ws, int ring, int C, int op, const float* scale,
+                       const float* offset, void* stream);
+/* Per (image, channel) statistics over the interior H x W of x [B, H+2*ring, W+2*ring, C]: mean, unbiased variance and
+ * sigma = sqrt(var + eps), each fp32 [B,C].  Sums and sums of squares in fp64, added in a fixed order (deterministic).
+ * partial: workspace of B * nchunk * 2 * C doubles; nchunk >= 1 workgroups share an image's pixels. */
+int stl_adain_stats(int dtype, const void* x, int B, int H, int W, int ring, int C, int nchunk, double* partial, float eps, float* mean,
+                    float* var, float* sigma, void* stream);
+/* AdaIN and the alpha blend as one affine of the content features: with m_s = sum_k weights[b,k] * mean_s[k,c] and s_s likewise from
+ * sigma_s (fp32 [S,C]; weights fp32 [B,S]), r = s_s / sqrt(var_c + eps): scale = alpha * r + (1 - alpha),
+ * offset = alpha * (m_s - mean_c * r), fp32 [B,C].  fp64 inside; alpha = 0 gives exactly (1, 0). */
+int stl_adain_affine(const float* mean_c, const float* var_c, const float* mean_s, const float* sigma_s, const float* weights, int B, int C,
+                     int S, float alpha, float eps, float* scale, float* offset, void* stream);
+/* Interior of the last conv's output x [B, H+2, W+2, C] (C = its Co padded to 8), channels 0..2 -> out NCHW fp32 [B,3,H,W];
+ * clamp != 0: to [0, 1]. */
+int stl_adain_output(int dtype, const void* x, float* out, int B, int H, int W, int C, int clamp, void* stream);
+
 const char* stl_last_error(void);
 int stl_version(void);
 /* Hash (16 hex digits) of the kernel and header sources this library was compiled from (stlpose_amd/build.py). */

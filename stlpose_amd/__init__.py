@@ -16,3 +16,5 @@ from .bounding_box import (bbox_filtering, bbox_nms, get_detections, reshape_det
 from .topdown import TransformDetection, PoseExtractor, extract_retrieval_db  # noqa: F401,E402
 from .efficientdet import EfficientDetBackbone, EfficientDet, setup_detector  # noqa: F401,E402
 from .topdown import detect_poses  # noqa: F401,E402
+from .adain import AdaINStylizer  # noqa: F401,E402
+from .styled_coco import create_styled_dataset  # noqa: F401,E402

@@ -29,6 +29,8 @@ POSE_TOPK_MAX, POSE_RANK_MAX, POSE_RANK_LABELS_MAX, POSE_NSCORES = 1024, 16384, 
 BOX_MAX, RESIZE_SRC_MAX, RESIZE_DST_MAX = 4096, 16384, 2048
 # person detector (STL_DET_NMS_MAX)
 DET_NMS_MAX = 65536
+# AdaIN gather ops (STL_GATHER_*)
+GATHER_COPY, GATHER_UP, GATHER_POOL = 0, 1, 2
 
 MIXED = dt2(BF16, F16)   # the mixed 16-bit mode: forward tensors f16, gradients bf16
 NSHARD = 2
@@ -211,6 +213,11 @@ SIGNATURES = {
     "stl_det_decode": [vp, vp, vp, i32, i32, i32, f32, f32, f32, vp, vp, vp, vp, vp, vp],
     "stl_det_nms": [vp, vp, vp, i32, C.c_double, vp, vp, vp, vp],
     "stl_det_nms_workspace": [i32],
+    "stl_adain_input": [i32, vp, vp, i32, i32, i32, vp],
+    "stl_reflect_gather": [i32, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp],
+    "stl_adain_stats": [i32, vp, i32, i32, i32, i32, i32, i32, vp, f32, vp, vp, vp, vp],
+    "stl_adain_affine": [vp, vp, vp, vp, vp, i32, i32, i32, f32, f32, vp, vp, vp],
+    "stl_adain_output": [i32, vp, vp, i32, i32, i32, i32, i32, vp],
     "stl_version": [],
 }
 
