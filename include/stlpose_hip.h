@@ -430,7 +430,9 @@ int stl_heatmap_resize_argmax(const float* hm, int BJ, int H, int W, int Ho, int
                               void* stream);
 
 /* ---- EfficientDet person detector (stlpose_amd/csrc/detector.hip): src/models/EfficientDet.py with
- * models/efficientdet_utils/{model,utils}.py and models/efficientnet/{model,utils,utils_extra}.py, inference only, fp32, NHWC activations. */
+ * models/efficientdet_utils/{model,utils}.py and models/efficientnet/{model,utils,utils_extra}.py, inference only, NHWC activations.
+ * The stl_det_* entry points without a suffix are the fp32 path.  The *16 entry points further down are the 16-bit compute modes
+ * (EfficientDetBackbone(compute_dtype="bf16" | "f16")): activations stored as STL_BF16 or STL_F16, every sum in fp32. */
 #define STL_DET_NMS_MAX 65536      /* candidates per image of stl_det_nms (all 49104 anchors of a 512 canvas fit) */
 
 /* One source image of stl_det_preprocess.  kind 0: uint8 HWC RGB (divided by 255), 1: float CHW in [0, 1]; new_h / new_w from
@@ -491,6 +493,42 @@ typedef struct {
     float* out;
 } StlDetFuse;
 int stl_det_fuse(const StlDetFuse* f, void* stream);
+
+/* -- 16-bit compute modes.  dtype is STL_BF16 or STL_F16 (anything else is an error).  Every 16-bit tensor is NHWC with C % 8 == 0
+ * (true of every tensor the network stores: the B0 / B3 widths and expansions, BiFPN 64 / 160): one 16-byte access moves 8 channels,
+ * and any other C is an error ("... C % 8 == 0" in stl_last_error) before anything is launched.  Tensors and the fp32 weight,
+ * bias and scale arrays must be 16-byte aligned.  Sums, depthwise weights, biases, the SE and attention arithmetic are fp32; a value is
+ * rounded to dtype once, when it is stored.  f16 activations past 65504 become inf: the model's f16 mode checks its head outputs. */
+/* stl_det_stem with a dtype output: x fp32 [B, H, W, 3] -> out dtype [B, ceil(H/2), ceil(W/2), Co]. */
+int stl_det_stem16(int dtype, const float* x, const float* w, const float* bias, void* out, int B, int H, int W, int Co, void* stream);
+/* stl_det_dwconv on dtype tensors, w [k][k][C] and bias [C] (or NULL) fp32, 8 channels per thread.  partial non-NULL (the MBConv
+ * case): also writes the squeeze-excitation pooling sums partial[B][stl_det_dw16_parts(Ho * Wo)][C], one slot per workgroup of
+ * pixels: the sum of that workgroup's fp32 outputs before rounding, added in a fixed order (no atomics); every slot is written. */
+int stl_det_dwconv16(int dtype, const void* x, const float* w, const float* bias, void* out, float* partial, int B, int H, int W, int C,
+                     int k, int s, int act, void* stream);
+int stl_det_dw16_parts(int HoWo);
+/* stl_det_se from pooling sums: partial [B][nparts][C] is added in slot order and divided by HW; scale fp32 [B, C] as stl_det_se. */
+int stl_det_se16(const float* partial, int B, int HW, int nparts, int C, int Cs, const float* w1, const float* b1, const float* w2,
+                 const float* b2, float* scale, void* stream);
+/* stl_det_pointwise on v_mfma_f32_16x16x32_{bf16,f16}, fp32 accumulation.  x dtype [M, Ci], Ci % 8 == 0.  w dtype, packed
+ * [Np / 16][Kp / 32][64][8]: element ((nt * (Kp / 32) + ks) * 64 + 16 * g + r) * 8 + i is w[k = 32 ks + 8 g + i][n = 16 nt + r],
+ * zero-padded to Kp % 32 == 0, Np % 64 == 0.  bias fp32 [Np] or NULL.  in_scale fp32 [B, Ci] or NULL: x * in_scale in fp32, rounded
+ * once to dtype.  residual dtype [M, Co] or NULL.  out_f32 0: out dtype (Co, strides and offset multiples of 4: the 4 channels a
+ * lane holds are one 8-byte store); out_f32 1: out fp32 with any Co, strides and offset (the head headers writing into reg / cls).
+ * MI355X, batch 32: the 16-bit forward takes 5.2 ms (D0) / 11.7 ms (D3) against 14.3 / 34.2 ms in fp32 (profiles/detector_bench.json). */
+typedef struct {
+    const void* x;
+    const void* w;
+    const float* bias;
+    const float* in_scale;
+    const void* residual;
+    void* out;
+    int64_t M, out_img_stride, out_row_stride, out_off;
+    int32_t HW, Ci, Co, Kp, Np, act, dtype, out_f32;
+} StlDetPointwise16;
+int stl_det_pointwise16(const StlDetPointwise16* p, void* stream);
+/* stl_det_fuse on dtype tensors (t[i].x and out point at dtype elements), the attention weights fp32, 8 channels per thread. */
+int stl_det_fuse16(const StlDetFuse* f, int dtype, void* stream);
 
 /* postprocess up to the NMS (efficientdet_utils/utils.py:14-56, 150-168): per image, score = max over the nc classes (first
  * maximum), kept when score > thr; BBoxTransform (exp) on anchors fp32 [A][4] (y1, x1, y2, x2) and reg [B, A, 4] (dy, dx, dh, dw);

@@ -126,6 +126,12 @@ class DetPointwise(C.Structure):
                 ("Kp", i32), ("Np", i32), ("act", i32)]
 
 
+class DetPointwise16(C.Structure):
+    _fields_ = [("x", vp), ("w", vp), ("bias", vp), ("in_scale", vp), ("residual", vp), ("out", vp), ("M", i64),
+                ("out_img_stride", i64), ("out_row_stride", i64), ("out_off", i64), ("HW", i32), ("Ci", i32), ("Co", i32),
+                ("Kp", i32), ("Np", i32), ("act", i32), ("dtype", i32), ("out_f32", i32)]
+
+
 class DetTerm(C.Structure):
     _fields_ = [("x", vp), ("mode", i32), ("H", i32), ("W", i32), ("pad_", i32)]
 
@@ -210,6 +216,12 @@ SIGNATURES = {
     "stl_det_se_workspace": [i32],
     "stl_det_pointwise": [C.POINTER(DetPointwise), vp],
     "stl_det_fuse": [C.POINTER(DetFuse), vp],
+    "stl_det_stem16": [i32, vp, vp, vp, vp, i32, i32, i32, i32, vp],
+    "stl_det_dwconv16": [i32, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp],
+    "stl_det_dw16_parts": [i32],
+    "stl_det_se16": [vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp],
+    "stl_det_pointwise16": [C.POINTER(DetPointwise16), vp],
+    "stl_det_fuse16": [C.POINTER(DetFuse), i32, vp],
     "stl_det_decode": [vp, vp, vp, i32, i32, i32, f32, f32, f32, vp, vp, vp, vp, vp, vp],
     "stl_det_nms": [vp, vp, vp, i32, C.c_double, vp, vp, vp, vp],
     "stl_det_nms_workspace": [i32],

@@ -1,4 +1,4 @@
-// EfficientDet person detector on gfx950, fp32, NHWC (src/models/EfficientDet.py and models/efficientdet_utils/*,
+// EfficientDet person detector on gfx950, NHWC (src/models/EfficientDet.py and models/efficientdet_utils/*,
 // models/efficientnet/{model,utils,utils_extra}.py): preprocess, the MBConv backbone, BiFPN and the shared heads, anchor decode and class-aware NMS.
 //
 //   stl_det_preprocess  normalise + aspect-aware bilinear resize + zero canvas (efficientdet_utils/utils.py:190-239)
@@ -11,6 +11,21 @@
 //                       fast-attention weights normalised on the device (efficientdet_utils/model.py:163-233)
 //   stl_det_decode      per-anchor class max, strict threshold, BBoxTransform, ClipBoxes, compaction in anchor order
 //   stl_det_nms         torchvision.ops.batched_nms (0.4: class offsets, then nms) over any number of candidates
+//
+// The 16-bit compute modes (EfficientDetBackbone(compute_dtype="bf16" | "f16")) have entry points of their own; activations
+// are stored as STL_BF16 / STL_F16 with C % 8 == 0 (8 channels per 16-byte access, any other C is an error), sums are fp32:
+//
+//   stl_det_stem16       fp32 canvas in, 16-bit out
+//   stl_det_dwconv16     8 channels per thread; on request also the squeeze-excitation pooling sums, one slot per workgroup
+//                        of pixels, taken from the fp32 values before rounding (a 16-bit plan has no pooling pass)
+//   stl_det_se16         stl_det_se from those sums, added in slot order
+//   stl_det_pointwise16  the GEMM on v_mfma_f32_16x16x32_{bf16,f16}, operands straight from global memory (no LDS): an NHWC
+//                        row is the operand layout, the weights are packed to one 16-byte load per lane; 16-bit or strided fp32 output
+//   stl_det_fuse16       the BiFPN node on 16-bit tensors, attention weights fp32
+//
+// f16 activations past 65504 become inf; the model checks its head outputs (FloatingPointError) and points to bf16.  On the
+// MI355X the 16-bit forwards take 5.2 ms (D0) and 11.7 ms (D3) at batch 32 against 14.3 and 34.2 ms in fp32
+// (profiles/detector_bench.json).
 //
 // Every reduction runs in a fixed order (no float atomics): two runs give bitwise equal results.
 #include "common.cuh"
@@ -152,7 +167,8 @@ __global__ __launch_bounds__(256) void se_pool_kernel(const float* __restrict__ 
 }
 
 // one workgroup per image: mean -> reduce (w1 [Cs][C] + b1) -> swish -> expand (w2 [C][Cs] + b2) -> sigmoid
-__global__ __launch_bounds__(256) void se_kernel(const float* __restrict__ partial, int HW, int C, int Cs, const float* __restrict__ w1,
+// partial [B][nparts][C], added in slot order
+__global__ __launch_bounds__(256) void se_kernel(const float* __restrict__ partial, int nparts, int HW, int C, int Cs, const float* __restrict__ w1,
                                                  const float* __restrict__ b1, const float* __restrict__ w2, const float* __restrict__ b2,
                                                  float* __restrict__ scale) {
     extern __shared__ float sm[];   // mean [C] | hidden [Cs]
@@ -161,7 +177,8 @@ __global__ __launch_bounds__(256) void se_kernel(const float* __restrict__ parti
     const int b = blockIdx.x;
     for (int c = threadIdx.x; c < C; c += 256) {
         float acc = 0.f;
-        for (int sp = 0; sp < kSeSplit; ++sp) acc += partial[((int64_t)b * kSeSplit + sp) * C + c];
+#pragma unroll 8
+        for (int sp = 0; sp < nparts; ++sp) acc += partial[((int64_t)b * nparts + sp) * C + c];
         mean[c] = acc / (float)HW;
     }
     __syncthreads();
@@ -444,6 +461,277 @@ __global__ __launch_bounds__(64) void nms_sweep_kernel(const unsigned long long*
     if (lane == 0) *count = kept;
 }
 
+// ================================================================================================ 16-bit compute modes
+// T = __bf16 or f16.  Activations are stored in T, NHWC, with C % 8 == 0, so that one 16-byte access moves 8 channels of a
+// pixel; every sum, every weight but the pointwise ones, every bias and the SE / attention arithmetic are fp32, and a value
+// is rounded to T once, when it is stored.
+
+// fp32 canvas [B, H, W, 3] -> T [B, Ho, Wo, Co]; one thread per (pixel, 8 channels)
+template <typename T>
+__global__ __launch_bounds__(256) void stem16_kernel(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ bias,
+                                                     T* __restrict__ out, int B, int H, int W, int Ho, int Wo, int Co) {
+    const int C8 = Co >> 3;
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= (int64_t)B * Ho * Wo * C8) return;
+    const int c0 = (int)(e % C8) * 8;
+    const int64_t pix = e / C8;
+    const int ox = (int)(pix % Wo), oy = (int)((pix / Wo) % Ho), b = (int)(pix / ((int64_t)Wo * Ho));
+    const int py = same_pad_before(H, 3, 2), px = same_pad_before(W, 3, 2);
+    float acc[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) acc[j] = 0.f;
+    for (int ky = 0; ky < 3; ++ky) {
+        const int iy = oy * 2 - py + ky;
+        if (iy < 0 || iy >= H) continue;
+        for (int kx = 0; kx < 3; ++kx) {
+            const int ix = ox * 2 - px + kx;
+            if (ix < 0 || ix >= W) continue;
+            const float* xp = x + (((int64_t)b * H + iy) * W + ix) * 3;
+            const float* wp = w + ((ky * 3 + kx) * 3) * Co + c0;
+            float wa[8], wb[8], wc[8];
+            unpack<float>(ldg16(wp), wa), unpack<float>(ldg16(wp + 4), wa + 4);
+            unpack<float>(ldg16(wp + Co), wb), unpack<float>(ldg16(wp + Co + 4), wb + 4);
+            unpack<float>(ldg16(wp + 2 * Co), wc), unpack<float>(ldg16(wp + 2 * Co + 4), wc + 4);
+            const float x0 = xp[0], x1 = xp[1], x2 = xp[2];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) acc[j] += x0 * wa[j] + x1 * wb[j] + x2 * wc[j];
+        }
+    }
+    float bv[8];
+    unpack<float>(ldg16(bias + c0), bv), unpack<float>(ldg16(bias + c0 + 4), bv + 4);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) acc[j] = swishf(acc[j] + bv[j]);
+    stg16(out + pix * Co + c0, pack<T>(acc));
+}
+
+// Depthwise: a workgroup is 8 channel groups (64 channels) x 32 pixel lanes of one image and walks `iters` rows of 32 pixels,
+// so a slab of 64 channels of a pixel is one 128-byte run.  POOL: the workgroup also writes partial[b][blockIdx.x][c], the
+// sum of its fp32 outputs before rounding: each thread adds its pixels in pixel order, then one thread per channel adds the 32
+// pixel lanes in lane order (lanes and iterations past the last pixel add nothing).  stl_det_se16 adds the slots in order.
+constexpr int kDwCG = 8, kDwPL = 32, kDwMaxParts = 64;
+static inline int dw16_iters(int HW) { return HW > kDwPL * kDwMaxParts ? ceil_div(HW, kDwPL * kDwMaxParts) : 1; }
+static inline int dw16_parts(int HW) { return ceil_div(HW, kDwPL * dw16_iters(HW)); }
+
+template <typename T, int K, bool POOL>
+__global__ __launch_bounds__(256) void dwconv16_kernel(const T* __restrict__ x, const float* __restrict__ w, const float* __restrict__ bias,
+                                                       T* __restrict__ out, float* __restrict__ partial, int H, int W, int C, int s,
+                                                       int Ho, int Wo, int act, int iters, int nparts) {
+    __shared__ float red[POOL ? kDwPL : 1][kDwCG * 8 + 1];
+    const int cl = threadIdx.x & (kDwCG - 1), pl = threadIdx.x / kDwCG;
+    const int c0 = (blockIdx.y * kDwCG + cl) * 8;
+    const int b = blockIdx.z;
+    const bool cok = c0 < C;   // C % 8 == 0: a group of 8 is inside or outside as a whole
+    const int py = same_pad_before(H, K, s), px = same_pad_before(W, K, s);
+    const int HW = Ho * Wo;
+    float bv[8], psum[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) bv[j] = psum[j] = 0.f;
+    if (cok && bias) unpack<float>(ldg16(bias + c0), bv), unpack<float>(ldg16(bias + c0 + 4), bv + 4);
+    for (int it = 0; it < iters; ++it) {
+        const int p = (blockIdx.x * iters + it) * kDwPL + pl;
+        if (!cok || p >= HW) continue;
+        const int oy = p / Wo, ox = p - oy * Wo;
+        const int y0 = oy * s - py, x0 = ox * s - px;
+        float acc[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) acc[j] = 0.f;
+#pragma unroll
+        for (int ky = 0; ky < K; ++ky) {
+            const int iy = y0 + ky;
+            if (iy < 0 || iy >= H) continue;
+#pragma unroll
+            for (int kx = 0; kx < K; ++kx) {
+                const int ix = x0 + kx;
+                if (ix < 0 || ix >= W) continue;
+                float f[8], wf[8];
+                unpack<T>(ldg16(x + (((int64_t)b * H + iy) * W + ix) * C + c0), f);
+                const float* wp = w + (ky * K + kx) * C + c0;
+                unpack<float>(ldg16(wp), wf), unpack<float>(ldg16(wp + 4), wf + 4);
+#pragma unroll
+                for (int j = 0; j < 8; ++j) acc[j] += f[j] * wf[j];
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            acc[j] += bv[j];
+            if (act == 1) acc[j] = swishf(acc[j]);
+            if (POOL) psum[j] += acc[j];
+        }
+        stg16(out + ((int64_t)b * HW + p) * C + c0, pack<T>(acc));
+    }
+    if constexpr (POOL) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) red[pl][cl * 8 + j] = psum[j];
+        __syncthreads();
+        const int c = blockIdx.y * kDwCG * 8 + threadIdx.x;
+        if (threadIdx.x < kDwCG * 8 && c < C) {
+            float a = 0.f;
+            for (int q = 0; q < kDwPL; ++q) a += red[q][threadIdx.x];
+            partial[((int64_t)b * nparts + blockIdx.x) * C + c] = a;
+        }
+    }
+}
+
+// Pointwise GEMM on v_mfma_f32_16x16x32_{bf16,f16}, no LDS.  The weights are the MFMA's A operand and the pixels its B operand,
+// so a lane ends up with 4 consecutive output channels of one pixel (D: row = 4 * (lane >> 4) + r is the channel, col =
+// lane & 15 the pixel) and stores them as one 8-byte (T) or 16-byte-wide (fp32) piece of an NHWC row.  An NHWC row is already
+// the operand layout: lane l loads the 8 channels k0 + 8 * (l >> 4) .. + 7 of pixel l & 15 in one 16-byte load (zero past M or
+// Ci; Ci % 8 == 0, so a group of 8 never straddles the end of a row).  w is packed [Np / 16][Kp / 32][64 lanes][8]: one
+// coalesced 16-byte load per lane and 16 x 32 tile, zero-padded to Kp % 32 == 0 and Np % 64 == 0.  A wave owns 32 pixels x 64
+// channels (8 accumulators), a workgroup 128 pixels.
+constexpr int kPw16M = 128, kPw16N = 64;
+
+template <typename T, bool F32OUT>
+__global__ __launch_bounds__(256) void pointwise16_kernel(const StlDetPointwise16 p) {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, g = lane >> 4;
+    const int ksteps = p.Kp >> 5;
+    const T* x = reinterpret_cast<const T*>(p.x);
+    int64_t row[2];
+    bool ok[2];
+    const T* xr[2];
+    const float* sr[2];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        row[h] = (int64_t)blockIdx.x * kPw16M + wv * 32 + h * 16 + (lane & 15);
+        ok[h] = row[h] < p.M;
+        xr[h] = x + (ok[h] ? row[h] : 0) * (int64_t)p.Ci;
+        sr[h] = p.in_scale ? p.in_scale + (ok[h] ? row[h] / p.HW : 0) * (int64_t)p.Ci : nullptr;
+    }
+    f32x4 acc[2][4];
+#pragma unroll
+    for (int h = 0; h < 2; ++h)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[h][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    const V16* wp = reinterpret_cast<const V16*>(p.w) + (int64_t)blockIdx.y * 4 * ksteps * 64 + lane;
+    for (int ks = 0; ks < ksteps; ++ks) {
+        const int k = ks * 32 + g * 8;
+        V16 a[2];
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            a[h] = zero16();
+            if (ok[h] && k < p.Ci) {
+                a[h] = ldg16(xr[h] + k);
+                if (p.in_scale) {   // the SE scale: multiplied in fp32, rounded once to the operand type
+                    float f[8], sc[8];
+                    unpack<T>(a[h], f);
+                    unpack<float>(ldg16(sr[h] + k), sc), unpack<float>(ldg16(sr[h] + k + 4), sc + 4);
+#pragma unroll
+                    for (int i = 0; i < 8; ++i) f[i] *= sc[i];
+                    a[h] = pack<T>(f);
+                }
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const V16 bw = wp[((int64_t)j * ksteps + ks) * 64];
+#pragma unroll
+            for (int h = 0; h < 2; ++h) mma16<T>(acc[h][j], bw, a[h]);
+        }
+    }
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        if (!ok[h]) continue;
+        const int64_t m = row[h];
+        const int64_t img = m / p.HW, pix = m - img * p.HW;
+        const int64_t obase = img * p.out_img_stride + pix * p.out_row_stride + p.out_off;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int n = blockIdx.y * kPw16N + j * 16 + g * 4;
+            if (n >= p.Co) continue;
+            float bv[4] = {0.f, 0.f, 0.f, 0.f}, v[4];
+            if (p.bias) unpack<float>(ldg16(p.bias + n), bv);   // bias is padded to Np
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                v[r] = acc[h][j][r] + bv[r];
+                if (p.act == 1) v[r] = swishf(v[r]);
+                else if (p.act == 2) v[r] = sigmoidf_(v[r]);
+            }
+            if constexpr (F32OUT) {   // any Co, any strides: element stores
+                float* o = reinterpret_cast<float*>(p.out) + obase + n;
+                const T* rs = reinterpret_cast<const T*>(p.residual) + m * p.Co + n;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    if (n + r >= p.Co) break;
+                    o[r] = p.residual ? v[r] + (float)rs[r] : v[r];
+                }
+            } else {   // Co % 4 == 0: the 4 channels are inside and 8-byte aligned
+                if (p.residual) {
+                    const uint2 rv = *reinterpret_cast<const uint2*>(reinterpret_cast<const T*>(p.residual) + m * p.Co + n);
+                    float q[4];
+                    unpack2<T>(rv.x, q[0], q[1]), unpack2<T>(rv.y, q[2], q[3]);
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) v[r] += q[r];
+                }
+                uint2 ov;
+                ov.x = pack2<T>(v[0], v[1]), ov.y = pack2<T>(v[2], v[3]);
+                *reinterpret_cast<uint2*>(reinterpret_cast<T*>(p.out) + obase + n) = ov;
+            }
+        }
+    }
+}
+
+// BiFPN node, 8 channels per thread
+template <typename T>
+__device__ __forceinline__ void fuse_read16(const StlDetTerm& t, int b, int y, int x, int c0, int C, float* f) {
+    const T* src = reinterpret_cast<const T*>(t.x);
+    if (t.mode == 0) return unpack<T>(ldg16(src + (((int64_t)b * t.H + y) * t.W + x) * C + c0), f);
+    if (t.mode == 1) return unpack<T>(ldg16(src + (((int64_t)b * t.H + (y >> 1)) * t.W + (x >> 1)) * C + c0), f);
+    const int py = same_pad_before(t.H, 3, 2), px = same_pad_before(t.W, 3, 2);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) f[j] = -INFINITY;
+    for (int ky = 0; ky < 3; ++ky) {
+        const int iy = y * 2 - py + ky;
+        for (int kx = 0; kx < 3; ++kx) {
+            const int ix = x * 2 - px + kx;
+            float v[8];
+            if (iy < 0 || iy >= t.H || ix < 0 || ix >= t.W) {   // padded taps read 0
+#pragma unroll
+                for (int j = 0; j < 8; ++j) v[j] = 0.f;
+            } else {
+                unpack<T>(ldg16(src + (((int64_t)b * t.H + iy) * t.W + ix) * C + c0), v);
+            }
+#pragma unroll
+            for (int j = 0; j < 8; ++j) f[j] = v[j] > f[j] ? v[j] : f[j];
+        }
+    }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void fuse16_kernel(const StlDetFuse f) {
+    const int C8 = f.C >> 3;
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= (int64_t)f.B * f.H * f.W * C8) return;
+    const int c0 = (int)(e % C8) * 8;
+    const int64_t pix = e / C8;
+    const int x = (int)(pix % f.W), y = (int)((pix / f.W) % f.H), b = (int)(pix / ((int64_t)f.W * f.H));
+    T* o = reinterpret_cast<T*>(f.out) + pix * f.C + c0;
+    float acc[8], v[8];
+    if (!f.wparam) {
+        fuse_read16<T>(f.t[0], b, y, x, c0, f.C, acc);
+        stg16(o, pack<T>(acc));
+        return;
+    }
+    float w[3], s = 0.f;
+    for (int i = 0; i < f.nterms; ++i) {
+        w[i] = f.wparam[i] > 0.f ? f.wparam[i] : 0.f;
+        s += w[i];
+    }
+    s += 1e-4f;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) acc[j] = 0.f;
+    for (int i = 0; i < f.nterms; ++i) {
+        fuse_read16<T>(f.t[i], b, y, x, c0, f.C, v);
+        const float wi = w[i] / s;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) acc[j] += wi * v[j];
+    }
+#pragma unroll
+    for (int j = 0; j < 8; ++j) acc[j] = swishf(acc[j]);
+    stg16(o, pack<T>(acc));
+}
+
+__host__ inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
 }  // namespace
 
 #define ST ((hipStream_t)stream)
@@ -488,7 +776,7 @@ extern "C" int stl_det_se(const float* x, int B, int HW, int C, int Cs, const fl
     STL_CHECK(x && w1 && b1 && w2 && b2 && partial && scale, "det_se: null pointer");
     STL_LAUNCH(se_pool_kernel, dim3(kSeSplit, B), dim3(256), 0, ST, x, HW, C, partial);
     STL_LAUNCH_CHECK("det_se_pool");
-    STL_LAUNCH(se_kernel, dim3(B), dim3(256), (size_t)(C + Cs) * 4, ST, partial, HW, C, Cs, w1, b1, w2, b2, scale);
+    STL_LAUNCH(se_kernel, dim3(B), dim3(256), (size_t)(C + Cs) * 4, ST, (const float*)partial, kSeSplit, HW, C, Cs, w1, b1, w2, b2, scale);
     STL_LAUNCH_CHECK("det_se");
     return 0;
 }
@@ -523,6 +811,118 @@ extern "C" int stl_det_fuse(const StlDetFuse* f, void* stream) {
     const int64_t n = (int64_t)f->B * f->H * f->W * f->C;
     STL_LAUNCH(fuse_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ST, *f);
     STL_LAUNCH_CHECK("det_fuse");
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------ 16-bit entry points
+#define DET16_DTYPE(name, dtype) STL_CHECK((dtype) == STL_BF16 || (dtype) == STL_F16, name ": dtype %d (STL_BF16 or STL_F16)", (int)(dtype))
+#define DET16_C8(name, C) STL_CHECK((C) >= 8 && (C) % 8 == 0, name ": C %d (16-bit tensors need C %% 8 == 0)", (int)(C))
+
+extern "C" int stl_det_stem16(int dtype, const float* x, const float* w, const float* bias, void* out, int B, int H, int W, int Co,
+                              void* stream) {
+    DET16_DTYPE("det_stem16", dtype);
+    STL_CHECK(B >= 1 && H >= 1 && W >= 1, "det_stem16: B %d, %d x %d", B, H, W);
+    DET16_C8("det_stem16", Co);
+    STL_CHECK(x && w && bias && out, "det_stem16: null pointer");
+    STL_CHECK(al16(w) && al16(bias) && al16(out), "det_stem16: w, bias and out must be 16-byte aligned");
+    const int Ho = (H + 1) / 2, Wo = (W + 1) / 2;
+    const int64_t n = (int64_t)B * Ho * Wo * (Co / 8);
+    STL_CHECK(n < (1ll << 31) * 256, "det_stem16: too large");
+    const dim3 grid((unsigned)((n + 255) / 256));
+    if (dtype == STL_BF16) STL_LAUNCH(stem16_kernel<__bf16>, grid, dim3(256), 0, ST, x, w, bias, (__bf16*)out, B, H, W, Ho, Wo, Co);
+    else STL_LAUNCH(stem16_kernel<f16>, grid, dim3(256), 0, ST, x, w, bias, (f16*)out, B, H, W, Ho, Wo, Co);
+    STL_LAUNCH_CHECK("det_stem16");
+    return 0;
+}
+
+extern "C" int stl_det_dw16_parts(int HoWo) { return HoWo >= 1 ? dw16_parts(HoWo) : 0; }
+
+template <typename T>
+static int dwconv16_launch(const void* x, const float* w, const float* bias, void* out, float* partial, int B, int H, int W, int C, int k,
+                           int s, int act, hipStream_t st) {
+    const int Ho = (H + s - 1) / s, Wo = (W + s - 1) / s;
+    const int iters = dw16_iters(Ho * Wo), nparts = dw16_parts(Ho * Wo);
+    const dim3 grid(nparts, ceil_div(C / 8, kDwCG), B);
+    const T* xi = (const T*)x;
+    T* o = (T*)out;
+    if (k == 3 && partial) STL_LAUNCH((dwconv16_kernel<T, 3, true>), grid, dim3(256), 0, st, xi, w, bias, o, partial, H, W, C, s, Ho, Wo, act, iters, nparts);
+    else if (k == 3) STL_LAUNCH((dwconv16_kernel<T, 3, false>), grid, dim3(256), 0, st, xi, w, bias, o, partial, H, W, C, s, Ho, Wo, act, iters, nparts);
+    else if (partial) STL_LAUNCH((dwconv16_kernel<T, 5, true>), grid, dim3(256), 0, st, xi, w, bias, o, partial, H, W, C, s, Ho, Wo, act, iters, nparts);
+    else STL_LAUNCH((dwconv16_kernel<T, 5, false>), grid, dim3(256), 0, st, xi, w, bias, o, partial, H, W, C, s, Ho, Wo, act, iters, nparts);
+    return 0;
+}
+
+extern "C" int stl_det_dwconv16(int dtype, const void* x, const float* w, const float* bias, void* out, float* partial, int B, int H,
+                                int W, int C, int k, int s, int act, void* stream) {
+    DET16_DTYPE("det_dwconv16", dtype);
+    STL_CHECK(B >= 1 && B <= 65535 && H >= 1 && W >= 1 && H <= 32768 && W <= 32768, "det_dwconv16: B %d, %d x %d", B, H, W);
+    DET16_C8("det_dwconv16", C);
+    STL_CHECK((k == 3 || k == 5) && (s == 1 || s == 2), "det_dwconv16: k %d s %d (k in {3, 5}, s in {1, 2})", k, s);
+    STL_CHECK(x && w && out, "det_dwconv16: null pointer");
+    STL_CHECK(al16(x) && al16(w) && al16(bias) && al16(out), "det_dwconv16: x, w, bias and out must be 16-byte aligned");
+    STL_CHECK(C / 8 <= 65535 * kDwCG, "det_dwconv16: C %d", C);
+    if (dtype == STL_BF16) dwconv16_launch<__bf16>(x, w, bias, out, partial, B, H, W, C, k, s, act, ST);
+    else dwconv16_launch<f16>(x, w, bias, out, partial, B, H, W, C, k, s, act, ST);
+    STL_LAUNCH_CHECK("det_dwconv16");
+    return 0;
+}
+
+extern "C" int stl_det_se16(const float* partial, int B, int HW, int nparts, int C, int Cs, const float* w1, const float* b1,
+                            const float* w2, const float* b2, float* scale, void* stream) {
+    STL_CHECK(B >= 1 && HW >= 1 && nparts >= 1 && C >= 1 && C <= 8192 && Cs >= 1 && Cs <= 1024, "det_se16: B %d HW %d parts %d C %d Cs %d",
+              B, HW, nparts, C, Cs);
+    STL_CHECK(partial && w1 && b1 && w2 && b2 && scale, "det_se16: null pointer");
+    STL_LAUNCH(se_kernel, dim3(B), dim3(256), (size_t)(C + Cs) * 4, ST, partial, nparts, HW, C, Cs, w1, b1, w2, b2, scale);
+    STL_LAUNCH_CHECK("det_se16");
+    return 0;
+}
+
+extern "C" int stl_det_pointwise16(const StlDetPointwise16* p, void* stream) {
+    STL_CHECK(p && p->x && p->w && p->out, "det_pointwise16: null pointer");
+    DET16_DTYPE("det_pointwise16", p->dtype);
+    STL_CHECK(p->M >= 1 && p->HW >= 1 && p->Co >= 1, "det_pointwise16: M %lld HW %d Co %d", (long long)p->M, p->HW, p->Co);
+    STL_CHECK(p->Ci >= 8 && p->Ci % 8 == 0, "det_pointwise16: Ci %d (16-bit tensors need C %% 8 == 0)", p->Ci);
+    STL_CHECK(p->Np % kPw16N == 0 && p->Np >= p->Co && p->Kp % 32 == 0 && p->Kp >= p->Ci, "det_pointwise16: packed %d x %d for %d x %d",
+              p->Kp, p->Np, p->Ci, p->Co);
+    STL_CHECK(p->act >= 0 && p->act <= 2, "det_pointwise16: act %d", p->act);
+    STL_CHECK(al16(p->x) && al16(p->w) && al16(p->bias) && al16(p->in_scale), "det_pointwise16: x, w, bias and in_scale must be 16-byte aligned");
+    if (!p->out_f32)   // 4 channels of a pixel are one 8-byte store
+        STL_CHECK(p->Co % 4 == 0 && p->out_img_stride % 4 == 0 && p->out_row_stride % 4 == 0 && p->out_off % 4 == 0 && ((uintptr_t)p->out & 7) == 0 &&
+                      ((uintptr_t)p->residual & 7) == 0,
+                  "det_pointwise16: a 16-bit output needs Co %d, strides and offset that are multiples of 4 and 8-byte aligned pointers", p->Co);
+    const int64_t mb = (p->M + kPw16M - 1) / kPw16M;
+    STL_CHECK(mb < (1ll << 31), "det_pointwise16: M too large");
+    const dim3 grid((unsigned)mb, p->Np / kPw16N);
+    if (p->dtype == STL_BF16) {
+        if (p->out_f32) STL_LAUNCH((pointwise16_kernel<__bf16, true>), grid, dim3(256), 0, ST, *p);
+        else STL_LAUNCH((pointwise16_kernel<__bf16, false>), grid, dim3(256), 0, ST, *p);
+    } else {
+        if (p->out_f32) STL_LAUNCH((pointwise16_kernel<f16, true>), grid, dim3(256), 0, ST, *p);
+        else STL_LAUNCH((pointwise16_kernel<f16, false>), grid, dim3(256), 0, ST, *p);
+    }
+    STL_LAUNCH_CHECK("det_pointwise16");
+    return 0;
+}
+
+extern "C" int stl_det_fuse16(const StlDetFuse* f, int dtype, void* stream) {
+    DET16_DTYPE("det_fuse16", dtype);
+    STL_CHECK(f && f->out && f->B >= 1 && f->H >= 1 && f->W >= 1, "det_fuse16: bad geometry");
+    DET16_C8("det_fuse16", f->C);
+    STL_CHECK(f->nterms >= 1 && f->nterms <= 3 && (f->wparam || f->nterms == 1), "det_fuse16: %d terms", f->nterms);
+    STL_CHECK(al16(f->out), "det_fuse16: out must be 16-byte aligned");
+    for (int i = 0; i < f->nterms; ++i) {
+        const StlDetTerm& t = f->t[i];
+        STL_CHECK(t.x && al16(t.x), "det_fuse16: term %d null or not 16-byte aligned", i);
+        const bool ok = t.mode == 0 ? (t.H == f->H && t.W == f->W)
+                      : t.mode == 1 ? (2 * t.H == f->H && 2 * t.W == f->W)
+                      : t.mode == 2 ? ((t.H + 1) / 2 == f->H && (t.W + 1) / 2 == f->W) : false;
+        STL_CHECK(ok, "det_fuse16: term %d mode %d of %d x %d into %d x %d", i, t.mode, t.H, t.W, f->H, f->W);
+    }
+    const int64_t n = (int64_t)f->B * f->H * f->W * (f->C / 8);
+    const dim3 grid((unsigned)((n + 255) / 256));
+    if (dtype == STL_BF16) STL_LAUNCH(fuse16_kernel<__bf16>, grid, dim3(256), 0, ST, *f);
+    else STL_LAUNCH(fuse16_kernel<f16>, grid, dim3(256), 0, ST, *f);
+    STL_LAUNCH_CHECK("det_fuse16");
     return 0;
 }
 

@@ -3,11 +3,18 @@
 
 ``EfficientDetBackbone(num_classes, compound_coef)`` holds the reference's parameters and buffers under the reference's key names
 (a reference checkpoint loads with ``strict=True``, also with the ``module.`` prefix of a DataParallel save).  Its forward is
-inference only and runs every layer through csrc/detector.hip (fp32, NHWC): the preprocess kernel, the stem, depthwise and
-squeeze-excitation kernels, the pointwise GEMM on fp32 MFMA with BN folded into its weights, the BiFPN node kernel, the shared
+inference only and runs every layer through csrc/detector.hip (NHWC): the preprocess kernel, the stem, depthwise and
+squeeze-excitation kernels, the pointwise GEMM on MFMA with BN folded into its weights, the BiFPN node kernel, the shared
 heads writing straight into the concatenated outputs, the decode kernel and the class-aware NMS.  BN is folded into packed fp32
 weights on the device and refolded when any parameter or buffer changes; the launches of one batch size are listed once
 (``_Plan``) and replayed; the last MAX_PLANS batch sizes keep their plans.  Only the kept boxes, scores and labels reach the host.
+
+``compute_dtype`` is "fp32" (the default), "bf16" or "f16".  Parameters, buffers and ``state_dict()`` are fp32 in every mode and
+BN is folded in fp64; a 16-bit mode stores the activations between the stem and the head outputs in that type (the canvas, the
+head outputs ``reg`` / ``cls``, decode and NMS stay fp32), rounds the folded pointwise weights once to it for the 16-bit MFMA and
+keeps every other weight, every bias and every sum in fp32.  The depthwise kernel of an MBConv block also writes the
+squeeze-excitation pooling sums, so a 16-bit plan has no pooling pass.  In "f16" a forward whose head outputs hold a non-finite
+value raises FloatingPointError (activations left f16's range: use "bf16"), as HRNet's "mixed" mode does.
 """
 from __future__ import annotations
 
@@ -38,6 +45,8 @@ ANCHOR_SCALE = {0: 4.0, 3: 4.0}
 STAGES = [(3, 1, 32, 16, 1, 1), (3, 2, 16, 24, 6, 2), (5, 2, 24, 40, 6, 2), (3, 3, 40, 80, 6, 2), (5, 3, 80, 112, 6, 1),
           (5, 4, 112, 192, 6, 2), (3, 1, 192, 320, 6, 1)]
 WIDTH_DEPTH = {0: (1.0, 1.0), 3: (1.2, 1.4)}   # efficientnet-b0 / -b3
+# compute_dtype -> (activation dtype, the library's dtype code STL_F32 / STL_BF16 / STL_F16)
+COMPUTE_DTYPES = {"fp32": (torch.float32, 0), "bf16": (torch.bfloat16, 1), "f16": (torch.float16, 2)}
 
 
 def round_filters(f: int, width: float) -> int:
@@ -204,10 +213,12 @@ def _fold(bn: nn.BatchNorm2d):
 
 
 class _Packer:
-    """Packs folded weights into one fp32 device buffer; every piece starts on a 16-float boundary."""
+    """Packs folded weights into one fp32 device buffer; every piece starts on a 16-float boundary.  With a 16-bit ``dtype`` the
+    pointwise weights go into a second buffer of that type, in the layout of stl_det_pointwise16."""
 
-    def __init__(self):
+    def __init__(self, dtype: torch.dtype = torch.float32):
         self.parts, self.n = [], 0
+        self.dtype, self.parts16, self.n16 = dtype, [], 0
 
     def add(self, t: torch.Tensor) -> int:
         off = self.n
@@ -218,7 +229,9 @@ class _Packer:
         return off
 
     def pw(self, conv: nn.Conv2d, bn: Optional[nn.BatchNorm2d] = None):
-        """1x1 conv (+ BN) -> (w offset, bias offset or None, Kp, Np): w packed [Kp][Np] zero-padded, bias [Np]."""
+        """1x1 conv (+ BN) -> (w offset, bias offset or None, Kp, Np): w packed [Kp][Np] zero-padded, bias [Np].  16-bit: the w
+        offset is into the 16-bit buffer, w rounded once from the fp64 fold and packed [Np / 16][Kp / 32][4][16][8] (a lane of the
+        MFMA loads its 8 k of one column in 16 bytes), Kp % 32 == 0."""
         w = conv.weight.detach().double().reshape(conv.out_channels, conv.in_channels)
         b = conv.bias.detach().double() if conv.bias is not None else None
         if bn is not None:
@@ -226,6 +239,20 @@ class _Packer:
             w = w * s[:, None]
             b = t if b is None else b * s + t
         co, ci = w.shape
+        if self.dtype != torch.float32:
+            kp, np_ = -(-ci // 32) * 32, -(-co // 64) * 64
+            wp = w.new_zeros(np_, kp)
+            wp[:co, :ci] = w
+            wp = wp.reshape(np_ // 16, 16, kp // 32, 4, 8).permute(0, 2, 3, 1, 4).reshape(-1).to(self.dtype)
+            bo = None
+            if b is not None:
+                bp = w.new_zeros(np_)
+                bp[:co] = b
+                bo = self.add(bp)
+            off = self.n16
+            self.parts16.append(wp)
+            self.n16 += wp.numel()
+            return off, bo, kp, np_
         kp, np_ = -(-ci // 16) * 16, -(-co // 64) * 64
         wp = w.new_zeros(kp, np_)
         wp[:ci, :co] = w.t()
@@ -249,24 +276,35 @@ class _Packer:
     def done(self, dev) -> torch.Tensor:
         return torch.cat(self.parts).float().to(dev).contiguous() if self.parts else torch.zeros(1, device=dev)
 
+    def done16(self, dev) -> Optional[torch.Tensor]:
+        return torch.cat(self.parts16).to(dev).contiguous() if self.parts16 else None
+
 
 # ------------------------------------------------------------------------------------------------ the launch plan
 class _Plan:
     """Every launch of one forward at batch B on the 512 canvas, with its buffers: a list of (entry point, arguments) replayed by
-    ``run``; ``canvas`` is the input, ``feats`` the five BiFPN outputs (NHWC), ``reg`` / ``cls`` the head outputs."""
+    ``run``; ``canvas`` is the input, ``feats`` the five BiFPN outputs (NHWC), ``reg`` / ``cls`` the head outputs.  In a 16-bit
+    mode every activation buffer has the model's compute type and the *16 entry points are listed; canvas, reg and cls are fp32.
+    ``launches`` counts kernel launches (the fp32 squeeze-excitation entry point is two: its pooling pass and the gate)."""
 
     def __init__(self, m: "EfficientDetBackbone", B: int, dev):
         self.B, self.dev, self.calls, self._keep = B, dev, [], []
-        self.flops = self.bytes = 0   # from the shapes: multiply-adds x 2, and every tensor each launch reads or writes once
-        self.wbuf = m._wbuf
+        self.flops = self.bytes = self.launches = 0   # from the shapes: multiply-adds x 2, and every tensor each launch reads or writes once
+        self.wbuf, self.wbuf16 = m._wbuf, m._wbuf16
+        self.adtype, self.code = COMPUTE_DTYPES[m.compute_dtype]
+        self.h16 = self.code != 0
+        self.es = 2 if self.h16 else 4   # bytes per stored activation / pointwise weight
         S = MAX_SIZE
         self.canvas = torch.empty(B, S, S, 3, device=dev)
         L = m._layout
         net = m.backbone_net.model
         H = (S + 1) // 2
         x = self._buf(B, H, H, net._conv_stem.conv.out_channels)
-        self._call("stl_det_stem", self.canvas, self._w(L["stem"][0]), self._w(L["stem"][1]), x, B, S, S, x.shape[3])
-        self._cost(2 * x.numel() * 27, 4 * (self.canvas.numel() + x.numel()))
+        if self.h16:
+            self._call("stl_det_stem16", self.code, self.canvas, self._w(L["stem"][0]), self._w(L["stem"][1]), x, B, S, S, x.shape[3])
+        else:
+            self._call("stl_det_stem", self.canvas, self._w(L["stem"][0]), self._w(L["stem"][1]), x, B, S, S, x.shape[3])
+        self._cost(2 * x.numel() * 27, 4 * self.canvas.numel() + self.es * x.numel())
         h = H
         feats, specs = [], net.specs
         for i, (b, lay) in enumerate(zip(specs, L["blocks"])):
@@ -279,15 +317,24 @@ class _Plan:
                 x = y
             ho = (h + b["s"] - 1) // b["s"]
             y = self._buf(B, ho, ho, b["mid"])
-            self._call("stl_det_dwconv", x, self._w(lay["dw"][0]), self._w(lay["dw"][1]), y, B, h, h, b["mid"], b["k"], b["s"], 1)
-            self._cost(2 * y.numel() * b["k"] ** 2, 4 * (x.numel() + y.numel()))
-            h, x = ho, y
-            part = torch.empty(capi.lib().stl_det_se_workspace(B) * b["mid"], device=dev)
             scale = torch.empty(B, b["mid"], device=dev)
             se = lay["se"]
-            self._call("stl_det_se", x, B, h * h, b["mid"], b["se"], self._w(se[0]), self._w(se[1]), self._w(se[2]), self._w(se[3]),
-                       part, scale)
-            self._cost(x.numel() + 4 * B * b["mid"] * b["se"], 4 * x.numel())
+            if self.h16:   # the depthwise kernel writes the pooling sums: no pass over its output
+                nparts = capi.lib().stl_det_dw16_parts(ho * ho)
+                part = torch.empty(B * nparts * b["mid"], device=dev)
+                self._dw(x, y, lay["dw"][0], lay["dw"][1], h, b["mid"], b["k"], b["s"], 1, part)
+                h, x = ho, y
+                self._call("stl_det_se16", part, B, h * h, nparts, b["mid"], b["se"], self._w(se[0]), self._w(se[1]), self._w(se[2]),
+                           self._w(se[3]), scale)
+                self._cost(part.numel() + 4 * B * b["mid"] * b["se"], 4 * part.numel())
+            else:
+                self._dw(x, y, lay["dw"][0], lay["dw"][1], h, b["mid"], b["k"], b["s"], 1)
+                h, x = ho, y
+                part = torch.empty(capi.lib().stl_det_se_workspace(B) * b["mid"], device=dev)
+                self._call("stl_det_se", x, B, h * h, b["mid"], b["se"], self._w(se[0]), self._w(se[1]), self._w(se[2]), self._w(se[3]),
+                           part, scale)
+                self.launches += 1
+                self._cost(x.numel() + 4 * B * b["mid"] * b["se"], 4 * x.numel())
             y = self._buf(B, h, h, b["co"])
             self._pw(x, y, B, h * h, b["mid"], b["co"], lay["project"], act=0, in_scale=scale, residual=inp if b["skip"] else None)
             x = y
@@ -308,19 +355,17 @@ class _Plan:
                 t = f
                 for i in range(len(head.conv_list)):
                     d = self._buf(B, hh, hh, c)
-                    self._call("stl_det_dwconv", t, self._w(lay["dw"][i]), None, d, B, hh, hh, c, 3, 1, 0)
-                    self._cost(2 * d.numel() * 9, 8 * d.numel())
+                    self._dw(t, d, lay["dw"][i], None, hh, c, 3, 1, 0)
                     e = self._buf(B, hh, hh, c)
                     self._pw(d, e, B, hh * hh, c, c, lay["pw"][li][i], act=1)
                     t = e
                 d = self._buf(B, hh, hh, c)
-                self._call("stl_det_dwconv", t, self._w(lay["hdw"]), None, d, B, hh, hh, c, 3, 1, 0)
-                self._cost(2 * d.numel() * 9, 8 * d.numel())
+                self._dw(t, d, lay["hdw"], None, hh, c, 3, 1, 0)
                 self._pw(d, out, B, hh * hh, c, 9 * k, lay["hpw"], act=act, img_stride=A * k, row_stride=9 * k, off=aoff * k)
                 aoff += hh * hh * 9
 
     def _buf(self, B, h, w, c):
-        return torch.empty(B, h, w, c, device=self.dev)
+        return torch.empty(B, h, w, c, device=self.dev, dtype=self.adtype)
 
     def _w(self, off):
         return None if off is None else self.wbuf[off:]
@@ -340,15 +385,35 @@ class _Plan:
             else:
                 conv.append(a)
         self.calls.append((getattr(capi.lib(), name), name, conv))
+        self.launches += 1
+
+    def _dw(self, x, y, w, bias, h, c, k, s, act, partial=None):
+        """Depthwise k x k / s on the h x h map x -> y; 16-bit with ``partial``: also the squeeze-excitation pooling sums."""
+        if self.h16:
+            self._call("stl_det_dwconv16", self.code, x, self._w(w), self._w(bias), y, partial, self.B, h, h, c, k, s, act)
+        else:
+            self._call("stl_det_dwconv", x, self._w(w), self._w(bias), y, self.B, h, h, c, k, s, act)
+        self._cost(2 * y.numel() * k * k, self.es * (x.numel() + y.numel()) + (0 if partial is None else 4 * partial.numel()))
 
     def _pw(self, x, out, B, hw, ci, co, pk, act, in_scale=None, residual=None, img_stride=None, row_stride=None, off=0):
         w, b, kp, np_ = pk
+        m = B * hw
+        self._keep += [x, out] + [t for t in (in_scale, residual) if t is not None]
+        self.launches += 1
+        if self.h16:
+            p = capi.DetPointwise16(x.data_ptr(), self.wbuf16[w:].data_ptr(), None if b is None else self.wbuf[b:].data_ptr(),
+                                    None if in_scale is None else in_scale.data_ptr(), None if residual is None else residual.data_ptr(),
+                                    out.data_ptr(), m, hw * co if img_stride is None else img_stride,
+                                    co if row_stride is None else row_stride, off, hw, ci, co, kp, np_, act, self.code,
+                                    1 if out.dtype == torch.float32 else 0)
+            self._cost(2 * m * ci * co, self.es * (m * ci + kp * np_ + (m * co if residual is not None else 0)) + out.element_size() * m * co)
+            self.calls.append((capi.lib().stl_det_pointwise16, "stl_det_pointwise16", [C.byref(p)]))
+            self._keep.append(p)
+            return
         p = capi.DetPointwise(x.data_ptr(), self.wbuf[w:].data_ptr(), None if b is None else self.wbuf[b:].data_ptr(),
                               None if in_scale is None else in_scale.data_ptr(), None if residual is None else residual.data_ptr(),
                               out.data_ptr(), B * hw, hw * co if img_stride is None else img_stride,
                               co if row_stride is None else row_stride, off, hw, ci, co, kp, np_, act)
-        self._keep += [x, out] + [t for t in (in_scale, residual) if t is not None]
-        m = B * hw
         self._cost(2 * m * ci * co, 4 * (m * ci + m * co * (2 if residual is not None else 1) + kp * np_))
         self.calls.append((capi.lib().stl_det_pointwise, "stl_det_pointwise", [C.byref(p)]))
         self._keep.append(p)
@@ -362,14 +427,17 @@ class _Plan:
         f.wparam = None if wparam is None else wparam.data_ptr()
         f.out = out.data_ptr()
         self._keep += [out, f]
-        self._cost(out.numel() * (2 * len(terms) + 4), 4 * (out.numel() + sum(t.numel() for t, _ in terms)))
-        self.calls.append((capi.lib().stl_det_fuse, "stl_det_fuse", [C.byref(f)]))
+        self._cost(out.numel() * (2 * len(terms) + 4), self.es * (out.numel() + sum(t.numel() for t, _ in terms)))
+        self.launches += 1
+        if self.h16:
+            self.calls.append((capi.lib().stl_det_fuse16, "stl_det_fuse16", [C.byref(f), self.code]))
+        else:
+            self.calls.append((capi.lib().stl_det_fuse, "stl_det_fuse", [C.byref(f)]))
 
     def _sep(self, x, pk, h, c):
         """SeparableConvBlock: depthwise 3x3 (no bias) then 1x1 with bias and BN folded, no activation."""
         d = self._buf(self.B, h, h, c)
-        self._call("stl_det_dwconv", x, self._w(pk[0]), None, d, self.B, h, h, c, 3, 1, 0)
-        self._cost(2 * d.numel() * 9, 8 * d.numel())
+        self._dw(x, d, pk[0], None, h, c, 3, 1, 0)
         y = self._buf(self.B, h, h, c)
         self._pw(d, y, self.B, h * h, c, c, pk[1], act=0)
         return y
@@ -432,10 +500,16 @@ class EfficientDetBackbone(nn.Module):
     (04 passes ``img / 255``) or a list of CHW float arrays in [0, 1]; postprocess=False returns (features, regression,
     classification, anchors) with the reference's shapes (five NCHW maps, [B, A, 4], [B, A, num_classes] after the sigmoid,
     [1, A, 4]) on the GPU; otherwise one dict per image with CPU tensors ``boxes`` float32 [k, 4] (x1, y1, x2, y2 in original
-    pixels), ``labels`` int32 (class + 1) and ``scores`` float32, in NMS keep order.  Raises in training mode."""
+    pixels), ``labels`` int32 (class + 1) and ``scores`` float32, in NMS keep order.  Raises in training mode.
 
-    def __init__(self, num_classes=80, compound_coef=0, load_weights=False, **kwargs):
+    compute_dtype "fp32" (default), "bf16" or "f16": the type the activations are stored in on the device (module docstring);
+    the outputs are fp32 in every mode.  A model keeps its compute_dtype for life."""
+
+    def __init__(self, num_classes=80, compound_coef=0, load_weights=False, compute_dtype="fp32", **kwargs):
         super().__init__()
+        if compute_dtype not in COMPUTE_DTYPES:
+            raise ValueError(f"EfficientDet: compute_dtype {compute_dtype!r} (one of 'fp32', 'bf16', 'f16')")
+        self.compute_dtype = compute_dtype
         if compound_coef not in FPN_FILTERS:
             raise NotImplementedError(f"EfficientDet: compound_coef {compound_coef} (supported: 0 and 3, what setup_detector allows)")
         if load_weights:
@@ -457,7 +531,7 @@ class EfficientDetBackbone(nn.Module):
         self.iou_threshold = kwargs.get("iou_threshold", 0.5)
         self.anchors_np = anchors(cc)
         self.num_anchors_total = self.anchors_np.shape[0]
-        self._version, self._plans, self._wbuf, self._anchor_dev = None, {}, None, None
+        self._version, self._plans, self._wbuf, self._wbuf16, self._anchor_dev = None, {}, None, None, None
         self.eval()
 
     # ---------------------------------------------------------------- state
@@ -468,14 +542,15 @@ class EfficientDetBackbone(nn.Module):
         return tuple((t.data_ptr(), t._version) for t in list(self.parameters()) + list(self.buffers()))
 
     def ready(self, dev) -> None:
-        """Fold BN and pack every weight into one fp32 device buffer; redone when any parameter or buffer has changed."""
+        """Fold BN and pack every weight into one fp32 device buffer (in a 16-bit mode the pointwise weights into a second one of
+        that type); redone when any parameter or buffer has changed."""
         dev = _device(dev)
         if self.backbone_net.model._bn0.weight.device != dev:
             self.to(dev)
         v = self._state_version()
         if v == self._version and self._wbuf is not None and self._wbuf.device == dev:
             return
-        P = _Packer()
+        P = _Packer(COMPUTE_DTYPES[self.compute_dtype][0])
         net = self.backbone_net.model
         s, t = _fold(net._bn0)
         stem = (P.add((net._conv_stem.conv.weight.detach().double() * s[:, None, None, None]).permute(2, 3, 1, 0).contiguous()),
@@ -507,7 +582,7 @@ class EfficientDetBackbone(nn.Module):
             heads[name] = {"dw": [P.dw(cv.depthwise_conv.conv)[0] for cv in hd.conv_list],
                            "pw": [[P.pw(cv.pointwise_conv.conv, hd.bn_list[lv][i]) for i, cv in enumerate(hd.conv_list)] for lv in range(5)],
                            "hdw": P.dw(hd.header.depthwise_conv.conv)[0], "hpw": P.pw(hd.header.pointwise_conv.conv)}
-        self._wbuf = P.done(dev)
+        self._wbuf, self._wbuf16 = P.done(dev), P.done16(dev)
         for cell in cells:   # BiFPN weight offsets -> device views
             cell["weights"] = {n: self._wbuf[o:] for n, o in cell["weights"].items()}
         self._layout = {"stem": stem, "blocks": blocks, "bifpn": cells, **heads}
@@ -569,8 +644,15 @@ class EfficientDetBackbone(nn.Module):
         with torch.no_grad():
             p, metas, keep = self._preprocess(srcs, kind, dev)
             p.run(ops._st())
+            self._range_guard(p)
         p._inflight = keep   # the sources and the record table live until the next call
         return p, metas
+
+    def _range_guard(self, p: _Plan) -> None:
+        """f16 only: an activation past 65504 became inf and reaches the head outputs as inf or NaN (one small reduction)."""
+        if self.compute_dtype == "f16" and not bool((torch.isfinite(p.reg).all() & torch.isfinite(p.cls).all()).item()):
+            raise FloatingPointError("EfficientDet: non-finite head outputs in compute_dtype='f16': activations left f16's range "
+                                     "(largest finite value 65504); build the detector with compute_dtype='bf16'")
 
     def forward(self, inputs, preprocess=True, postprocess=True, threshold=None, iou_threshold=None):
         self._check_mode()
@@ -589,9 +671,10 @@ class EfficientDetBackbone(nn.Module):
             with torch.no_grad():
                 p.canvas.copy_(x.permute(0, 2, 3, 1))
                 p.run(ops._st())
+                self._range_guard(p)
             metas = None
         if not postprocess:
-            feats = tuple(f.permute(0, 3, 1, 2).clone() for f, _ in p.feats)
+            feats = tuple(f.permute(0, 3, 1, 2).to(torch.float32, copy=True) for f, _ in p.feats)
             return feats, p.reg.clone(), p.cls.clone(), self._anchor_dev[None].clone()
         return self.detect(p, metas, self.threshold, self.iou_threshold)
 
@@ -638,9 +721,10 @@ def detect_from_heads(reg: torch.Tensor, cls: torch.Tensor, anchors_dev: torch.T
     return out
 
 
-def setup_detector(model_name="faster_rcnn", model_type="", pretrained=True, num_classes=1, **kwargs):
+def setup_detector(model_name="faster_rcnn", model_type="", pretrained=True, num_classes=1, compute_dtype="fp32", **kwargs):
     """lib/model_setup.py:60-95.  "efficientdet" with model_type "" / "d0" or "d3" builds the reference's configuration
-    (num_classes, its anchors, threshold 0.5, iou_threshold 0.5); weights come from a state_dict (load_state_dict)."""
+    (num_classes, its anchors, threshold 0.5, iou_threshold 0.5); weights come from a state_dict (load_state_dict).
+    compute_dtype ("fp32", "bf16", "f16") is EfficientDetBackbone's."""
     if model_name not in ("faster_rcnn", "efficientdet"):
         raise ValueError(f"setup_detector: model_name {model_name!r} (one of 'faster_rcnn', 'efficientdet')")
     if model_type not in ("", "d0", "d3", None):
@@ -650,4 +734,4 @@ def setup_detector(model_name="faster_rcnn", model_type="", pretrained=True, num
                                   "reference's own code; use 'efficientdet'")
     cc = 3 if model_type == "d3" else 0
     return EfficientDetBackbone(compound_coef=cc, num_classes=num_classes, ratios=RATIOS, scales=SCALES, threshold=0.5,
-                                iou_threshold=0.5)
+                                iou_threshold=0.5, compute_dtype=compute_dtype)
