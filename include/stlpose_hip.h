@@ -430,7 +430,8 @@ int stl_heatmap_resize_argmax(const float* hm, int BJ, int H, int W, int Ho, int
                               void* stream);
 
 /* ---- EfficientDet person detector (stlpose_amd/csrc/detector.hip): src/models/EfficientDet.py with
- * models/efficientdet_utils/{model,utils}.py and models/efficientnet/{model,utils,utils_extra}.py, inference only, NHWC activations.
+ * models/efficientdet_utils/{model,utils}.py and models/efficientnet/{model,utils,utils_extra}.py, NHWC activations; inference, and
+ * fine-tuning of the heads (further down).
  * The stl_det_* entry points without a suffix are the fp32 path.  The *16 entry points further down are the 16-bit compute modes
  * (EfficientDetBackbone(compute_dtype="bf16" | "f16")): activations stored as STL_BF16 or STL_F16, every sum in fp32. */
 #define STL_DET_NMS_MAX 65536      /* candidates per image of stl_det_nms (all 49104 anchors of a 512 canvas fit) */
@@ -543,6 +544,56 @@ int stl_det_decode(const float* reg, const float* cls, const float* anchors, int
 int stl_det_nms(const float* boxes, const int32_t* classes, const int32_t* order, int n, double iou_thr, void* work, int32_t* keep,
                 int32_t* count, void* stream);
 int64_t stl_det_nms_workspace(int n);
+
+/* -- Fine-tuning the heads (stlpose_amd/csrc/detector_train.hip; stlpose_amd/detector_train.py).  The backbone and the BiFPN are
+ * frozen and every BN runs on its running statistics, so the heads are depthwise 3x3 -> pointwise (bias and BN folded, W' and b')
+ * -> swish per layer and level, and a header.  fp32, NHWC; every reduction in a fixed order (two runs are bitwise equal). */
+/* stl_det_pointwise with act 1 (swish) and no residual that also keeps the pre-activation: z [M, Co] = x w + bias, out = swish(z).
+ * The kernel of stl_det_pointwise: out equals that call's bit for bit. */
+int stl_det_pointwise_train(const StlDetPointwise* p, float* z, void* stream);
+/* The RetinaNet / EfficientDet detection loss (no reference item; restated in tests/detector_train_ref.py).  reg [B, A, 4] (dy, dx,
+ * dh, dw), cls [B, A, nc] after the sigmoid, anchors [A, 4] (y1, x1, y2, x2), gt [sum G, 5] (x1, y1, x2, y2, class) on the canvas with
+ * offsets int32 [B + 1] (gt may be NULL when every image is empty).  Per image: IoU = inter / max(area_a + area_g - inter, 1e-8); an
+ * anchor is positive (first argmax g*) at max IoU >= 0.5, negative below 0.4, ignored between, negative when the image has no box.
+ * Classification, p = clamp(cls, 1e-4, 1 - 1e-4): alpha (1 - p)^gamma (-log p) at (positive, class of g*), (1 - alpha) p^gamma
+ * (-log(1 - p)) at every other class of a positive or negative anchor, summed and divided by max(N_pos, 1).  Regression over the
+ * positives: smooth L1 (4.5 d^2 if d <= 1/9, else d - 1/18) of d = |t - reg|, t = ((cy_g - cy_a) / h_a, (cx_g - cx_a) / w_a,
+ * log(h_g / h_a), log(w_g / w_a)) with w_g, h_g >= 1, mean over 4 N_pos (0 without positives).  losses [2] = (mean_b L_cls,b,
+ * box_weight * mean_b L_reg,b); dreg [B, A, 4] and dlogit [B, A, nc] are the gradients of losses[1] and losses[0] with respect to
+ * reg and to the classifier header's pre-sigmoid output (zero where the clamp is active); npos int32 [B].  Workspaces: assign int32
+ * [B, A], per_image [B, 2].  One workgroup per image (N_pos normalises that image's gradients), then one launch for the batch means. */
+int stl_det_loss(const float* reg, const float* cls, const float* anchors, const float* gt, const int32_t* offsets, int B, int A, int nc,
+                 float alpha, float gamma, float box_weight, int32_t* assign, float* per_image, float* losses, float* dreg, float* dlogit,
+                 int32_t* npos, void* stream);
+/* Backward of stl_det_pointwise (no in_scale, no residual; the activation's derivative is already in dy).  dy is read as the forward
+ * writes its output: dy[img(m) * dy_img_stride + pix(m) * dy_row_stride + dy_off + n], so a header's gradient comes straight out of
+ * the concatenated [B, A, k] tensor.  w is the forward's packed [Kp][Np].
+ *   bwd_data:   dx [M, Ci] = sum_n dy[m, n] w[k, n]                                       (reads w, dy; writes dx)
+ *   bwd_weight: dw [Ci][Co] = sum_m x[m, k] dy[m, n], db [Co] = sum_m dy[m, n]            (reads x [M, Ci], dy; writes dw, db)
+ * bwd_weight splits M into stl_det_pointwise_bwd_slabs(M) slabs over workgroups and adds them in slab order; partial holds
+ * slabs * (Ci * Co + Co) floats.  Both run on v_mfma_f32_16x16x4_f32. */
+typedef struct {
+    const float* x;
+    const float* w;
+    const float* dy;
+    float* dx;
+    float* dw;
+    float* db;
+    float* partial;
+    int64_t M, dy_img_stride, dy_row_stride, dy_off;
+    int32_t HW, Ci, Co, Kp, Np, pad_;
+} StlDetPointwiseBwd;
+int stl_det_pointwise_bwd_data(const StlDetPointwiseBwd* p, void* stream);
+int stl_det_pointwise_bwd_weight(const StlDetPointwiseBwd* p, void* stream);
+int stl_det_pointwise_bwd_slabs(int64_t M);
+/* Backward of stl_det_dwconv with k 3, s 1, no bias, no activation (the heads' depthwise layers).  bwd_data: dx [B, H, W, C] =
+ * sum_{ky, kx} dy[b, y + 1 - ky, x + 1 - kx, c] w[ky][kx][c] (w as the forward takes it; the kernel flips the taps), times swish'(z)
+ * when z [B, H, W, C] (the stored pre-activation of the layer below) is not NULL.  bwd_weight: dw [3][3][C] = sum over batch and
+ * pixels of x[b, y - 1 + ky, x - 1 + kx, c] dy[b, y, x, c]: stl_det_dwconv_bwd_parts(B * H * W) partial sums (partial: parts * 9 * C
+ * floats), then added in part order. */
+int stl_det_dwconv_bwd_data(const float* dy, const float* w, const float* z, float* dx, int B, int H, int W, int C, void* stream);
+int stl_det_dwconv_bwd_weight(const float* x, const float* dy, float* partial, float* dw, int B, int H, int W, int C, void* stream);
+int stl_det_dwconv_bwd_parts(int64_t npix);
 
 /* ---- AdaIN feed-forward stylisation (csrc/adain.hip; stlpose_amd/adain.py).  No reference counterpart: the network is the published
  * one (Huang & Belongie 2017), restated in tests/adain_ref.py.  The 3x3 convs pad by reflection and stl_conv pads with zeros, so every

@@ -132,6 +132,12 @@ class DetPointwise16(C.Structure):
                 ("Kp", i32), ("Np", i32), ("act", i32), ("dtype", i32), ("out_f32", i32)]
 
 
+class DetPointwiseBwd(C.Structure):
+    _fields_ = [("x", vp), ("w", vp), ("dy", vp), ("dx", vp), ("dw", vp), ("db", vp), ("partial", vp), ("M", i64),
+                ("dy_img_stride", i64), ("dy_row_stride", i64), ("dy_off", i64), ("HW", i32), ("Ci", i32), ("Co", i32),
+                ("Kp", i32), ("Np", i32), ("pad_", i32)]
+
+
 class DetTerm(C.Structure):
     _fields_ = [("x", vp), ("mode", i32), ("H", i32), ("W", i32), ("pad_", i32)]
 
@@ -225,6 +231,14 @@ SIGNATURES = {
     "stl_det_decode": [vp, vp, vp, i32, i32, i32, f32, f32, f32, vp, vp, vp, vp, vp, vp],
     "stl_det_nms": [vp, vp, vp, i32, C.c_double, vp, vp, vp, vp],
     "stl_det_nms_workspace": [i32],
+    "stl_det_pointwise_train": [C.POINTER(DetPointwise), vp, vp],
+    "stl_det_loss": [vp, vp, vp, vp, vp, i32, i32, i32, f32, f32, f32, vp, vp, vp, vp, vp, vp, vp],
+    "stl_det_pointwise_bwd_data": [C.POINTER(DetPointwiseBwd), vp],
+    "stl_det_pointwise_bwd_weight": [C.POINTER(DetPointwiseBwd), vp],
+    "stl_det_pointwise_bwd_slabs": [i64],
+    "stl_det_dwconv_bwd_data": [vp, vp, vp, vp, i32, i32, i32, i32, vp],
+    "stl_det_dwconv_bwd_weight": [vp, vp, vp, vp, i32, i32, i32, i32, vp],
+    "stl_det_dwconv_bwd_parts": [i64],
     "stl_adain_input": [i32, vp, vp, i32, i32, i32, vp],
     "stl_reflect_gather": [i32, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp],
     "stl_adain_stats": [i32, vp, i32, i32, i32, i32, i32, i32, vp, f32, vp, vp, vp, vp],

@@ -7,6 +7,8 @@
 //   stl_det_se          squeeze-excitation scale[B, C] (efficientnet/model.py:84-89)
 //   stl_det_pointwise   1x1 conv as a GEMM on v_mfma_f32_16x16x4_f32: SE scale on load, bias, swish / sigmoid, residual,
 //                       strided output (the head headers write straight into the concatenated [B, A, k] outputs)
+//   stl_det_pointwise_train  the same launch with swish, also keeping its pre-activation z (the heads' training forward,
+//                       stlpose_amd/detector_train.py; the backward kernels are in detector_train.hip)
 //   stl_det_fuse        BiFPN node swish(sum w_i * in_i) with same / nearest-2x / zero-padded 3x3 s2 max-pool inputs, the
 //                       fast-attention weights normalised on the device (efficientdet_utils/model.py:163-233)
 //   stl_det_decode      per-anchor class max, strict threshold, BBoxTransform, ClipBoxes, compaction in anchor order
@@ -203,10 +205,12 @@ __global__ __launch_bounds__(256) void se_kernel(const float* __restrict__ parti
 // out[m, n] = act(sum_k x[m, k] * (scale[img(m), k]) * w[k, n] + bias[n]) (+ residual[m, n]), m over B * HW pixels.
 // Workgroup tile 64 x 64, 4 waves, wave w owns rows 16w .. 16w + 15 and all 64 columns (4 accumulators of 16 x 16);
 // K in steps of 16 through LDS.  w is packed [Kp][Np] with zero padding (Kp % 16 == 0, Np % 64 == 0): activations are read
-// with bounds checks, never padded.
+// with bounds checks, never padded.  KEEPZ: the value before the activation also goes to z [M, Co] (one kernel, so that the
+// training forward of the heads is the inference forward bit for bit).
 constexpr int kPwM = 64, kPwN = 64, kPwK = 16;
 
-__global__ __launch_bounds__(256) void pointwise_kernel(const StlDetPointwise p) {
+template <bool KEEPZ>
+__global__ __launch_bounds__(256) void pointwise_kernel(const StlDetPointwise p, float* __restrict__ z) {
     __shared__ float sa[kPwK][kPwM + 4];   // [k][m]
     __shared__ float sb[kPwK][kPwN];       // [k][n]
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -262,6 +266,7 @@ __global__ __launch_bounds__(256) void pointwise_kernel(const StlDetPointwise p)
             const int64_t m = m0 + wv * 16 + (lane >> 4) * 4 + r;
             if (m >= p.M) continue;
             float v = acc[j][r] + bias;
+            if (KEEPZ) z[m * p.Co + n] = v;
             if (p.act == 1) v = swishf(v);
             else if (p.act == 2) v = sigmoidf_(v);
             if (p.residual) v += p.residual[m * p.Co + n];
@@ -783,7 +788,7 @@ extern "C" int stl_det_se(const float* x, int B, int HW, int C, int Cs, const fl
 
 extern "C" int stl_det_se_workspace(int B) { return B * kSeSplit; }
 
-extern "C" int stl_det_pointwise(const StlDetPointwise* p, void* stream) {
+static int pointwise_launch(const StlDetPointwise* p, float* z, hipStream_t st) {
     STL_CHECK(p && p->x && p->w && p->out, "det_pointwise: null pointer");
     STL_CHECK(p->M >= 1 && p->HW >= 1 && p->Ci >= 1 && p->Co >= 1, "det_pointwise: M %lld HW %d Ci %d Co %d", (long long)p->M, p->HW,
               p->Ci, p->Co);
@@ -792,9 +797,19 @@ extern "C" int stl_det_pointwise(const StlDetPointwise* p, void* stream) {
     STL_CHECK(p->act >= 0 && p->act <= 2, "det_pointwise: act %d", p->act);
     const int64_t mb = (p->M + kPwM - 1) / kPwM;
     STL_CHECK(mb < (1ll << 31), "det_pointwise: M too large");
-    STL_LAUNCH(pointwise_kernel, dim3((unsigned)mb, p->Np / kPwN), dim3(256), 0, ST, *p);
+    const dim3 grid((unsigned)mb, p->Np / kPwN);
+    if (z) STL_LAUNCH(pointwise_kernel<true>, grid, dim3(256), 0, st, *p, z);
+    else STL_LAUNCH(pointwise_kernel<false>, grid, dim3(256), 0, st, *p, z);
     STL_LAUNCH_CHECK("det_pointwise");
     return 0;
+}
+
+extern "C" int stl_det_pointwise(const StlDetPointwise* p, void* stream) { return pointwise_launch(p, nullptr, ST); }
+
+extern "C" int stl_det_pointwise_train(const StlDetPointwise* p, float* z, void* stream) {
+    STL_CHECK(z, "det_pointwise_train: null z");
+    STL_CHECK(p && p->act == 1 && !p->residual, "det_pointwise_train: the layer must end in swish without a residual");
+    return pointwise_launch(p, z, ST);
 }
 
 extern "C" int stl_det_fuse(const StlDetFuse* f, void* stream) {

@@ -1,0 +1,270 @@
+"""Fine-tuning the EfficientDet heads on the MI355X: ``EfficientDetBackbone.detection_loss`` (the counterpart of
+``loss_dict = self.model(imgs / 255, targets)`` + ``loss.backward()`` in reference ``src/02_train_faster_rcnn.py:189-239``).
+
+The reference has no detection loss for its own EfficientDet; the loss is the published RetinaNet / EfficientDet one (focal
+classification + smooth-L1 box regression over IoU-assigned anchors, stl_det_loss in include/stlpose_hip.h), restated in
+tests/detector_train_ref.py.  This is the first stage of fine-tuning: the backbone and the BiFPN are frozen and run as the
+inference plan's launches, every BN stays on its running statistics (the reference model's ``freeze_bn()``), and the
+``regressor.*`` / ``classifier.*`` parameters get gradients.
+
+``HeadTrain`` belongs to one inference plan (one batch size).  Its forward runs the heads with the inference kernels -- ``reg`` and
+``cls`` equal the inference plan's bit for bit -- and keeps what the backward needs: every depthwise output, and the pre-activation
+``z`` of every swish, written by the pointwise launch that applies it (stl_det_pointwise_train).  Its backward walks each (head,
+level) from the header down through csrc/detector_train.hip and produces gradients of the *folded* weights W' = W s, b' = b s + t
+(s, t the frozen BN's scale and shift) per level; ``fold_chain`` carries them to W, b, gamma and beta in a few elementwise torch
+ops, and the weights shared by the five levels sum their five contributions.  The first depthwise layer of a (head, level) reads
+a frozen feature map: no data gradient is computed for it.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Dict, List, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from . import capi, ops
+from .efficientdet import MAX_SIZE, resize_meta
+
+HEADS = ("regressor", "classifier")
+
+
+# ------------------------------------------------------------------------------------------------ targets
+def pack_targets(targets, sizes: Sequence[Tuple[int, int]], num_classes: int):
+    """The reference's list of target dicts (02_train_faster_rcnn.py:204-209: ``boxes`` [n, 4] x1, y1, x2, y2 in original pixels,
+    ``labels`` [n], 1 = the first class) for images of ``sizes`` (height, width) -> (gt float32 [sum n, 5] (x1, y1, x2, y2, class =
+    label - 1) on the 512 canvas, scaled by resize_meta's ratios, offsets int32 [B + 1]).  ValueError on anything else."""
+    if not isinstance(targets, (list, tuple)) or len(targets) != len(sizes):
+        raise ValueError(f"EfficientDet.detection_loss: targets must be a list of {len(sizes)} dicts (one per image)")
+    rows, offsets = [], [0]
+    for i, (t, (oh, ow)) in enumerate(zip(targets, sizes)):
+        if not isinstance(t, dict) or "boxes" not in t or "labels" not in t:
+            raise ValueError(f"EfficientDet.detection_loss: targets[{i}] must be a dict with 'boxes' and 'labels'")
+        boxes = np.asarray(torch.as_tensor(t["boxes"]).detach().cpu().numpy(), np.float64)
+        lab_t = torch.as_tensor(t["labels"]).detach().cpu()
+        if lab_t.is_floating_point() or lab_t.dtype == torch.bool:
+            raise ValueError(f"EfficientDet.detection_loss: targets[{i}]['labels'] must be integers, got {lab_t.dtype}")
+        labels = lab_t.numpy().astype(np.int64)
+        if labels.ndim != 1:
+            raise ValueError(f"EfficientDet.detection_loss: targets[{i}]['labels'] must be [n], got {labels.shape}")
+        n = labels.shape[0]
+        if boxes.size == 0 and n == 0:
+            boxes = boxes.reshape(0, 4)
+        if boxes.ndim != 2 or boxes.shape != (n, 4):
+            raise ValueError(f"EfficientDet.detection_loss: targets[{i}]['boxes'] must be [n={n}, 4], got {boxes.shape}")
+        if not np.isfinite(boxes).all():
+            raise ValueError(f"EfficientDet.detection_loss: targets[{i}]['boxes'] holds a non-finite value")
+        if n and (labels.min() < 1 or labels.max() > num_classes):
+            raise ValueError(f"EfficientDet.detection_loss: targets[{i}]['labels'] must lie in 1 .. {num_classes}, got "
+                             f"{int(labels.min())} .. {int(labels.max())}")
+        new_w, new_h = resize_meta(int(oh), int(ow))[:2]
+        sx, sy = new_w / ow, new_h / oh
+        g = np.concatenate([boxes * np.array([sx, sy, sx, sy]), (labels - 1)[:, None].astype(np.float64)], 1)
+        rows.append(g.astype(np.float32))
+        offsets.append(offsets[-1] + n)
+    return np.concatenate(rows, 0).reshape(-1, 5), np.asarray(offsets, np.int32)
+
+
+# ------------------------------------------------------------------------------------------------ folded -> raw
+def fold_chain(W, b, gamma, mean, var, eps, GW, Gb):
+    """Gradients of the folded pointwise layer W' = W s[:, None], b' = b s + beta - mean s, s = gamma / sqrt(var + eps) (frozen
+    running statistics), carried to the raw parameters: W, GW [co, ci]; b, gamma, mean, var, Gb [co].  Returns (dW, db, dgamma,
+    dbeta)."""
+    r = torch.rsqrt(var + eps)
+    s = gamma * r
+    ds = (GW * W).sum(1) + Gb * (b - mean)
+    return GW * s[:, None], Gb * s, ds * r, Gb
+
+
+# ------------------------------------------------------------------------------------------------ launches
+class HeadTrain:
+    """Training forward and backward of the two heads on the features of one inference plan (efficientdet._Plan)."""
+
+    def __init__(self, m, plan):
+        self.B, self.dev = B, dev = plan.B, plan.dev
+        self.generation = 0   # forwards through these buffers (the stale-backward check of _DetLossFn)
+        self.fwd, self.bwd, self._keep = [], [], []
+        self.hdr = {h: [] for h in HEADS}   # the headers' backward descriptors: their dy is set per call (set_grads)
+        L = m._layout
+        c, A, nc = m.fpn_channels, m.num_anchors_total, m.num_classes
+        self.c, self.nlayers = c, len(m.regressor.conv_list)
+        self.reg = torch.empty(B, A, 4, device=dev)
+        self.cls = torch.empty(B, A, nc, device=dev)
+        lib = capi.lib()
+        h0 = plan.feats[0][1]
+        m0 = B * h0 * h0
+        self.ga, self.gb = torch.empty(m0 * c, device=dev), torch.empty(m0 * c, device=dev)   # gradients in flight, reused
+        kmax = max(c, 9 * max(4, nc))
+        self.pw_part = torch.empty(lib.stl_det_pointwise_bwd_slabs(m0) * (c * kmax + kmax), device=dev)
+        self.dw_part = torch.empty(lib.stl_det_dwconv_bwd_parts(m0) * 9 * c, device=dev)
+        self.grads: Dict[str, Dict[str, torch.Tensor]] = {}
+        for name, out, k, act in (("regressor", self.reg, 4, 0), ("classifier", self.cls, nc, 2)):
+            lay, n = L[name], self.nlayers
+            g = dict(pw_w=torch.empty(5, n, c, c, device=dev), pw_b=torch.empty(5, n, c, device=dev),
+                     dw=torch.empty(5, n, 3, 3, c, device=dev), hpw_w=torch.empty(5, c, 9 * k, device=dev),
+                     hpw_b=torch.empty(5, 9 * k, device=dev), hdw=torch.empty(5, 3, 3, c, device=dev))
+            self.grads[name] = g
+            aoff = 0
+            for lv, (f, hh) in enumerate(plan.feats):
+                M = B * hh * hh
+                buf = lambda: torch.empty(B, hh, hh, c, device=dev)   # noqa: E731
+                t, d, z = [f], [], []
+                for i in range(n):
+                    d.append(buf()), z.append(buf()), t.append(buf())
+                    self._dw(t[i], d[i], plan._w(lay["dw"][i]), hh)
+                    self._pw(plan, d[i], t[i + 1], M, hh * hh, c, c, lay["pw"][lv][i], 1, z=z[i])
+                dh = buf()
+                self._dw(t[n], dh, plan._w(lay["hdw"]), hh)
+                strides = dict(img_stride=A * k, row_stride=9 * k, off=aoff * k)
+                self._pw(plan, dh, out, M, hh * hh, c, 9 * k, lay["hpw"], act, **strides)
+                # backward, from the header down; ga / gb alternate as the gradient of a depthwise / a pointwise output
+                self.hdr[name].append(self._pw_bwd(plan, dh, None, self.ga, M, hh * hh, c, 9 * k, lay["hpw"], g["hpw_w"][lv],
+                                                   g["hpw_b"][lv], **strides))
+                self._dw_bwd(t[n], self.ga, plan._w(lay["hdw"]), g["hdw"][lv], z[n - 1], self.gb, hh)
+                for i in range(n - 1, -1, -1):
+                    self._pw_bwd(plan, d[i], self.gb, self.ga, M, hh * hh, c, c, lay["pw"][lv][i], g["pw_w"][lv, i], g["pw_b"][lv, i])
+                    self._dw_bwd(t[i], self.ga, plan._w(lay["dw"][i]), g["dw"][lv, i], z[i - 1] if i else None, self.gb if i else None, hh)
+                aoff += hh * hh * 9
+
+    def _args(self, args):
+        out = []
+        for a in args:
+            if torch.is_tensor(a):
+                out.append(C.c_void_p(a.data_ptr()))
+                self._keep.append(a)
+            else:
+                out.append(a)
+        return out
+
+    def _dw(self, x, y, w, h):
+        self.fwd.append((capi.lib().stl_det_dwconv, "stl_det_dwconv", self._args((x, w, None, y, self.B, h, h, self.c, 3, 1, 0))))
+
+    def _pw(self, plan, x, out, M, hw, ci, co, pk, act, z=None, img_stride=None, row_stride=None, off=0):
+        w, b, kp, np_ = pk
+        p = capi.DetPointwise(x.data_ptr(), plan.wbuf[w:].data_ptr(), plan.wbuf[b:].data_ptr(), None, None, out.data_ptr(), M,
+                              hw * co if img_stride is None else img_stride, co if row_stride is None else row_stride, off, hw, ci, co,
+                              kp, np_, act)
+        self._keep += [p, x, out]
+        if z is None:
+            self.fwd.append((capi.lib().stl_det_pointwise, "stl_det_pointwise", [C.byref(p)]))
+        else:
+            self.fwd.append((capi.lib().stl_det_pointwise_train, "stl_det_pointwise_train", [C.byref(p)] + self._args((z,))))
+
+    def _pw_bwd(self, plan, x, dy, dx, M, hw, ci, co, pk, gw, gb, img_stride=None, row_stride=None, off=0):
+        """Weight and data gradient of one pointwise layer; dy None: a header, whose dy (dreg / dlogit) set_grads fills in."""
+        w, _, kp, np_ = pk
+        p = capi.DetPointwiseBwd(x.data_ptr(), plan.wbuf[w:].data_ptr(), None if dy is None else dy.data_ptr(), dx.data_ptr(),
+                                 gw.data_ptr(), gb.data_ptr(), self.pw_part.data_ptr(), M, hw * co if img_stride is None else img_stride,
+                                 co if row_stride is None else row_stride, off, hw, ci, co, kp, np_, 0)
+        self._keep += [p, x, gw, gb]
+        self.bwd.append((capi.lib().stl_det_pointwise_bwd_weight, "stl_det_pointwise_bwd_weight", [C.byref(p)]))
+        self.bwd.append((capi.lib().stl_det_pointwise_bwd_data, "stl_det_pointwise_bwd_data", [C.byref(p)]))
+        return p
+
+    def _dw_bwd(self, x, dy, w, gw, z, dx, h):
+        """Weight gradient of one depthwise layer and, with dx, its data gradient times swish'(z) of the layer below."""
+        self.bwd.append((capi.lib().stl_det_dwconv_bwd_weight, "stl_det_dwconv_bwd_weight",
+                         self._args((x, dy, self.dw_part, gw, self.B, h, h, self.c))))
+        if dx is not None:
+            self.bwd.append((capi.lib().stl_det_dwconv_bwd_data, "stl_det_dwconv_bwd_data",
+                             self._args((dy, w, z, dx, self.B, h, h, self.c))))
+
+    def set_grads(self, dreg: torch.Tensor, dlogit: torch.Tensor) -> None:
+        self.dreg, self.dlogit = dreg, dlogit
+        for name, t in (("regressor", dreg), ("classifier", dlogit)):
+            for p in self.hdr[name]:
+                p.dy = t.data_ptr()
+
+    def forward(self, stream: int) -> None:
+        self.generation += 1
+        self._run(self.fwd, stream)
+
+    def backward(self, stream: int) -> None:
+        self._run(self.bwd, stream)
+
+    @staticmethod
+    def _run(calls, stream):
+        st = C.c_void_p(stream)
+        for fn, name, args in calls:
+            capi.check(fn(*args, st), name)
+
+
+# ------------------------------------------------------------------------------------------------ autograd
+def head_parameters(m) -> List[Tuple[str, torch.nn.Parameter]]:
+    return [(f"{h}.{n}", p) for h in HEADS for n, p in getattr(m, h).named_parameters()]
+
+
+def raw_grads(m, tr: HeadTrain) -> Dict[str, torch.Tensor]:
+    """{parameter name: gradient} of every regressor.* / classifier.* parameter from the folded per-level gradients of tr."""
+    out = {}
+    for h in HEADS:
+        hd, g = getattr(m, h), tr.grads[h]
+        for i, cv in enumerate(hd.conv_list):
+            pre = f"{h}.conv_list.{i}."
+            out[pre + "depthwise_conv.conv.weight"] = g["dw"][:, i].sum(0).permute(2, 0, 1)[:, None]
+            pw = cv.pointwise_conv.conv
+            W, b = pw.weight.detach().reshape(pw.out_channels, pw.in_channels), pw.bias.detach()
+            dW, db = torch.zeros_like(W), torch.zeros_like(b)
+            for lv in range(5):
+                bn = hd.bn_list[lv][i]
+                a, bb, dgam, dbeta = fold_chain(W, b, bn.weight.detach(), bn.running_mean, bn.running_var, bn.eps,
+                                                g["pw_w"][lv, i].t(), g["pw_b"][lv, i])
+                dW, db = dW + a, db + bb
+                out[f"{h}.bn_list.{lv}.{i}.weight"], out[f"{h}.bn_list.{lv}.{i}.bias"] = dgam, dbeta.clone()
+            out[pre + "pointwise_conv.conv.weight"], out[pre + "pointwise_conv.conv.bias"] = dW[:, :, None, None], db
+        out[f"{h}.header.depthwise_conv.conv.weight"] = g["hdw"].sum(0).permute(2, 0, 1)[:, None]
+        out[f"{h}.header.pointwise_conv.conv.weight"] = g["hpw_w"].sum(0).t()[:, :, None, None]
+        out[f"{h}.header.pointwise_conv.conv.bias"] = g["hpw_b"].sum(0)
+    return out
+
+
+class _DetLossFn(torch.autograd.Function):
+    """(classification, regression) as functions of the head parameters: forward hands out the losses stl_det_loss computed,
+    backward runs the heads' backward launches and the folded-to-raw chain."""
+
+    @staticmethod
+    def forward(ctx, m, tr, names, losses, *params):
+        ctx.m, ctx.tr, ctx.names, ctx.generation = m, tr, names, tr.generation
+        return losses[0].clone(), losses[1].clone()
+
+    @staticmethod
+    def backward(ctx, gc, gr):
+        tr = ctx.tr
+        if ctx.generation != tr.generation:
+            raise RuntimeError(
+                "stlpose_amd.EfficientDetBackbone: backward through a stale forward -- the plan for this batch size ran "
+                f"detection_loss #{tr.generation} after the one (#{ctx.generation}) being differentiated, and its activations "
+                "were overwritten (the reference's autograd keeps one set per call; this engine keeps one per plan).  Call "
+                "backward before the next detection_loss of the same batch size.")
+        with torch.no_grad():
+            tr.backward(ops._st())
+            grads = raw_grads(ctx.m, tr)
+            scale = {"regressor": gr, "classifier": gc}   # dreg / dlogit are the gradients of the regression / classification loss
+            out = [grads[n].contiguous() * scale[n.split(".", 1)[0]] for n in ctx.names]
+        return (None, None, None, None, *out)
+
+
+def detection_loss(m, inputs, targets, alpha: float = 0.25, gamma: float = 2.0, box_weight: float = 50.0) -> Dict[str, torch.Tensor]:
+    """EfficientDetBackbone.detection_loss (documented there)."""
+    if m.compute_dtype != "fp32":
+        raise NotImplementedError(f"EfficientDet.detection_loss: compute_dtype {m.compute_dtype!r}; the heads train in \"fp32\" only")
+    dev = torch.device("cuda", torch.cuda.current_device())
+    srcs = m._float_sources(inputs, dev)
+    gt, offsets = pack_targets(targets, [(int(s.shape[1]), int(s.shape[2])) for s in srcs], m.num_classes)
+    st = ops._st()
+    with torch.no_grad():
+        p, _, keep = m._preprocess(srcs, 1, dev)
+        if p.train is None:
+            p.train = HeadTrain(m, p)
+        tr = p.train
+        p.run(st, upto=p.head_start)
+        tr.forward(st)
+        p._inflight = keep
+        losses, dreg, dlogit, npos = torch.ops.stlpose.det_loss(tr.reg, tr.cls, m._anchor_dev, torch.from_numpy(gt).to(dev),
+                                                                torch.from_numpy(offsets).to(dev), float(alpha), float(gamma),
+                                                                float(box_weight))
+        tr.set_grads(dreg, dlogit)
+        tr.npos = npos
+    named = head_parameters(m)
+    c, r = _DetLossFn.apply(m, tr, [n for n, _ in named], losses, *[q for _, q in named])
+    return {"classification": c, "regression": r}

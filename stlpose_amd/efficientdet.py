@@ -3,11 +3,12 @@
 
 ``EfficientDetBackbone(num_classes, compound_coef)`` holds the reference's parameters and buffers under the reference's key names
 (a reference checkpoint loads with ``strict=True``, also with the ``module.`` prefix of a DataParallel save).  Its forward is
-inference only and runs every layer through csrc/detector.hip (NHWC): the preprocess kernel, the stem, depthwise and
+inference only (``detection_loss`` fine-tunes the heads, see below) and runs every layer through csrc/detector.hip (NHWC): the preprocess kernel, the stem, depthwise and
 squeeze-excitation kernels, the pointwise GEMM on MFMA with BN folded into its weights, the BiFPN node kernel, the shared
 heads writing straight into the concatenated outputs, the decode kernel and the class-aware NMS.  BN is folded into packed fp32
-weights on the device and refolded when any parameter or buffer changes; the launches of one batch size are listed once
-(``_Plan``) and replayed; the last MAX_PLANS batch sizes keep their plans.  Only the kept boxes, scores and labels reach the host.
+weights on the device and refolded when any parameter or buffer changes (only the heads' pieces, in place, when only
+``regressor.*`` / ``classifier.*`` changed: an optimiser step of the fine-tuning keeps the plans); the launches of one batch size
+are listed once (``_Plan``) and replayed; the last MAX_PLANS batch sizes keep their plans.  Only the kept boxes, scores and labels reach the host.
 
 ``compute_dtype`` is "fp32" (the default), "bf16" or "f16".  Parameters, buffers and ``state_dict()`` are fp32 in every mode and
 BN is folded in fp64; a 16-bit mode stores the activations between the stem and the head outputs in that type (the canvas, the
@@ -15,6 +16,11 @@ head outputs ``reg`` / ``cls``, decode and NMS stay fp32), rounds the folded poi
 keeps every other weight, every bias and every sum in fp32.  The depthwise kernel of an MBConv block also writes the
 squeeze-excitation pooling sums, so a 16-bit plan has no pooling pass.  In "f16" a forward whose head outputs hold a non-finite
 value raises FloatingPointError (activations left f16's range: use "bf16"), as HRNet's "mixed" mode does.
+
+``detection_loss(inputs, targets)`` (fp32 only; stlpose_amd/detector_train.py, csrc/detector_train.hip) is the first stage of
+EfficientDet fine-tuning, the counterpart of ``loss_dict = model(imgs / 255, targets)`` in ``02_train_faster_rcnn.py:212``: the
+backbone and the BiFPN are frozen, every BN stays on its running statistics, and ``sum(loss_dict.values()).backward()`` fills
+``.grad`` of the ``regressor.*`` and ``classifier.*`` parameters.
 """
 from __future__ import annotations
 
@@ -347,6 +353,8 @@ class _Plan:
             levels = self._bifpn(cell, lay, levels, p3, p4, p5, c)
         self.feats = levels
         A, nc = m.num_anchors_total, m.num_classes
+        self.head_start = len(self.calls)   # calls[:head_start] is the frozen trunk (detector_train runs the heads itself)
+        self.train = None                   # detector_train.HeadTrain, built by the first detection_loss of this batch size
         self.reg = torch.empty(B, A, 4, device=dev)
         self.cls = torch.empty(B, A, nc, device=dev)
         for head, lay, out, k, act in ((m.regressor, L["regressor"], self.reg, 4, 0), (m.classifier, L["classifier"], self.cls, nc, 2)):
@@ -486,15 +494,16 @@ class _Plan:
         p7_out = node("conv7_down", "p7_w2", [(p7_in, 0), (p6_out, 2)], hs[4])
         return [(p, p.shape[1]) for p in (p3_out, p4_out, p5_out, p6_out, p7_out)]
 
-    def run(self, stream: int) -> None:
+    def run(self, stream: int, upto: Optional[int] = None) -> None:
         st = C.c_void_p(stream)
-        for fn, name, args in self.calls:
+        for fn, name, args in self.calls[:upto]:
             capi.check(fn(*args, st), name)
 
 
 # ------------------------------------------------------------------------------------------------ the model
 class EfficientDetBackbone(nn.Module):
-    """models.EfficientDet (EfficientDetBackbone, src/models/EfficientDet.py:16-133), inference on the MI355X.
+    """models.EfficientDet (EfficientDetBackbone, src/models/EfficientDet.py:16-133) on the MI355X: inference (forward) and
+    fine-tuning of the heads (detection_loss).
 
     forward(inputs, preprocess=True, postprocess=True, threshold=None, iou_threshold=None): inputs a float tensor [B, 3, H, W]
     (04 passes ``img / 255``) or a list of CHW float arrays in [0, 1]; postprocess=False returns (features, regression,
@@ -539,16 +548,44 @@ class EfficientDetBackbone(nn.Module):
         return super().load_state_dict(_strip(dict(state_dict)), strict=strict, assign=assign)
 
     def _state_version(self):
-        return tuple((t.data_ptr(), t._version) for t in list(self.parameters()) + list(self.buffers()))
+        """(trunk, heads): data pointer and version of every parameter and buffer outside / inside regressor.* and classifier.*"""
+        heads = [t for h in (self.regressor, self.classifier) for t in list(h.parameters()) + list(h.buffers())]
+        ids = {id(t) for t in heads}
+        trunk = [t for t in list(self.parameters()) + list(self.buffers()) if id(t) not in ids]
+        return tuple(tuple((t.data_ptr(), t._version) for t in ts) for ts in (trunk, heads))
+
+    def _pack_heads(self, P: _Packer) -> dict:
+        heads = {}
+        for name in ("regressor", "classifier"):
+            hd = getattr(self, name)
+            heads[name] = {"dw": [P.dw(cv.depthwise_conv.conv)[0] for cv in hd.conv_list],
+                           "pw": [[P.pw(cv.pointwise_conv.conv, hd.bn_list[lv][i]) for i, cv in enumerate(hd.conv_list)] for lv in range(5)],
+                           "hdw": P.dw(hd.header.depthwise_conv.conv)[0], "hpw": P.pw(hd.header.pointwise_conv.conv)}
+        return heads
+
+    def _refold_heads(self) -> None:
+        """Only regressor.* / classifier.* changed (an optimiser step of detection_loss): their pieces are the tail of the weight
+        buffers and are rewritten in place, through the same packing as a full refold (bit-identical); the plans stay."""
+        P = _Packer(COMPUTE_DTYPES[self.compute_dtype][0])
+        P.n, P.n16 = self._head_off
+        heads = self._pack_heads(P)
+        assert all(heads[k] == self._layout[k] for k in heads) and P.n == self._wbuf.numel(), "EfficientDet: head layout changed"
+        n0, n16 = self._head_off
+        self._wbuf[n0:].copy_(torch.cat(P.parts).float())
+        if P.parts16:
+            self._wbuf16[n16:].copy_(torch.cat(P.parts16))
 
     def ready(self, dev) -> None:
         """Fold BN and pack every weight into one fp32 device buffer (in a 16-bit mode the pointwise weights into a second one of
-        that type); redone when any parameter or buffer has changed."""
+        that type); redone when any parameter or buffer has changed (_refold_heads when only the heads' have)."""
         dev = _device(dev)
         if self.backbone_net.model._bn0.weight.device != dev:
             self.to(dev)
         v = self._state_version()
-        if v == self._version and self._wbuf is not None and self._wbuf.device == dev:
+        if self._version is not None and v[0] == self._version[0] and self._wbuf is not None and self._wbuf.device == dev:
+            if v[1] != self._version[1]:
+                self._refold_heads()
+                self._version = v
             return
         P = _Packer(COMPUTE_DTYPES[self.compute_dtype][0])
         net = self.backbone_net.model
@@ -576,12 +613,8 @@ class EfficientDetBackbone(nn.Module):
                     lay[key] = P.pw(seq[0].conv, seq[1])
             lay["weights"] = {n: P.add(getattr(cell, n).detach()) for n, _ in _BiFPN.WEIGHTS}
             cells.append(lay)
-        heads = {}
-        for name in ("regressor", "classifier"):
-            hd = getattr(self, name)
-            heads[name] = {"dw": [P.dw(cv.depthwise_conv.conv)[0] for cv in hd.conv_list],
-                           "pw": [[P.pw(cv.pointwise_conv.conv, hd.bn_list[lv][i]) for i, cv in enumerate(hd.conv_list)] for lv in range(5)],
-                           "hdw": P.dw(hd.header.depthwise_conv.conv)[0], "hpw": P.pw(hd.header.pointwise_conv.conv)}
+        self._head_off = (P.n, P.n16)   # the heads are packed last: _refold_heads rewrites the buffers from here on
+        heads = self._pack_heads(P)
         self._wbuf, self._wbuf16 = P.done(dev), P.done16(dev)
         for cell in cells:   # BiFPN weight offsets -> device views
             cell["weights"] = {n: self._wbuf[o:] for n, o in cell["weights"].items()}
@@ -647,6 +680,17 @@ class EfficientDetBackbone(nn.Module):
             self._range_guard(p)
         p._inflight = keep   # the sources and the record table live until the next call
         return p, metas
+
+    def detection_loss(self, inputs, targets, alpha=0.25, gamma=2.0, box_weight=50.0) -> Dict[str, torch.Tensor]:
+        """The fine-tuning counterpart of ``loss_dict = model(imgs / 255, targets)`` (02_train_faster_rcnn.py:212): the focal
+        classification and smooth-L1 box regression losses of RetinaNet / EfficientDet over IoU-assigned anchors.  inputs as
+        forward takes them; targets one dict per image with ``boxes`` [n, 4] (x1, y1, x2, y2 in original pixels) and ``labels``
+        [n] in 1 .. num_classes (n = 0 allowed).  Returns {"classification", "regression"}: fp32 device scalars whose backward
+        fills ``.grad`` of every regressor.* and classifier.* parameter; the backbone and the BiFPN are frozen and every BN runs
+        on its running statistics, whatever ``.training`` is.  fp32 only.  One activation set per batch size: backward before the
+        next detection_loss of that batch size (a stale-forward error otherwise).  See stlpose_amd/detector_train.py."""
+        from . import detector_train
+        return detector_train.detection_loss(self, inputs, targets, alpha, gamma, box_weight)
 
     def _range_guard(self, p: _Plan) -> None:
         """f16 only: an activation past 65504 became inf and reaches the head outputs as inf or NaN (one small reduction)."""

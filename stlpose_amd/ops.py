@@ -420,6 +420,45 @@ def _det_nms(boxes, classes, order, iou_thr: float):
 _define("det_nms(Tensor boxes, Tensor classes, Tensor order, float iou_thr) -> (Tensor, Tensor)", _det_nms,
         lambda b, c, o, t: (b.new_empty(b.shape[0], dtype=torch.int32), b.new_empty(1, dtype=torch.int32)))
 
+
+# ------------------------------------------------------------------ detector fine-tuning loss (csrc/detector_train.hip)
+def _det_loss(reg, cls, anchors, gt, offsets, alpha: float, gamma: float, box_weight: float):
+    if reg.dim() != 3 or reg.shape[2] != 4 or reg.dtype != torch.float32 or reg.shape[0] < 1 or reg.shape[1] < 1:
+        raise ValueError(f"stlpose det_loss: regression must be float32 [B, A, 4], got {reg.dtype} {tuple(reg.shape)}")
+    b, a = reg.shape[:2]
+    if cls.dim() != 3 or tuple(cls.shape[:2]) != (b, a) or cls.shape[2] < 1 or cls.dtype != torch.float32:
+        raise ValueError(f"stlpose det_loss: classification must be float32 [B={b}, A={a}, nc], got {cls.dtype} {tuple(cls.shape)}")
+    if tuple(anchors.shape[-2:]) != (a, 4) or anchors.numel() != a * 4 or anchors.dtype != torch.float32:
+        raise ValueError(f"stlpose det_loss: anchors must be float32 [A={a}, 4], got {anchors.dtype} {tuple(anchors.shape)}")
+    if gt.dim() != 2 or gt.shape[1] != 5 or gt.dtype != torch.float32:
+        raise ValueError(f"stlpose det_loss: gt must be float32 [sum G, 5] (x1, y1, x2, y2, class), got {gt.dtype} {tuple(gt.shape)}")
+    if offsets.dim() != 1 or offsets.shape[0] != b + 1 or offsets.dtype != torch.int32:
+        raise ValueError(f"stlpose det_loss: offsets must be int32 [B + 1 = {b + 1}], got {offsets.dtype} {tuple(offsets.shape)}")
+    if not (0.0 <= alpha <= 1.0) or gamma < 1.0:
+        raise ValueError(f"stlpose det_loss: alpha {alpha} (0 .. 1), gamma {gamma} (>= 1)")
+    if not reg.is_cuda:
+        raise RuntimeError("stlpose det_loss: regression must be on the GPU")
+    _same_device((("classification", cls), ("anchors", anchors), ("gt", gt), ("offsets", offsets)), reg.device)
+    r, c, an, g, o = reg.contiguous(), cls.contiguous(), anchors.contiguous(), gt.contiguous(), offsets.contiguous()
+    nc = c.shape[2]
+    losses = torch.empty(2, device=reg.device)
+    dreg, dlogit = torch.empty_like(r), torch.empty_like(c)
+    npos = torch.empty(b, dtype=torch.int32, device=reg.device)
+    assign = torch.empty(b, a, dtype=torch.int32, device=reg.device)
+    per_image = torch.empty(b, 2, device=reg.device)
+    capi.call("stl_det_loss", r.data_ptr(), c.data_ptr(), an.data_ptr(), g.data_ptr() if g.numel() else None, o.data_ptr(), b, a, nc,
+              float(alpha), float(gamma), float(box_weight), assign.data_ptr(), per_image.data_ptr(), losses.data_ptr(),
+              dreg.data_ptr(), dlogit.data_ptr(), npos.data_ptr(), _st())
+    return losses, dreg, dlogit, npos
+
+
+# losses [2] = (classification, regression); the offsets must be ascending from 0 to gt.shape[0] and the classes inside [0, nc)
+# (EfficientDetBackbone.detection_loss builds them from validated targets)
+_define("det_loss(Tensor regression, Tensor classification, Tensor anchors, Tensor gt, Tensor offsets, float alpha, float gamma, "
+        "float box_weight) -> (Tensor, Tensor, Tensor, Tensor)", _det_loss,
+        lambda r, c, a, g, o, al, ga, bw: (r.new_empty(2), r.new_empty(r.shape), c.new_empty(c.shape),
+                                           r.new_empty(r.shape[0], dtype=torch.int32)))
+
 OPS = ["person_mse", "heatmap_argmax", "final_preds", "flip_merge", "flip_merge_backward", "gaussian_targets", "affine_crop",
        "hrnet_forward", "hrnet_backward", "hrnet_backward_input", "pose_vectors", "pose_distances", "pose_topk", "pose_rank",
-       "box_select", "heatmap_resize_argmax", "det_decode", "det_nms"]
+       "box_select", "heatmap_resize_argmax", "det_decode", "det_nms", "det_loss"]
