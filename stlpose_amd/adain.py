@@ -31,6 +31,7 @@ import torch
 import torch.nn as nn
 
 from . import capi
+from .launch import LaunchList
 from .vgg import Trunk, dtype_code
 
 # (Sequential index, cin, cout, op in front of the conv's reflection pad: None, "pool" or "up")
@@ -103,10 +104,10 @@ def _leaf(parent: nn.Module, idx: int, ci: int, co: int, ks: int) -> nn.Module:
 class _Plan:
     """Static launch list for nb images of H x W: the encoder up to relu4_1 with its statistics and, with ``decode``, the
     decoder behind the affine gather.  Two buffers alternate: a gather writes ``pad``, the conv reads it and writes ``act``,
-    the next gather reads ``act``.  Holds every buffer its launches point into."""
+    the next gather reads ``act``.  Holds every buffer the launches of ``encode`` and ``decode`` (LaunchLists, one ``keep``) point into."""
 
     def __init__(self, mod: "AdaINStylizer", nb: int, H: int, W: int, dev, decode: bool):
-        self.dt, self.esz, self.keep = mod.dtype, (2 if mod.dtype == capi.BF16 else 4), []
+        self.dt, self.esz = mod.dtype, (2 if mod.dtype == capi.BF16 else 4)
         self.nb, self.H, self.W = nb, H, W
         self.img = torch.zeros(nb, 3, H, W, device=dev)
         dt, nb_ = self.dt, nb
@@ -136,32 +137,26 @@ class _Plan:
                        bias=mod.bias_flat.data_ptr() + 4 * mod.bias_off[li], out_relu=relu)
 
         # ---- encoder: conv1_1 (with the 1x1 input conv folded in) on reflection patches, then gather -> conv per layer
-        self.encode = ops = [("stl_adain_input", (dt, self.img.data_ptr(), self.patch.data_ptr(), nb, H, W))]
+        self.encode = ops = LaunchList()
+        ops.add("stl_adain_input", dt, self.img.data_ptr(), self.patch.data_ptr(), nb, H, W)
         conv(ops, 0, H, W, 32, 64, 1, self.patch.data_ptr(), 1)
         ph, pw, ring = H, W, 0          # interior size and ring of what `act` holds
         for li, ci, co, op, h, w in layers[1:len(ENCODER_LAYOUT)]:
-            ops.append(("stl_reflect_gather", (dt, act, pad, nb, ph, pw, ring, ci, _OPS[op], 0, 0)))
+            ops.add("stl_reflect_gather", dt, act, pad, nb, ph, pw, ring, ci, _OPS[op], 0, 0)
             conv(ops, li, h + 2, w + 2, ci, co, 3, pad, 1)
             ph, pw, ring = h, w, 1
-        ops.append(("stl_adain_stats", (dt, act, nb, h8, w8, 1, FEAT, self.nchunk, self.partial.data_ptr(), EPS, self.mean.data_ptr(),
-                                        self.var.data_ptr(), self.sigma.data_ptr())))
+        ops.add("stl_adain_stats", dt, act, nb, h8, w8, 1, FEAT, self.nchunk, self.partial.data_ptr(), EPS, self.mean.data_ptr(),
+                self.var.data_ptr(), self.sigma.data_ptr())
         # ---- decoder: the affine rides on the first gather; stl_adain_output is launched by stylise() (`clamp` is its argument)
-        self.decode = ops = []
+        self.decode = ops = LaunchList(self.encode.keep)
         if decode:
             for li, ci, co, op, h, w in layers[len(ENCODER_LAYOUT):]:
                 first = li == len(ENCODER_LAYOUT)
-                ops.append(("stl_reflect_gather", (dt, act, pad, nb, ph, pw, ring, ci, _OPS[op],
-                                                   self.scale.data_ptr() if first else 0, self.offset.data_ptr() if first else 0)))
+                ops.add("stl_reflect_gather", dt, act, pad, nb, ph, pw, ring, ci, _OPS[op],
+                        self.scale.data_ptr() if first else 0, self.offset.data_ptr() if first else 0)
                 last = li == len(layers) - 1
                 conv(ops, li, h + 2, w + 2, ci, OUT_CO if last else co, 3, pad, 0 if last else 1)
                 ph, pw = h, w
-
-    def run(self, ops, st) -> None:
-        lib = capi.lib()
-        for name, args in ops:
-            rc = getattr(lib, name)(*args, st)
-            if rc != 0:
-                raise RuntimeError(f"{name}: {lib.stl_last_error().decode()}")
 
 
 class AdaINStylizer(nn.Module):
@@ -290,7 +285,7 @@ class AdaINStylizer(nn.Module):
         S, _, h, w = style.shape
         plan = self._plan(dev, S, h, w, False)
         plan.img.copy_(style)
-        plan.run(plan.encode, torch.cuda.current_stream().cuda_stream)
+        plan.encode.run(torch.cuda.current_stream().cuda_stream)
         return plan.mean.clone(), plan.sigma.clone()
 
     @torch.no_grad()
@@ -316,10 +311,10 @@ class AdaINStylizer(nn.Module):
         st = torch.cuda.current_stream().cuda_stream
         plan = self._plan(dev, B, H, W, True)
         plan.img.copy_(content)
-        plan.run(plan.encode, st)
+        plan.encode.run(st)
         capi.call("stl_adain_affine", plan.mean.data_ptr(), plan.var.data_ptr(), mean_s.data_ptr(), sigma_s.data_ptr(), wmix.data_ptr(),
                   B, FEAT, S, float(alpha), EPS, plan.scale.data_ptr(), plan.offset.data_ptr(), st)
-        plan.run(plan.decode, st)
+        plan.decode.run(st)
         capi.call("stl_adain_output", self.dtype, plan.act.data_ptr(), plan.out.data_ptr(), B, H, W, OUT_CO, int(bool(clamp)), st)
         return plan.out.clone()
 

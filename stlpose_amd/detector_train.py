@@ -17,14 +17,14 @@ a frozen feature map: no data gradient is computed for it.
 """
 from __future__ import annotations
 
-import ctypes as C
 from typing import Dict, List, Sequence, Tuple
 
 import numpy as np
 import torch
 
 from . import capi, ops
-from .efficientdet import MAX_SIZE, resize_meta
+from .efficientdet import MAX_SIZE, pointwise_fields, resize_meta
+from .launch import LaunchList
 
 HEADS = ("regressor", "classifier")
 
@@ -83,8 +83,9 @@ class HeadTrain:
     def __init__(self, m, plan):
         self.B, self.dev = B, dev = plan.B, plan.dev
         self.generation = 0   # forwards through these buffers (the stale-backward check of _DetLossFn)
-        self.fwd, self.bwd, self._keep = [], [], []
-        self.hdr = {h: [] for h in HEADS}   # the headers' backward descriptors: their dy is set per call (set_grads)
+        self.fwd = LaunchList()
+        self.bwd = LaunchList(self.fwd.keep)
+        self.hdr = {h: [] for h in HEADS}   # the headers' backward descriptors, the very objects `bwd` passes by reference: set_grads sets their dy
         L = m._layout
         c, A, nc = m.fpn_channels, m.num_anchors_total, m.num_classes
         self.c, self.nlayers = c, len(m.regressor.conv_list)
@@ -126,29 +127,15 @@ class HeadTrain:
                     self._dw_bwd(t[i], self.ga, plan._w(lay["dw"][i]), g["dw"][lv, i], z[i - 1] if i else None, self.gb if i else None, hh)
                 aoff += hh * hh * 9
 
-    def _args(self, args):
-        out = []
-        for a in args:
-            if torch.is_tensor(a):
-                out.append(C.c_void_p(a.data_ptr()))
-                self._keep.append(a)
-            else:
-                out.append(a)
-        return out
-
     def _dw(self, x, y, w, h):
-        self.fwd.append((capi.lib().stl_det_dwconv, "stl_det_dwconv", self._args((x, w, None, y, self.B, h, h, self.c, 3, 1, 0))))
+        self.fwd.add("stl_det_dwconv", x, w, None, y, self.B, h, h, self.c, 3, 1, 0)
 
     def _pw(self, plan, x, out, M, hw, ci, co, pk, act, z=None, img_stride=None, row_stride=None, off=0):
         w, b, kp, np_ = pk
-        p = capi.DetPointwise(x.data_ptr(), plan.wbuf[w:].data_ptr(), plan.wbuf[b:].data_ptr(), None, None, out.data_ptr(), M,
-                              hw * co if img_stride is None else img_stride, co if row_stride is None else row_stride, off, hw, ci, co,
-                              kp, np_, act)
-        self._keep += [p, x, out]
-        if z is None:
-            self.fwd.append((capi.lib().stl_det_pointwise, "stl_det_pointwise", [C.byref(p)]))
-        else:
-            self.fwd.append((capi.lib().stl_det_pointwise_train, "stl_det_pointwise_train", [C.byref(p)] + self._args((z,))))
+        p = capi.DetPointwise(*pointwise_fields(x, plan.wbuf[w:], plan.wbuf[b:], None, None, out, M, hw, ci, co, kp, np_, act,
+                                                img_stride, row_stride, off))
+        self.fwd.keep_alive(x, out)   # the descriptor holds their addresses
+        self.fwd.add(*(("stl_det_pointwise", p) if z is None else ("stl_det_pointwise_train", p, z)))   # _train: also stores the pre-activation z
 
     def _pw_bwd(self, plan, x, dy, dx, M, hw, ci, co, pk, gw, gb, img_stride=None, row_stride=None, off=0):
         """Weight and data gradient of one pointwise layer; dy None: a header, whose dy (dreg / dlogit) set_grads fills in."""
@@ -156,18 +143,16 @@ class HeadTrain:
         p = capi.DetPointwiseBwd(x.data_ptr(), plan.wbuf[w:].data_ptr(), None if dy is None else dy.data_ptr(), dx.data_ptr(),
                                  gw.data_ptr(), gb.data_ptr(), self.pw_part.data_ptr(), M, hw * co if img_stride is None else img_stride,
                                  co if row_stride is None else row_stride, off, hw, ci, co, kp, np_, 0)
-        self._keep += [p, x, gw, gb]
-        self.bwd.append((capi.lib().stl_det_pointwise_bwd_weight, "stl_det_pointwise_bwd_weight", [C.byref(p)]))
-        self.bwd.append((capi.lib().stl_det_pointwise_bwd_data, "stl_det_pointwise_bwd_data", [C.byref(p)]))
+        self.bwd.keep_alive(x, gw, gb)   # the descriptor holds their addresses
+        self.bwd.add("stl_det_pointwise_bwd_weight", p)
+        self.bwd.add("stl_det_pointwise_bwd_data", p)
         return p
 
     def _dw_bwd(self, x, dy, w, gw, z, dx, h):
         """Weight gradient of one depthwise layer and, with dx, its data gradient times swish'(z) of the layer below."""
-        self.bwd.append((capi.lib().stl_det_dwconv_bwd_weight, "stl_det_dwconv_bwd_weight",
-                         self._args((x, dy, self.dw_part, gw, self.B, h, h, self.c))))
+        self.bwd.add("stl_det_dwconv_bwd_weight", x, dy, self.dw_part, gw, self.B, h, h, self.c)
         if dx is not None:
-            self.bwd.append((capi.lib().stl_det_dwconv_bwd_data, "stl_det_dwconv_bwd_data",
-                             self._args((dy, w, z, dx, self.B, h, h, self.c))))
+            self.bwd.add("stl_det_dwconv_bwd_data", dy, w, z, dx, self.B, h, h, self.c)
 
     def set_grads(self, dreg: torch.Tensor, dlogit: torch.Tensor) -> None:
         self.dreg, self.dlogit = dreg, dlogit
@@ -177,16 +162,10 @@ class HeadTrain:
 
     def forward(self, stream: int) -> None:
         self.generation += 1
-        self._run(self.fwd, stream)
+        self.fwd.run(stream)
 
     def backward(self, stream: int) -> None:
-        self._run(self.bwd, stream)
-
-    @staticmethod
-    def _run(calls, stream):
-        st = C.c_void_p(stream)
-        for fn, name, args in calls:
-            capi.check(fn(*args, st), name)
+        self.bwd.run(stream)
 
 
 # ------------------------------------------------------------------------------------------------ autograd

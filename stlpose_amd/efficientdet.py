@@ -24,7 +24,6 @@ backbone and the BiFPN are frozen, every BN stays on its running statistics, and
 """
 from __future__ import annotations
 
-import ctypes as C
 import math
 from typing import Dict, List, Optional
 
@@ -33,6 +32,7 @@ import torch
 import torch.nn as nn
 
 from . import capi, ops  # noqa: F401  (ops registers the stlpose:: custom ops)
+from .launch import LaunchList
 
 BN_EPS = 1e-3
 MAX_SIZE = 512   # preprocess canvas; the reference passes 512 for every compound_coef (EfficientDet.py:96)
@@ -287,14 +287,22 @@ class _Packer:
 
 
 # ------------------------------------------------------------------------------------------------ the launch plan
+def pointwise_fields(x, w, bias, in_scale, residual, out, m, hw, ci, co, kp, np_, act, img_stride=None, row_stride=None, off=0):
+    """The fields of capi.DetPointwise, which DetPointwise16 starts with too: m rows of ci channels onto co, written densely
+    unless the strides and the offset place them inside a larger output.  The tensors are the caller's to keep."""
+    ptrs = [None if t is None else t.data_ptr() for t in (x, w, bias, in_scale, residual, out)]
+    return (*ptrs, m, hw * co if img_stride is None else img_stride, co if row_stride is None else row_stride, off, hw, ci, co, kp, np_, act)
+
+
 class _Plan:
-    """Every launch of one forward at batch B on the 512 canvas, with its buffers: a list of (entry point, arguments) replayed by
+    """Every launch of one forward at batch B on the 512 canvas, with its buffers: ``calls``, a LaunchList replayed by
     ``run``; ``canvas`` is the input, ``feats`` the five BiFPN outputs (NHWC), ``reg`` / ``cls`` the head outputs.  In a 16-bit
     mode every activation buffer has the model's compute type and the *16 entry points are listed; canvas, reg and cls are fp32.
     ``launches`` counts kernel launches (the fp32 squeeze-excitation entry point is two: its pooling pass and the gate)."""
 
     def __init__(self, m: "EfficientDetBackbone", B: int, dev):
-        self.B, self.dev, self.calls, self._keep = B, dev, [], []
+        self.B, self.dev, self.calls = B, dev, LaunchList()
+        self._keep = self.calls.keep
         self.flops = self.bytes = self.launches = 0   # from the shapes: multiply-adds x 2, and every tensor each launch reads or writes once
         self.wbuf, self.wbuf16 = m._wbuf, m._wbuf16
         self.adtype, self.code = COMPUTE_DTYPES[m.compute_dtype]
@@ -307,9 +315,9 @@ class _Plan:
         H = (S + 1) // 2
         x = self._buf(B, H, H, net._conv_stem.conv.out_channels)
         if self.h16:
-            self._call("stl_det_stem16", self.code, self.canvas, self._w(L["stem"][0]), self._w(L["stem"][1]), x, B, S, S, x.shape[3])
+            self._add("stl_det_stem16", self.code, self.canvas, self._w(L["stem"][0]), self._w(L["stem"][1]), x, B, S, S, x.shape[3])
         else:
-            self._call("stl_det_stem", self.canvas, self._w(L["stem"][0]), self._w(L["stem"][1]), x, B, S, S, x.shape[3])
+            self._add("stl_det_stem", self.canvas, self._w(L["stem"][0]), self._w(L["stem"][1]), x, B, S, S, x.shape[3])
         self._cost(2 * x.numel() * 27, 4 * self.canvas.numel() + self.es * x.numel())
         h = H
         feats, specs = [], net.specs
@@ -330,14 +338,14 @@ class _Plan:
                 part = torch.empty(B * nparts * b["mid"], device=dev)
                 self._dw(x, y, lay["dw"][0], lay["dw"][1], h, b["mid"], b["k"], b["s"], 1, part)
                 h, x = ho, y
-                self._call("stl_det_se16", part, B, h * h, nparts, b["mid"], b["se"], self._w(se[0]), self._w(se[1]), self._w(se[2]),
+                self._add("stl_det_se16", part, B, h * h, nparts, b["mid"], b["se"], self._w(se[0]), self._w(se[1]), self._w(se[2]),
                            self._w(se[3]), scale)
                 self._cost(part.numel() + 4 * B * b["mid"] * b["se"], 4 * part.numel())
             else:
                 self._dw(x, y, lay["dw"][0], lay["dw"][1], h, b["mid"], b["k"], b["s"], 1)
                 h, x = ho, y
                 part = torch.empty(capi.lib().stl_det_se_workspace(B) * b["mid"], device=dev)
-                self._call("stl_det_se", x, B, h * h, b["mid"], b["se"], self._w(se[0]), self._w(se[1]), self._w(se[2]), self._w(se[3]),
+                self._add("stl_det_se", x, B, h * h, b["mid"], b["se"], self._w(se[0]), self._w(se[1]), self._w(se[2]), self._w(se[3]),
                            part, scale)
                 self.launches += 1
                 self._cost(x.numel() + 4 * B * b["mid"] * b["se"], 4 * x.numel())
@@ -382,65 +390,44 @@ class _Plan:
         self.flops += int(flops)
         self.bytes += int(nbytes)
 
-    def _call(self, name, *args):
-        conv = []
-        for a in args:
-            if torch.is_tensor(a):
-                conv.append(C.c_void_p(a.data_ptr()))
-                self._keep.append(a)
-            elif a is None:
-                conv.append(None)
-            else:
-                conv.append(a)
-        self.calls.append((getattr(capi.lib(), name), name, conv))
+    def _add(self, name, *args):
+        self.calls.add(name, *args)
         self.launches += 1
 
     def _dw(self, x, y, w, bias, h, c, k, s, act, partial=None):
         """Depthwise k x k / s on the h x h map x -> y; 16-bit with ``partial``: also the squeeze-excitation pooling sums."""
         if self.h16:
-            self._call("stl_det_dwconv16", self.code, x, self._w(w), self._w(bias), y, partial, self.B, h, h, c, k, s, act)
+            self._add("stl_det_dwconv16", self.code, x, self._w(w), self._w(bias), y, partial, self.B, h, h, c, k, s, act)
         else:
-            self._call("stl_det_dwconv", x, self._w(w), self._w(bias), y, self.B, h, h, c, k, s, act)
+            self._add("stl_det_dwconv", x, self._w(w), self._w(bias), y, self.B, h, h, c, k, s, act)
         self._cost(2 * y.numel() * k * k, self.es * (x.numel() + y.numel()) + (0 if partial is None else 4 * partial.numel()))
 
     def _pw(self, x, out, B, hw, ci, co, pk, act, in_scale=None, residual=None, img_stride=None, row_stride=None, off=0):
         w, b, kp, np_ = pk
         m = B * hw
-        self._keep += [x, out] + [t for t in (in_scale, residual) if t is not None]
-        self.launches += 1
+        common = pointwise_fields(x, (self.wbuf16 if self.h16 else self.wbuf)[w:], self._w(b), in_scale, residual, out, m, hw, ci, co,
+                                  kp, np_, act, img_stride, row_stride, off)
+        self.calls.keep_alive(x, out, in_scale, residual)   # the descriptor holds their addresses
         if self.h16:
-            p = capi.DetPointwise16(x.data_ptr(), self.wbuf16[w:].data_ptr(), None if b is None else self.wbuf[b:].data_ptr(),
-                                    None if in_scale is None else in_scale.data_ptr(), None if residual is None else residual.data_ptr(),
-                                    out.data_ptr(), m, hw * co if img_stride is None else img_stride,
-                                    co if row_stride is None else row_stride, off, hw, ci, co, kp, np_, act, self.code,
-                                    1 if out.dtype == torch.float32 else 0)
+            self._add("stl_det_pointwise16", capi.DetPointwise16(*common, self.code, 1 if out.dtype == torch.float32 else 0))
             self._cost(2 * m * ci * co, self.es * (m * ci + kp * np_ + (m * co if residual is not None else 0)) + out.element_size() * m * co)
-            self.calls.append((capi.lib().stl_det_pointwise16, "stl_det_pointwise16", [C.byref(p)]))
-            self._keep.append(p)
-            return
-        p = capi.DetPointwise(x.data_ptr(), self.wbuf[w:].data_ptr(), None if b is None else self.wbuf[b:].data_ptr(),
-                              None if in_scale is None else in_scale.data_ptr(), None if residual is None else residual.data_ptr(),
-                              out.data_ptr(), B * hw, hw * co if img_stride is None else img_stride,
-                              co if row_stride is None else row_stride, off, hw, ci, co, kp, np_, act)
-        self._cost(2 * m * ci * co, 4 * (m * ci + m * co * (2 if residual is not None else 1) + kp * np_))
-        self.calls.append((capi.lib().stl_det_pointwise, "stl_det_pointwise", [C.byref(p)]))
-        self._keep.append(p)
+        else:
+            self._add("stl_det_pointwise", capi.DetPointwise(*common))
+            self._cost(2 * m * ci * co, 4 * (m * ci + m * co * (2 if residual is not None else 1) + kp * np_))
 
     def _fuse(self, out, terms, wparam):
         f = capi.DetFuse()
         f.B, f.H, f.W, f.C, f.nterms = out.shape[0], out.shape[1], out.shape[2], out.shape[3], len(terms)
         for i, (t, mode) in enumerate(terms):
             f.t[i] = capi.DetTerm(t.data_ptr(), mode, t.shape[1], t.shape[2], 0)
-            self._keep.append(t)
         f.wparam = None if wparam is None else wparam.data_ptr()
         f.out = out.data_ptr()
-        self._keep += [out, f]
+        self.calls.keep_alive(out, *[t for t, _ in terms])   # the descriptor holds their addresses
         self._cost(out.numel() * (2 * len(terms) + 4), self.es * (out.numel() + sum(t.numel() for t, _ in terms)))
-        self.launches += 1
         if self.h16:
-            self.calls.append((capi.lib().stl_det_fuse16, "stl_det_fuse16", [C.byref(f), self.code]))
+            self._add("stl_det_fuse16", f, self.code)
         else:
-            self.calls.append((capi.lib().stl_det_fuse, "stl_det_fuse", [C.byref(f)]))
+            self._add("stl_det_fuse", f)
 
     def _sep(self, x, pk, h, c):
         """SeparableConvBlock: depthwise 3x3 (no bias) then 1x1 with bias and BN folded, no activation."""
@@ -495,9 +482,7 @@ class _Plan:
         return [(p, p.shape[1]) for p in (p3_out, p4_out, p5_out, p6_out, p7_out)]
 
     def run(self, stream: int, upto: Optional[int] = None) -> None:
-        st = C.c_void_p(stream)
-        for fn, name, args in self.calls[:upto]:
-            capi.check(fn(*args, st), name)
+        self.calls.run(stream, 0, upto)
 
 
 # ------------------------------------------------------------------------------------------------ the model

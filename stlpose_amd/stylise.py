@@ -50,19 +50,19 @@ class GatysStylizer:
         st = torch.cuda.current_stream().cuda_stream
         it = self._plan(dev, B, H, W, "buffer", True)
         it.trunk.img.copy_(content)
-        it.trunk.run(st)
+        it.trunk.ops.run(st)
         it.ctarget.view(torch.uint8).copy_(it.trunk.acts[CONTENT_TAP])
         Bs, _, Hs, Ws = style.shape
         sp = self._plan(dev, Bs, Hs, Ws, None, False)
         sp.trunk.img.copy_(style)
-        sp.trunk.run(st)
+        sp.trunk.ops.run(st)
         return it, sp.grams()
 
     # ---------------------------------------------------------------- one iteration, in two halves (tools/stylise_bench.py times them)
     def forward_loss(self, it: StylePlan, img: torch.Tensor, style_grams):
         """Forward of the B images `img` against the cached targets: (total loss, per-tap (G, A)) on device."""
         it.trunk.img.copy_(img)
-        it.trunk.run(torch.cuda.current_stream().cuda_stream)
+        it.trunk.ops.run(torch.cuda.current_stream().cuda_stream)
         s_loss = torch.zeros((), dtype=torch.float64, device=img.device)
         grams = []
         for G, A in zip(it.grams(), style_grams):

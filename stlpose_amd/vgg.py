@@ -29,6 +29,7 @@ import torch
 import torch.nn as nn
 
 from . import capi
+from .launch import LaunchList
 
 # (slice, features index, cin, cout); 'p' marks a 2x2 max-pool in front of the conv
 VGG16_LAYOUT = [
@@ -77,11 +78,12 @@ class Trunk:
     ``rows`` = [(cin, cout, 2x2 max-pool in front)] of a module packed by ``ready``, each with bias + ReLU.
 
     ``hook(trunk, i)`` runs right after conv i is listed and may list launches of its own behind it.  grad: ``wk`` also
-    holds the data-gradient layouts of the convs behind the forward ones (``tab[i].bwd_off``).  The plan holds every
-    buffer its launches point into (``keep``)."""
+    holds the data-gradient layouts of the convs behind the forward ones (``tab[i].bwd_off``).  ``ops`` is the forward
+    ``LaunchList``; the plan holds every buffer its launches point into (``keep``, the list's)."""
 
     def __init__(self, mod: nn.Module, rows, nb: int, H: int, W: int, dev, hook, grad: bool = False):
-        self.ops, self.keep, self.acts, self.dims = [], [], [], []   # acts, dims: per conv its output [nb, h, w, co], (h, w, co)
+        self.ops = LaunchList()
+        self.keep, self.acts, self.dims = self.ops.keep, [], []   # acts, dims: per conv its output [nb, h, w, co], (h, w, co)
         self.dt, self.esz = mod.dtype, (2 if mod.dtype == capi.BF16 else 4)
         self.tdt = torch.bfloat16 if self.dt == capi.BF16 else torch.float32
         self.w_flat = mod.w_flat
@@ -113,12 +115,12 @@ class Trunk:
             return t
 
         x = act(nb, H, W, 32)
-        self.ops.append(("stl_patch3x3", (self.dt, self.img.data_ptr(), x.data_ptr(), nb, H, W, 1, mod.mean.data_ptr(), mod.std.data_ptr())))
+        self.ops.add("stl_patch3x3", self.dt, self.img.data_ptr(), x.data_ptr(), nb, H, W, 1, mod.mean.data_ptr(), mod.std.data_ptr())
         h, w, c = H, W, 32
         for i, (_, co, pool) in enumerate(rows):
             if pool:
                 y = act(nb, h // 2, w // 2, c)
-                self.ops.append(("stl_maxpool2x2", (self.dt, x.data_ptr(), y.data_ptr(), nb, h, w, c)))
+                self.ops.add("stl_maxpool2x2", self.dt, x.data_ptr(), y.data_ptr(), nb, h, w, c)
                 x, h, w = y, h // 2, w // 2
             y = act(nb, h, w, co)
             self.conv(self.ops, nb, h, w, c, co, 1 if i == 0 else 3, x.data_ptr(), self.wk.data_ptr() + tab[i].fwd_off * self.esz,
@@ -129,28 +131,19 @@ class Trunk:
             hook(self, i)
 
     def conv(self, ops, B, h, w, ci, co, ks, src, wptr, out, bias=0, out_relu=0, addend=0, mask_z=0) -> None:
-        """List a stride-1 'same' conv of the NHWC map at `src` onto `out`."""
+        """List a stride-1 'same' conv of the NHWC map at `src` onto `out` in the LaunchList `ops` (needs ``self.dt`` only)."""
         p = capi.Conv()
         p.dtype, p.B, p.Hi, p.Wi, p.Ci, p.Ho, p.Wo, p.Co = self.dt, B, h, w, ci, h, w, co
         p.ks, p.stride, p.shape = ks, 1, -1
         p.src.x, p.src.mode = src, capi.SRC_PLAIN
         p.w, p.out, p.bias, p.out_relu, p.addend, p.mask_z = wptr, out, bias, out_relu, addend, mask_z
         capi.call("stl_conv_plan", C.byref(p))
-        self.keep.append(p)
-        ops.append(("stl_conv_forward", (C.byref(p),)))
+        ops.add("stl_conv_forward", p)
 
     def prep_weights(self, st) -> None:
         """``w_flat`` -> the kernel layouts in ``wk``."""
         capi.call("stl_weight_prep", self.dt, self.w_flat.data_ptr(), self.wk.data_ptr(), self.wtab.data_ptr(), self.nconv,
                   self.wblocks, st)
-
-    def run(self, st, ops=None) -> None:
-        """Launch `ops` (default: the forward list) on stream `st`."""
-        lib = capi.lib()
-        for name, args in self.ops if ops is None else ops:
-            rc = getattr(lib, name)(*args, st)
-            if rc != 0:
-                raise RuntimeError(f"{name}: {lib.stl_last_error().decode()}")
 
 
 class VGGPerceptualLoss(nn.Module):
@@ -189,11 +182,11 @@ class VGGPerceptualLoss(nn.Module):
                 s, x = SLICE_END[i], t.acts[i].data_ptr()
                 h, w, c = t.dims[i]
                 half = (B2 // 2) * h * w * c
-                t.ops.append(("stl_l1_partial", (t.dt, x, x + half * t.esz, half, partial[s].data_ptr(), 1024)))
-                t.ops.append(("stl_sum_partials", (partial[s].data_ptr(), 1024, 1.0 / half, loss.data_ptr(), int(s > 0))))
+                t.ops.add("stl_l1_partial", t.dt, x, x + half * t.esz, half, partial[s].data_ptr(), 1024)
+                t.ops.add("stl_sum_partials", partial[s].data_ptr(), 1024, 1.0 / half, loss.data_ptr(), int(s > 0))
 
         trunk = Trunk(self, [row[2:] for row in VGG16_LAYOUT], B2, H, W, dev, l1)
-        trunk.keep.append(partial)
+        trunk.ops.keep_alive(partial)
         return trunk, loss
 
     def forward(self, input: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
@@ -219,5 +212,5 @@ class VGGPerceptualLoss(nn.Module):
         trunk, loss = plan
         trunk.img.copy_(x)
         trunk.prep_weights(st)
-        trunk.run(st)
+        trunk.ops.run(st)
         return loss.clone()

@@ -30,6 +30,7 @@ import torch
 import torch.nn as nn
 
 from . import capi
+from .launch import LaunchList
 from .vgg import Trunk, add_conv, dtype_code, ready
 
 # (features index, cin, cout, 2x2 max-pool in front): torchvision VGG19 "E" up to conv5_1
@@ -77,28 +78,24 @@ class StylePlan:
                 else:
                     self.ctarget = torch.zeros(n, dtype=t.tdt, device=dev)
                     tgt = self.ctarget.data_ptr()
-                t.ops.append(("stl_l2_partial", (dt, x, tgt, n, self.cpartial.data_ptr(), 1024)))
-                t.ops.append(("stl_sum_partials", (self.cpartial.data_ptr(), 1024, 1.0 / n, self.content.data_ptr(), 0)))
+                t.ops.add("stl_l2_partial", dt, x, tgt, n, self.cpartial.data_ptr(), 1024)
+                t.ops.add("stl_sum_partials", self.cpartial.data_ptr(), 1024, 1.0 / n, self.content.data_ptr(), 0)
                 self.ctarget_ptr = tgt
             if i in STYLE_TAPS and len(gram_imgs):
                 from .engine import choose_tile
                 th, tw = choose_tile(1, h, w, 1, 1, esz, bn_cols=32, maxhalo=576)
                 npt = math.ceil((h + 1) / th) * math.ceil(w / tw)
-                wg0 = capi.Wgrad()
-                wg0.dtype, wg0.B, wg0.Hi, wg0.Wi, wg0.Ci, wg0.Ho, wg0.Wo, wg0.Co, wg0.ks, wg0.stride = dt, 1, h, w, c, h, w, c, 1, 1
-                ctile = capi.lib().stl_wgrad_chunk(C.byref(wg0))
+                shape = (dt, 1, h, w, c, h, w, c, 1, 1)   # one image's map as a 1x1 conv of itself: dtype, B, Hi, Wi, Ci, Ho, Wo, Co, ks, stride
+                ctile = capi.lib().stl_wgrad_chunk(C.byref(capi.Wgrad(*shape)))
                 chunks = math.ceil(c / ctile) ** 2
                 nsplit = max(1, min(npt, max(1, 256 // chunks)))
                 slabs = torch.zeros(len(gram_imgs), nsplit, c, c, dtype=torch.float32, device=dev)
                 for j, b in enumerate(gram_imgs):
-                    wg = capi.Wgrad()
-                    wg.dtype, wg.B, wg.Hi, wg.Wi, wg.Ci, wg.Ho, wg.Wo, wg.Co, wg.ks, wg.stride = dt, 1, h, w, c, h, w, c, 1, 1
-                    wg.TH, wg.TW, wg.nsplit = th, tw, nsplit
+                    wg = capi.Wgrad(*shape, th, tw, nsplit)
                     ptr = x + b * img_elems * esz
                     wg.h.x, wg.h.mode, wg.g.x, wg.g.mode = ptr, capi.SRC_PLAIN, ptr, capi.SRC_PLAIN
                     wg.partial = slabs[j].data_ptr()
-                    t.keep.append(wg)
-                    t.ops.append(("stl_conv_wgrad", (C.byref(wg),)))
+                    t.ops.add("stl_conv_wgrad", wg)
                 self.slabs.append((slabs, 1.0 / (c * h * w)))
 
         self.trunk = Trunk(mod, [row[1:] for row in VGG19_LAYOUT], nb, H, W, dev, taps, grad)
@@ -116,7 +113,7 @@ class StylePlan:
         adjoint.  Gradients ping-pong between two buffers per resolution."""
         t, B = self.trunk, self.B
         dt, esz = t.dt, t.esz
-        self.bwd_ops = []
+        self.bwd_ops = LaunchList(t.keep)   # shares the trunk's keep
         self.cscale = torch.zeros((), dtype=torch.float32, device=dev)   # 2 wc / n, set by backward()
         self.gw = {}                                                     # style tap -> [B, C, C] weight ks * (G_b - A_b)
         self.dimg = torch.zeros(B, 3, self.H, self.W, dtype=torch.float32, device=dev)
@@ -142,12 +139,12 @@ class StylePlan:
                            addend=(g + b * pix) if g is not None else 0, mask_z=f + b * pix)
                 g = out
             elif i == CONTENT_TAP:   # + wc * 2 (F_x - F_c) / n, then the ReLU mask, in place
-                self.bwd_ops.append(("stl_l2_backward", (dt, f, self.ctarget_ptr, g, B * h * w * c, self.cscale.data_ptr(), 1)))
+                self.bwd_ops.add("stl_l2_backward", dt, f, self.ctarget_ptr, g, B * h * w * c, self.cscale.data_ptr(), 1)
             _, ci, co, pool = VGG19_LAYOUT[i]
             out = other(h, w, g)
             if i == 0:   # conv1_1: 1x1 onto the 32-wide patches, then the patch adjoint (with 1 / std) to the NCHW image
                 t.conv(self.bwd_ops, B, h, w, co, 32, 1, g, t.wk.data_ptr() + t.tab[0].bwd_off * esz, out)
-                self.bwd_ops.append(("stl_patch3x3_backward", (dt, out, self.dimg.data_ptr(), B, self.H, self.W, 1, mod.std.data_ptr())))
+                self.bwd_ops.add("stl_patch3x3_backward", dt, out, self.dimg.data_ptr(), B, self.H, self.W, 1, mod.std.data_ptr())
                 break
             hp, wp, cp = t.dims[i - 1]
             fp = t.acts[i - 1].data_ptr()
@@ -156,7 +153,7 @@ class StylePlan:
                    mask_z=fp if masked and not pool else 0)
             if pool:
                 dst = other(hp, wp, None)
-                self.bwd_ops.append(("stl_maxpool2x2_backward", (dt, fp, out, dst, B, hp, wp, cp, int(masked))))
+                self.bwd_ops.add("stl_maxpool2x2_backward", dt, fp, out, dst, B, hp, wp, cp, int(masked))
                 out = dst
             g = out
 
@@ -173,7 +170,7 @@ class StylePlan:
             self.cscale.copy_(wc * (2.0 / (B * h * w * c)))
         else:
             self.cscale.fill_(wc * 2.0 / (B * h * w * c))
-        self.trunk.run(torch.cuda.current_stream().cuda_stream, self.bwd_ops)
+        self.bwd_ops.run(torch.cuda.current_stream().cuda_stream)
         return self.dimg
 
 
@@ -249,7 +246,7 @@ class VGG19StyleLoss(nn.Module):
             plan = self._plans[key] = StylePlan(self, B3, H, W, dev, B, "batch", list(range(B)) + list(range(2 * B, 3 * B)), grad)
         plan.trunk.img.copy_(xin)
         plan.trunk.prep_weights(st)
-        plan.trunk.run(st)
+        plan.trunk.ops.run(st)
         # C x C Gram matrices: split-K slabs -> sum, scale, squared distance (a few hundred KB of bookkeeping)
         s_loss = torch.zeros((), dtype=torch.float64, device=dev)
         grams = []

@@ -77,9 +77,9 @@ def families(m, content, dt, reps):
     _, _, by = cost(dt, True)
     out = {}
     for fam, names in FAMILIES.items():
-        ops = [op for op in plan.encode + plan.decode if op[0] in names]
-        sec = timed(lambda: plan.run(ops, st), reps)
-        out[fam] = {"launches": len(ops), "ms": sec * 1e3}
+        ops = [lst.select(lambda n: n in names) for lst in (plan.encode, plan.decode)]
+        sec = timed(lambda: [lst.run(st) for lst in ops], reps)
+        out[fam] = {"launches": sum(map(len, ops)), "ms": sec * 1e3}
         if fam in by:
             out[fam].update(bytes=by[fam], tb_per_s=by[fam] / sec / 1e12, share_of_hbm_peak=by[fam] / sec / PEAK_BW)
     sec = timed(lambda: capi.call("stl_adain_output", m.dtype, plan.act.data_ptr(), plan.out.data_ptr(), B, H, W, 8, 1, st), reps)
