@@ -595,6 +595,62 @@ int stl_det_dwconv_bwd_data(const float* dy, const float* w, const float* z, flo
 int stl_det_dwconv_bwd_weight(const float* x, const float* dy, float* partial, float* dw, int B, int H, int W, int C, void* stream);
 int stl_det_dwconv_bwd_parts(int64_t npix);
 
+/* -- Fine-tuning the heads of a 16-bit model (EfficientDetBackbone(compute_dtype="f16").detection_loss): f16 forward, bf16 gradients,
+ * the recipe of the pose network's mixed mode.  The arithmetic contract, which tests/detector_train16_ref.py emulates:
+ *   forward   exactly the 16-bit inference plan: the depthwise output d, the swish output t and the kept pre-activation z are stored
+ *             in dtype, each rounded once from its fp32 value (t = round(swish(z_fp32)), so reg / cls equal inference bit for bit);
+ *             reg, cls, stl_det_loss and its dreg / dlogit stay fp32.
+ *   backward  gradients in flight are bf16, rounded once when stored.  Pointwise data gradient dX = dY W'^T: dY bf16 (a header's
+ *             fp32 dreg / dlogit is rounded to bf16 in registers), W'^T from a bf16 pack rounded once from the same fp64 fold as the
+ *             forward pack, fp32 accumulation, dX stored bf16.  Pointwise weight gradient dW' = X^T dY, db' = sum dY: X is the stored
+ *             dtype tensor converted to bf16 while staging, dY bf16 (db' adds the same bf16 values the MFMA sees), fp32 sums, dW' and
+ *             db' stored fp32.  Depthwise: taps fp32, fp32 VALU arithmetic, dY bf16, swish'(z) in fp32 from the stored z, dX stored
+ *             bf16; the weight gradient multiplies x (dtype) and dY (bf16) in fp32, fp32 partial sums, dw fp32.
+ * Every reduction in a fixed order, no atomics: two runs are bitwise equal.  16-bit tensors need C % 8 == 0 and 16-byte alignment as
+ * above; a failed check sets stl_last_error and launches nothing.
+ * tools/detector_train_bench.py times the f16 step, its trunk and the heads' share next to the fp32 ones in one run and fails if the
+ * f16 step is not faster than fp32 at batch 32 (profiles/detector_train_bench.json).  Step fp32 -> f16 at batch 32: D0 30.5 -> 20.0 ms,
+ * D3 59.6 -> 30.0 ms; trunk 12.8 -> 4.5 and 29.4 -> 10.0 ms; heads' share (with the f16 step's host wait for the non-finite check)
+ * 17.7 -> 15.5 and 30.2 -> 20.0 ms.  At batch 8: D3 30.4 -> 22.2 ms (heads 17.6 -> 16.6); D0 16.4 -> 14.2 ms with a heads' share
+ * that is not below fp32's (10.9 -> 11.8 ms): short kernels, the same 150 launches, and per step a refold of the transposed packs
+ * on the host and one wait for the device. */
+/* stl_det_pointwise16 with act 1 (swish), no residual and a 16-bit output that also keeps the pre-activation: z dtype [M, Co] =
+ * round(x w + bias), out = round(swish(x w + bias)).  The kernel of stl_det_pointwise16: out equals that call's bit for bit. */
+int stl_det_pointwise16_train(const StlDetPointwise16* p, void* z, void* stream);
+/* Backward of stl_det_pointwise16 (no in_scale, no residual; the activation's derivative is already in dy), both on
+ * v_mfma_f32_16x16x32_bf16.  x xdtype (STL_F16 or STL_BF16) [M, Ci], Ci % 8 == 0.  dy is addressed as in StlDetPointwiseBwd:
+ * dy_f32 0: bf16, Co, strides and offset multiples of 8 (16-byte loads); dy_f32 1: the strided fp32 [B, A, k] tensor of a header,
+ * any Co, rounded to bf16 in registers.  wt is the bf16 transposed pack: the forward's layout with the roles of k and n swapped,
+ * [Np / 16][Kp / 32][64][8] with element ((kt * (Kp / 32) + ns) * 64 + 16 * g + r) * 8 + i = W'[k = 16 kt + r][n = 32 ns + 8 g + i],
+ * zero-padded to Kp = ceil(Co / 32) * 32 and Np = ceil(Ci / 64) * 64.
+ *   bwd_data:   dx bf16 [M, Ci] = sum_n dy[m, n] W'[k, n]; dY rows are read straight from global memory, 8 consecutive n per lane
+ *   bwd_weight: dw fp32 [Ci][Co] = sum_m x[m, k] dy[m, n], db fp32 [Co] = sum_m dy[m, n]: the contraction runs over m, so 64-row
+ *               tiles of x and dy are staged through LDS transposed (two rows paired in registers, dword writes, 16-byte reads)
+ * Rows past M and channels past Ci / Co contribute exact zeros and are never read.  bwd_weight splits M into
+ * stl_det_pointwise16_bwd_slabs(M) slabs and adds them in slab order; partial holds slabs * (Ci * Co + Co) floats. */
+typedef struct {
+    const void* x;
+    const void* wt;
+    const void* dy;
+    void* dx;
+    float* dw;
+    float* db;
+    float* partial;
+    int64_t M, dy_img_stride, dy_row_stride, dy_off;
+    int32_t HW, Ci, Co, Kp, Np, xdtype, dy_f32, pad_;
+} StlDetPointwise16Bwd;
+int stl_det_pointwise16_bwd_data(const StlDetPointwise16Bwd* p, void* stream);
+int stl_det_pointwise16_bwd_weight(const StlDetPointwise16Bwd* p, void* stream);
+int stl_det_pointwise16_bwd_slabs(int64_t M);
+/* Backward of stl_det_dwconv16 with k 3, s 1, no bias, no activation, 8 channels per thread and 16-byte accesses (C % 8 == 0).
+ * bwd_data: dy bf16, w fp32 [3][3][C], z zdtype [B, H, W, C] or NULL, dx bf16 = (flipped-tap sum in fp32) * swish'(z).  bwd_weight:
+ * x xdtype, dy bf16, dw fp32 [3][3][C] through stl_det_dwconv16_bwd_parts(B * H * W) fp32 partial sums (partial: parts * 9 * C
+ * floats) added in part order. */
+int stl_det_dwconv16_bwd_data(const void* dy, const float* w, const void* z, void* dx, int B, int H, int W, int C, int zdtype, void* stream);
+int stl_det_dwconv16_bwd_weight(int xdtype, const void* x, const void* dy, float* partial, float* dw, int B, int H, int W, int C,
+                                void* stream);
+int stl_det_dwconv16_bwd_parts(int64_t npix);
+
 /* ---- AdaIN feed-forward stylisation (csrc/adain.hip; stlpose_amd/adain.py).  No reference counterpart: the network is the published
  * one (Huang & Belongie 2017), restated in tests/adain_ref.py.  The 3x3 convs pad by reflection and stl_conv pads with zeros, so every
  * conv runs as a "same" conv on an explicitly padded (H+2) x (W+2) NHWC map whose output ring is never read.  dtype STL_F32 or STL_BF16

@@ -138,6 +138,12 @@ class DetPointwiseBwd(C.Structure):
                 ("Kp", i32), ("Np", i32), ("pad_", i32)]
 
 
+class DetPointwise16Bwd(C.Structure):
+    _fields_ = [("x", vp), ("wt", vp), ("dy", vp), ("dx", vp), ("dw", vp), ("db", vp), ("partial", vp), ("M", i64),
+                ("dy_img_stride", i64), ("dy_row_stride", i64), ("dy_off", i64), ("HW", i32), ("Ci", i32), ("Co", i32),
+                ("Kp", i32), ("Np", i32), ("xdtype", i32), ("dy_f32", i32), ("pad_", i32)]
+
+
 class DetTerm(C.Structure):
     _fields_ = [("x", vp), ("mode", i32), ("H", i32), ("W", i32), ("pad_", i32)]
 
@@ -239,6 +245,13 @@ SIGNATURES = {
     "stl_det_dwconv_bwd_data": [vp, vp, vp, vp, i32, i32, i32, i32, vp],
     "stl_det_dwconv_bwd_weight": [vp, vp, vp, vp, i32, i32, i32, i32, vp],
     "stl_det_dwconv_bwd_parts": [i64],
+    "stl_det_pointwise16_train": [C.POINTER(DetPointwise16), vp, vp],
+    "stl_det_pointwise16_bwd_data": [C.POINTER(DetPointwise16Bwd), vp],
+    "stl_det_pointwise16_bwd_weight": [C.POINTER(DetPointwise16Bwd), vp],
+    "stl_det_pointwise16_bwd_slabs": [i64],
+    "stl_det_dwconv16_bwd_data": [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp],
+    "stl_det_dwconv16_bwd_weight": [i32, vp, vp, vp, vp, i32, i32, i32, i32, vp],
+    "stl_det_dwconv16_bwd_parts": [i64],
     "stl_adain_input": [i32, vp, vp, i32, i32, i32, vp],
     "stl_reflect_gather": [i32, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp],
     "stl_adain_stats": [i32, vp, i32, i32, i32, i32, i32, i32, vp, f32, vp, vp, vp, vp],

@@ -365,6 +365,11 @@ __device__ __forceinline__ void block_argmax(const float* row, int n, float& bv,
 
 static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 
+// The argument checks of the detector's 16-bit entry points (detector.hip, detector_train.hip).
+static inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+#define DET16_DTYPE(name, dtype) STL_CHECK((dtype) == STL_BF16 || (dtype) == STL_F16, name ": dtype %d (STL_BF16 or STL_F16)", (int)(dtype))
+#define DET16_C8(name, C) STL_CHECK((C) >= 8 && (C) % 8 == 0, name ": C %d (16-bit tensors need C %% 8 == 0)", (int)(C))
+
 // ---------------------------------------------------------------- launches
 // Every kernel of the library is launched through STL_LAUNCH: hipLaunchKernel on the caller's stream, with each argument
 // converted to the type of the kernel's parameter.

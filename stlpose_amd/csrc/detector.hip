@@ -23,6 +23,8 @@
 //   stl_det_se16         stl_det_se from those sums, added in slot order
 //   stl_det_pointwise16  the GEMM on v_mfma_f32_16x16x32_{bf16,f16}, operands straight from global memory (no LDS): an NHWC
 //                        row is the operand layout, the weights are packed to one 16-byte load per lane; 16-bit or strided fp32 output
+//   stl_det_pointwise16_train  the same launch with swish and a 16-bit output, also keeping its pre-activation z rounded once to
+//                        the 16-bit type (the 16-bit heads' training forward; the backward kernels are in detector_train.hip)
 //   stl_det_fuse16       the BiFPN node on 16-bit tensors, attention weights fp32
 //
 // f16 activations past 65504 become inf; the model checks its head outputs (FloatingPointError) and points to bf16.  On the
@@ -586,8 +588,9 @@ __global__ __launch_bounds__(256) void dwconv16_kernel(const T* __restrict__ x, 
 // channels (8 accumulators), a workgroup 128 pixels.
 constexpr int kPw16M = 128, kPw16N = 64;
 
-template <typename T, bool F32OUT>
-__global__ __launch_bounds__(256) void pointwise16_kernel(const StlDetPointwise16 p) {
+// KEEPZ (stl_det_pointwise16_train, 16-bit output only): also z[m, n] = the fp32 pre-activation rounded once to T.
+template <typename T, bool F32OUT, bool KEEPZ = false>
+__global__ __launch_bounds__(256) void pointwise16_kernel(const StlDetPointwise16 p, T* __restrict__ z) {
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, g = lane >> 4;
     const int ksteps = p.Kp >> 5;
     const T* x = reinterpret_cast<const T*>(p.x);
@@ -646,8 +649,14 @@ __global__ __launch_bounds__(256) void pointwise16_kernel(const StlDetPointwise1
             float bv[4] = {0.f, 0.f, 0.f, 0.f}, v[4];
             if (p.bias) unpack<float>(ldg16(p.bias + n), bv);   // bias is padded to Np
 #pragma unroll
+            for (int r = 0; r < 4; ++r) v[r] = acc[h][j][r] + bv[r];
+            if constexpr (KEEPZ) {
+                uint2 zv;
+                zv.x = pack2<T>(v[0], v[1]), zv.y = pack2<T>(v[2], v[3]);
+                *reinterpret_cast<uint2*>(z + m * p.Co + n) = zv;
+            }
+#pragma unroll
             for (int r = 0; r < 4; ++r) {
-                v[r] = acc[h][j][r] + bv[r];
                 if (p.act == 1) v[r] = swishf(v[r]);
                 else if (p.act == 2) v[r] = sigmoidf_(v[r]);
             }
@@ -734,8 +743,6 @@ __global__ __launch_bounds__(256) void fuse16_kernel(const StlDetFuse f) {
     for (int j = 0; j < 8; ++j) acc[j] = swishf(acc[j]);
     stg16(o, pack<T>(acc));
 }
-
-__host__ inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 }  // namespace
 
@@ -830,8 +837,7 @@ extern "C" int stl_det_fuse(const StlDetFuse* f, void* stream) {
 }
 
 // ------------------------------------------------------------------------------------------------ 16-bit entry points
-#define DET16_DTYPE(name, dtype) STL_CHECK((dtype) == STL_BF16 || (dtype) == STL_F16, name ": dtype %d (STL_BF16 or STL_F16)", (int)(dtype))
-#define DET16_C8(name, C) STL_CHECK((C) >= 8 && (C) % 8 == 0, name ": C %d (16-bit tensors need C %% 8 == 0)", (int)(C))
+// (al16, DET16_DTYPE and DET16_C8 are in common.cuh, shared with detector_train.hip)
 
 extern "C" int stl_det_stem16(int dtype, const float* x, const float* w, const float* bias, void* out, int B, int H, int W, int Co,
                               void* stream) {
@@ -892,7 +898,7 @@ extern "C" int stl_det_se16(const float* partial, int B, int HW, int nparts, int
     return 0;
 }
 
-extern "C" int stl_det_pointwise16(const StlDetPointwise16* p, void* stream) {
+static int pointwise16_launch(const StlDetPointwise16* p, void* z, hipStream_t st) {
     STL_CHECK(p && p->x && p->w && p->out, "det_pointwise16: null pointer");
     DET16_DTYPE("det_pointwise16", p->dtype);
     STL_CHECK(p->M >= 1 && p->HW >= 1 && p->Co >= 1, "det_pointwise16: M %lld HW %d Co %d", (long long)p->M, p->HW, p->Co);
@@ -909,14 +915,24 @@ extern "C" int stl_det_pointwise16(const StlDetPointwise16* p, void* stream) {
     STL_CHECK(mb < (1ll << 31), "det_pointwise16: M too large");
     const dim3 grid((unsigned)mb, p->Np / kPw16N);
     if (p->dtype == STL_BF16) {
-        if (p->out_f32) STL_LAUNCH((pointwise16_kernel<__bf16, true>), grid, dim3(256), 0, ST, *p);
-        else STL_LAUNCH((pointwise16_kernel<__bf16, false>), grid, dim3(256), 0, ST, *p);
+        if (z) STL_LAUNCH((pointwise16_kernel<__bf16, false, true>), grid, dim3(256), 0, st, *p, (__bf16*)z);
+        else if (p->out_f32) STL_LAUNCH((pointwise16_kernel<__bf16, true>), grid, dim3(256), 0, st, *p, (__bf16*)nullptr);
+        else STL_LAUNCH((pointwise16_kernel<__bf16, false>), grid, dim3(256), 0, st, *p, (__bf16*)nullptr);
     } else {
-        if (p->out_f32) STL_LAUNCH((pointwise16_kernel<f16, true>), grid, dim3(256), 0, ST, *p);
-        else STL_LAUNCH((pointwise16_kernel<f16, false>), grid, dim3(256), 0, ST, *p);
+        if (z) STL_LAUNCH((pointwise16_kernel<f16, false, true>), grid, dim3(256), 0, st, *p, (f16*)z);
+        else if (p->out_f32) STL_LAUNCH((pointwise16_kernel<f16, true>), grid, dim3(256), 0, st, *p, (f16*)nullptr);
+        else STL_LAUNCH((pointwise16_kernel<f16, false>), grid, dim3(256), 0, st, *p, (f16*)nullptr);
     }
     STL_LAUNCH_CHECK("det_pointwise16");
     return 0;
+}
+
+extern "C" int stl_det_pointwise16(const StlDetPointwise16* p, void* stream) { return pointwise16_launch(p, nullptr, ST); }
+
+extern "C" int stl_det_pointwise16_train(const StlDetPointwise16* p, void* z, void* stream) {
+    STL_CHECK(z && (((uintptr_t)z) & 7) == 0, "det_pointwise16_train: z null or not 8-byte aligned");
+    STL_CHECK(p && p->act == 1 && !p->residual && !p->out_f32, "det_pointwise16_train: the layer must end in swish, without a residual, with a 16-bit output");
+    return pointwise16_launch(p, z, ST);
 }
 
 extern "C" int stl_det_fuse16(const StlDetFuse* f, int dtype, void* stream) {

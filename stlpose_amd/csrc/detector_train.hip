@@ -1,7 +1,7 @@
 // Fine-tuning the EfficientDet heads on gfx950 (stlpose_amd/detector_train.py): the detection loss with its head-output gradients
 // and the backward kernels of the shared heads (depthwise 3x3 -> pointwise + frozen BN -> swish, five levels, one header).  The
 // reference has no detection loss for its EfficientDet (src/models/EfficientDet.py takes no targets); this is the published
-// RetinaNet / EfficientDet loss, restated in tests/detector_train_ref.py.  fp32, NHWC.
+// RetinaNet / EfficientDet loss, restated in tests/detector_train_ref.py.  NHWC; fp32 first, the 16-bit heads further down.
 //
 //   stl_det_loss                  IoU assignment of every anchor (positive >= 0.5, negative < 0.4, ignored between), focal
 //                                 classification + smooth-L1 regression, and dL/dreg, dL/dlogit for the whole batch: one launch
@@ -16,6 +16,15 @@
 //
 // The training forward's pointwise launch (stl_det_pointwise_train, swish with its pre-activation kept) is the forward kernel
 // itself and lives in detector.hip.  Every reduction runs in a fixed order (no float atomics): two runs give bitwise equal results.
+//
+// A model with compute_dtype "f16" trains its heads in 16 bit (further down): forward tensors d, z, t in f16, each rounded once from
+// its fp32 value; gradients in flight bf16, rounded once when stored; every sum fp32; dW', db', dw fp32.
+//   stl_det_pointwise16_bwd_data    dX = dY W'^T on v_mfma_f32_16x16x32_bf16: dY bf16 (a header's fp32 dreg / dlogit rounded in
+//                                   registers) straight from global memory, W'^T from a bf16 transposed pack in the forward's tile layout
+//   stl_det_pointwise16_bwd_weight  dW' = X^T dY, db' = sum dY on the same MFMA: X (f16) converted to bf16 while staged, both operands
+//                                   transposed through LDS (two rows paired in registers), slabs of M added in slab order
+//   stl_det_dwconv16_bwd_data / _weight  8 channels per thread and 16-byte accesses; taps and arithmetic fp32, swish'(z) from the stored z
+// (stl_det_pointwise16_train, the 16-bit training forward's launch, is pointwise16_kernel in detector.hip.)
 #include "common.cuh"
 
 namespace {
@@ -357,6 +366,270 @@ __global__ __launch_bounds__(256) void dwconv_bwd_weight_kernel(const float* __r
     }
 }
 
+// ================================================================================================ 16-bit heads (compute_dtype "f16")
+// The backward of a 16-bit head.  Forward tensors (d, z, t) are stored in the model's 16-bit type, gradients in flight are bf16
+// (rounded once when stored), every sum is fp32, and dW', db', dw come out in fp32 as in the fp32 path.  Both pointwise kernels run
+// on v_mfma_f32_16x16x32_bf16.
+
+// 8 consecutive n of dY row m as a bf16 MFMA operand: bf16 [.., Co] straight (Co % 8 == 0), or a header's fp32 dreg / dlogit
+// rounded to bf16 in registers (any Co, any offset: element loads).  Zero past Co.
+__device__ __forceinline__ V16 load_dy8(const StlDetPointwise16Bwd& p, int64_t base, int n) {
+    if (n >= p.Co) return zero16();
+    if (!p.dy_f32) return ldg16(reinterpret_cast<const __bf16*>(p.dy) + base + n);
+    const float* r = reinterpret_cast<const float*>(p.dy) + base + n;
+    float f[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) f[i] = n + i < p.Co ? r[i] : 0.f;
+    return pack<__bf16>(f);
+}
+
+__device__ __forceinline__ int64_t dy_row16(const StlDetPointwise16Bwd& p, int64_t m) {
+    const int64_t img = m / p.HW, pix = m - img * p.HW;
+    return img * p.dy_img_stride + pix * p.dy_row_stride + p.dy_off;
+}
+
+// dX[m, k] = sum_n dY[m, n] W'[k, n]: the forward's GEMM (detector.hip, pointwise16_kernel) with dY in the place of x and the bf16
+// transposed pack wt [Np / 16][Kp / 32][64][8] (Np over Ci, Kp over Co) in the place of w; no LDS.  A wave owns 32 rows x 64 k,
+// a lane ends up with 4 consecutive k of one row and stores them as one 8-byte piece of bf16.  Grid (M / 128, Np / 64).
+__global__ __launch_bounds__(256) void pointwise16_bwd_data_kernel(const StlDetPointwise16Bwd p) {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, g = lane >> 4;
+    const int nsteps = p.Kp >> 5;
+    int64_t row[2], base[2];
+    bool ok[2];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        row[h] = (int64_t)blockIdx.x * 128 + wv * 32 + h * 16 + (lane & 15);
+        ok[h] = row[h] < p.M;
+        base[h] = ok[h] ? dy_row16(p, row[h]) : 0;
+    }
+    f32x4 acc[2][4];
+#pragma unroll
+    for (int h = 0; h < 2; ++h)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[h][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    const V16* wp = reinterpret_cast<const V16*>(p.wt) + (int64_t)blockIdx.y * 4 * nsteps * 64 + lane;
+    for (int ns = 0; ns < nsteps; ++ns) {
+        const int n = ns * 32 + g * 8;
+        V16 a[2];
+#pragma unroll
+        for (int h = 0; h < 2; ++h) a[h] = ok[h] ? load_dy8(p, base[h], n) : zero16();
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const V16 bw = wp[((int64_t)j * nsteps + ns) * 64];
+#pragma unroll
+            for (int h = 0; h < 2; ++h) mma16<__bf16>(acc[h][j], bw, a[h]);
+        }
+    }
+    __bf16* dx = reinterpret_cast<__bf16*>(p.dx);
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        if (!ok[h]) continue;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int k = blockIdx.y * 64 + j * 16 + g * 4;
+            if (k >= p.Ci) continue;   // Ci % 8 == 0: the 4 channels are inside and 8-byte aligned
+            uint2 ov;
+            ov.x = pack2<__bf16>(acc[h][j][0], acc[h][j][1]), ov.y = pack2<__bf16>(acc[h][j][2], acc[h][j][3]);
+            *reinterpret_cast<uint2*>(dx + row[h] * p.Ci + k) = ov;
+        }
+    }
+}
+
+constexpr int kW16Step = 64;                       // rows of M per LDS stage: two 32-deep MFMA steps
+constexpr int kW16Ld = kW16Step / 2 + 4;           // dwords per LDS row: 64 rows of M as bf16 pairs, padded (144 bytes: 16-byte aligned)
+constexpr int kSlab16Min = 256, kSlab16Max = 256;  // at least 256 rows per slab, at most 256 slabs
+
+// Dword index of the 16-byte piece q (8 rows of M: 8 q .. 8 q + 7) of a staged column: the pieces of a column are swizzled by the
+// column's group of 8, so that the 32 lanes of a dword write (8 column groups x 4 row pairs) meet 32 different banks.
+__device__ __forceinline__ int w16_at(int col, int q) { return col * kW16Ld + ((q ^ ((col >> 3) & 7)) << 2); }
+
+static inline int64_t slab_rows16(int64_t M) {
+    const int64_t per = (M + kSlab16Max - 1) / kSlab16Max;
+    const int64_t r = (per + kW16Step - 1) / kW16Step * kW16Step;
+    return r < kSlab16Min ? kSlab16Min : r;
+}
+
+// dW'[k, n] = sum_m X[m, k] dY[m, n], db'[n] = sum_m dY[m, n] over one slab of rows.  The contraction runs over m, so both MFMA
+// operands need 8 consecutive rows per lane: a workgroup stages 64 rows x 64 columns of X and of dY through LDS, transposed.  A
+// thread loads 8 columns of two consecutive rows (16 bytes each; X converted from its 16-bit type to bf16, an fp32 dY rounded to
+// bf16), pairs them in registers and writes 8 dwords (row m, row m + 1) to s[column][m / 2] (16-byte pieces swizzled, w16_at); a lane then reads its 8 rows of one
+// column as 16 bytes.  Wave w owns k rows 16w .. 16w + 15 and 64 n columns (A = X^T: row = k, B = dY: column = n; D: row k =
+// 4 (lane >> 4) + r, column n = lane & 15).  Rows past the slab, k past Ci and n past Co are staged as zeros.  The k-tile-0
+// workgroups also add db' from the staged (bf16) dY: each wave its 16 rows of every stage in row order, then the four waves in
+// wave order.  partial[slab][Ci * Co + Co].  Grid (slabs, Ci tiles, Co tiles).
+template <typename TX>
+__global__ __launch_bounds__(256) void pointwise16_bwd_weight_kernel(const StlDetPointwise16Bwd p, int64_t rows) {
+    __shared__ __attribute__((aligned(16))) uint32_t sx[64 * kW16Ld];   // [k][m pair]
+    __shared__ __attribute__((aligned(16))) uint32_t sy[64 * kW16Ld];   // [n][m pair]
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, g = lane >> 4;
+    const int k0 = blockIdx.y * 64, n0 = blockIdx.z * 64;
+    const int64_t mbeg = (int64_t)blockIdx.x * rows;
+    const int64_t mend = mbeg + rows < p.M ? mbeg + rows : p.M;
+    f32x4 acc[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    float bacc = 0.f;
+    const int cg = (tid & 7) * 8, mp = tid >> 3;   // staging: columns cg .. cg + 7 of rows 2 mp, 2 mp + 1
+    const int wpos = (((mp >> 2) ^ (tid & 7)) << 2) | (mp & 3);   // w16_at(column, mp >> 2) + (mp & 3) without the row
+    const TX* x = reinterpret_cast<const TX*>(p.x);
+    for (int64_t ms = mbeg; ms < mend; ms += kW16Step) {
+        float fx[2][8];
+        V16 vy[2];
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+            const int64_t row = ms + 2 * mp + q;
+            const bool ok = row < mend;
+            V16 vx = zero16();
+            if (ok && k0 + cg < p.Ci) vx = ldg16(x + row * p.Ci + k0 + cg);   // Ci % 8 == 0: inside or outside as a whole
+            unpack<TX>(vx, fx[q]);
+            vy[q] = ok ? load_dy8(p, dy_row16(p, row), n0 + cg) : zero16();
+        }
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            sx[(cg + i) * kW16Ld + wpos] = pack2<__bf16>(fx[0][i], fx[1][i]);
+            const uint32_t lo = (vy[0].w[i >> 1] >> ((i & 1) * 16)) & 0xFFFFu, hi = (vy[1].w[i >> 1] >> ((i & 1) * 16)) & 0xFFFFu;
+            sy[(cg + i) * kW16Ld + wpos] = lo | (hi << 16);
+        }
+        __syncthreads();
+#pragma unroll
+        for (int s = 0; s < kW16Step / 32; ++s) {
+            const V16 a = *reinterpret_cast<const V16*>(&sx[w16_at(wv * 16 + (lane & 15), s * 4 + g)]);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const V16 b = *reinterpret_cast<const V16*>(&sy[w16_at(j * 16 + (lane & 15), s * 4 + g)]);
+                mma16<__bf16>(acc[j], a, b);
+            }
+        }
+        if (blockIdx.y == 0) {   // wave w adds rows 16 w .. 16 w + 15 of the stage for column `lane`: two 16-byte reads
+#pragma unroll
+            for (int q = 0; q < 2; ++q) {
+                const V16 v = *reinterpret_cast<const V16*>(&sy[w16_at(lane, wv * 2 + q)]);
+                float f[8];
+                unpack<__bf16>(v, f);
+#pragma unroll
+                for (int i = 0; i < 8; ++i) bacc += f[i];
+            }
+        }
+        __syncthreads();
+    }
+    if (blockIdx.y == 0) {   // the four waves' sums, added in wave order (the loop's last barrier freed sx)
+        float* red = reinterpret_cast<float*>(sx);
+        red[wv * 64 + lane] = bacc;
+        __syncthreads();
+        bacc = (red[lane] + red[64 + lane]) + (red[128 + lane] + red[192 + lane]);
+    }
+    float* part = p.partial + (int64_t)blockIdx.x * ((int64_t)p.Ci * p.Co + p.Co);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int n = n0 + j * 16 + (lane & 15);
+        if (n >= p.Co) continue;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int k = k0 + wv * 16 + g * 4 + r;
+            if (k < p.Ci) part[(int64_t)k * p.Co + n] = acc[j][r];
+        }
+    }
+    if (blockIdx.y == 0 && tid < 64 && n0 + tid < p.Co) part[(int64_t)p.Ci * p.Co + n0 + tid] = bacc;
+}
+
+// The depthwise data gradient, 8 channels per thread: dy bf16, taps fp32, z in TZ (swish'(z) in fp32 from the stored z), dx bf16.
+template <typename TZ>
+__global__ __launch_bounds__(256) void dwconv16_bwd_data_kernel(const __bf16* __restrict__ dy, const float* __restrict__ w,
+                                                                const TZ* __restrict__ z, __bf16* __restrict__ dx, int B, int H, int W,
+                                                                int C) {
+    const int C8 = C >> 3;
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= (int64_t)B * H * W * C8) return;
+    const int c0 = (int)(e % C8) * 8;
+    const int64_t pix = e / C8;
+    const int x = (int)(pix % W), y = (int)((pix / W) % H), b = (int)(pix / ((int64_t)W * H));
+    float acc[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) acc[j] = 0.f;
+#pragma unroll
+    for (int ky = 0; ky < 3; ++ky) {
+        const int oy = y + 1 - ky;
+        if (oy < 0 || oy >= H) continue;
+#pragma unroll
+        for (int kx = 0; kx < 3; ++kx) {
+            const int ox = x + 1 - kx;
+            if (ox < 0 || ox >= W) continue;
+            float f[8], wf[8];
+            unpack<__bf16>(ldg16(dy + (((int64_t)b * H + oy) * W + ox) * C + c0), f);
+            const float* wp = w + (ky * 3 + kx) * C + c0;
+            unpack<float>(ldg16(wp), wf), unpack<float>(ldg16(wp + 4), wf + 4);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) acc[j] += f[j] * wf[j];
+        }
+    }
+    if (z) {
+        float zf[8];
+        unpack<TZ>(ldg16(z + pix * C + c0), zf);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) acc[j] *= dswishf(zf[j]);
+    }
+    stg16(dx + pix * C + c0, pack<__bf16>(acc));
+}
+
+constexpr int kDw16PartMax = 512, kDw16PartPix = 256;   // at most 512 partial sums, at least 256 pixels each
+static inline int dw16_bwd_parts(int64_t npix) {
+    const int64_t p = (npix + kDw16PartPix - 1) / kDw16PartPix;
+    return (int)(p < 1 ? 1 : (p > kDw16PartMax ? kDw16PartMax : p));
+}
+
+// partial[part][9][C]: a workgroup is 8 channel groups (64 channels) x 32 pixel lanes over the part's pixels; a thread adds its
+// pixels in pixel order (fp32 products of x in TX and dy in bf16), then, tap by tap, one thread per channel adds the 32 lanes in
+// lane order.
+template <typename TX>
+__global__ __launch_bounds__(256) void dwconv16_bwd_weight_kernel(const TX* __restrict__ x, const __bf16* __restrict__ dy,
+                                                                  float* __restrict__ partial, int64_t npix, int H, int W, int C,
+                                                                  int64_t per) {
+    __shared__ float red[32][65];
+    const int cl = threadIdx.x & 7, pl = threadIdx.x >> 3;
+    const int c0 = (blockIdx.y * 8 + cl) * 8;
+    const bool cok = c0 < C;   // C % 8 == 0: a group of 8 is inside or outside as a whole
+    const int64_t p0 = (int64_t)blockIdx.x * per, p1 = p0 + per < npix ? p0 + per : npix;
+    float acc[9][8];
+#pragma unroll
+    for (int t = 0; t < 9; ++t)
+#pragma unroll
+        for (int j = 0; j < 8; ++j) acc[t][j] = 0.f;
+    if (cok) {
+        for (int64_t p = p0 + pl; p < p1; p += 32) {
+            const int px = (int)(p % W), py = (int)((p / W) % H);
+            float gf[8];
+            unpack<__bf16>(ldg16(dy + p * C + c0), gf);
+#pragma unroll
+            for (int ky = 0; ky < 3; ++ky) {
+                const int iy = py - 1 + ky;
+                if (iy < 0 || iy >= H) continue;
+#pragma unroll
+                for (int kx = 0; kx < 3; ++kx) {
+                    const int ix = px - 1 + kx;
+                    if (ix < 0 || ix >= W) continue;
+                    float xf[8];
+                    unpack<TX>(ldg16(x + (p + (int64_t)(ky - 1) * W + (kx - 1)) * C + c0), xf);
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) acc[ky * 3 + kx][j] += xf[j] * gf[j];
+                }
+            }
+        }
+    }
+    const int c = blockIdx.y * 64 + threadIdx.x;
+#pragma unroll
+    for (int t = 0; t < 9; ++t) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) red[pl][cl * 8 + j] = acc[t][j];
+        __syncthreads();
+        if (threadIdx.x < 64 && c < C) {
+            float a = 0.f;
+            for (int q = 0; q < 32; ++q) a += red[q][threadIdx.x];
+            partial[((int64_t)blockIdx.x * 9 + t) * C + c] = a;
+        }
+        __syncthreads();
+    }
+}
+
 }  // namespace
 
 #define ST ((hipStream_t)stream)
@@ -437,5 +710,92 @@ extern "C" int stl_det_dwconv_bwd_weight(const float* x, const float* dy, float*
     const int64_t n = 9ll * C;
     STL_LAUNCH(sum_parts_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ST, (const float*)partial, parts, n, n, dw, dw);
     STL_LAUNCH_CHECK("det_dwconv_bwd_weight_sum");
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------ 16-bit entry points
+// (al16, DET16_DTYPE and DET16_C8: common.cuh)
+
+static int pointwise16_bwd_check(const StlDetPointwise16Bwd* p, const char* name) {
+    STL_CHECK(p && p->dy, "%s: null pointer", name);
+    STL_CHECK(p->M >= 1 && p->HW >= 1 && p->Co >= 1, "%s: M %lld HW %d Co %d", name, (long long)p->M, p->HW, p->Co);
+    STL_CHECK(p->Ci >= 8 && p->Ci % 8 == 0, "%s: C %d (16-bit tensors need C %% 8 == 0)", name, p->Ci);
+    STL_CHECK(p->dy_f32 == 0 || p->dy_f32 == 1, "%s: dy_f32 %d", name, p->dy_f32);
+    STL_CHECK(p->dy_img_stride >= 0 && p->dy_row_stride >= p->Co && p->dy_off >= 0, "%s: dy strides %lld %lld offset %lld", name,
+              (long long)p->dy_img_stride, (long long)p->dy_row_stride, (long long)p->dy_off);
+    if (p->dy_f32) STL_CHECK(((uintptr_t)p->dy & 3) == 0, "%s: dy must be 4-byte aligned", name);
+    else STL_CHECK(p->Co % 8 == 0 && p->dy_img_stride % 8 == 0 && p->dy_row_stride % 8 == 0 && p->dy_off % 8 == 0 && al16(p->dy),
+                   "%s: a bf16 dy needs Co %d, strides and offset that are multiples of 8 and a 16-byte aligned pointer", name, p->Co);
+    STL_CHECK((p->M + 127) / 128 < (1ll << 31), "%s: M too large", name);
+    return 0;
+}
+
+extern "C" int stl_det_pointwise16_bwd_data(const StlDetPointwise16Bwd* p, void* stream) {
+    if (pointwise16_bwd_check(p, "det_pointwise16_bwd_data")) return 1;
+    STL_CHECK(p->wt && p->dx, "det_pointwise16_bwd_data: null pointer");
+    STL_CHECK(p->Np % 64 == 0 && p->Np >= p->Ci && p->Kp % 32 == 0 && p->Kp >= p->Co,
+              "det_pointwise16_bwd_data: transposed pack %d x %d for %d x %d", p->Kp, p->Np, p->Co, p->Ci);
+    STL_CHECK(al16(p->wt) && al16(p->dx), "det_pointwise16_bwd_data: wt and dx must be 16-byte aligned");
+    STL_LAUNCH(pointwise16_bwd_data_kernel, dim3((unsigned)((p->M + 127) / 128), p->Np / 64), dim3(256), 0, ST, *p);
+    STL_LAUNCH_CHECK("det_pointwise16_bwd_data");
+    return 0;
+}
+
+extern "C" int stl_det_pointwise16_bwd_slabs(int64_t M) { return M >= 1 ? (int)((M + slab_rows16(M) - 1) / slab_rows16(M)) : 0; }
+
+extern "C" int stl_det_pointwise16_bwd_weight(const StlDetPointwise16Bwd* p, void* stream) {
+    if (pointwise16_bwd_check(p, "det_pointwise16_bwd_weight")) return 1;
+    DET16_DTYPE("det_pointwise16_bwd_weight", p->xdtype);
+    STL_CHECK(p->x && p->partial && p->dw && p->db, "det_pointwise16_bwd_weight: null pointer");
+    STL_CHECK(al16(p->x), "det_pointwise16_bwd_weight: x must be 16-byte aligned");
+    STL_CHECK(p->Ci <= 65535 * 64 && p->Co <= 65535 * 64, "det_pointwise16_bwd_weight: Ci %d Co %d", p->Ci, p->Co);
+    const int64_t rows = slab_rows16(p->M);
+    const int slabs = stl_det_pointwise16_bwd_slabs(p->M);
+    const dim3 grid(slabs, ceil_div(p->Ci, 64), ceil_div(p->Co, 64));
+    if (p->xdtype == STL_BF16) STL_LAUNCH(pointwise16_bwd_weight_kernel<__bf16>, grid, dim3(256), 0, ST, *p, rows);
+    else STL_LAUNCH(pointwise16_bwd_weight_kernel<f16>, grid, dim3(256), 0, ST, *p, rows);
+    STL_LAUNCH_CHECK("det_pointwise16_bwd_weight");
+    const int64_t n0 = (int64_t)p->Ci * p->Co, n = n0 + p->Co;
+    STL_LAUNCH(sum_parts_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ST, (const float*)p->partial, slabs, n, n0, p->dw, p->db);
+    STL_LAUNCH_CHECK("det_pointwise16_bwd_weight_sum");
+    return 0;
+}
+
+extern "C" int stl_det_dwconv16_bwd_data(const void* dy, const float* w, const void* z, void* dx, int B, int H, int W, int C, int zdtype,
+                                         void* stream) {
+    STL_CHECK(B >= 1 && H >= 1 && W >= 1, "det_dwconv16_bwd_data: B %d, %d x %d", B, H, W);
+    DET16_C8("det_dwconv16_bwd_data", C);
+    if (z) DET16_DTYPE("det_dwconv16_bwd_data", zdtype);
+    STL_CHECK(dy && w && dx, "det_dwconv16_bwd_data: null pointer");
+    STL_CHECK(al16(dy) && al16(w) && al16(z) && al16(dx), "det_dwconv16_bwd_data: dy, w, z and dx must be 16-byte aligned");
+    const int64_t n = (int64_t)B * H * W * (C / 8);
+    STL_CHECK((n + 255) / 256 < (1ll << 31), "det_dwconv16_bwd_data: too large");
+    const dim3 grid((unsigned)((n + 255) / 256));
+    if (zdtype == STL_BF16) STL_LAUNCH(dwconv16_bwd_data_kernel<__bf16>, grid, dim3(256), 0, ST, (const __bf16*)dy, w, (const __bf16*)z, (__bf16*)dx, B, H, W, C);
+    else STL_LAUNCH(dwconv16_bwd_data_kernel<f16>, grid, dim3(256), 0, ST, (const __bf16*)dy, w, (const f16*)z, (__bf16*)dx, B, H, W, C);
+    STL_LAUNCH_CHECK("det_dwconv16_bwd_data");
+    return 0;
+}
+
+extern "C" int stl_det_dwconv16_bwd_parts(int64_t npix) { return npix >= 1 ? dw16_bwd_parts(npix) : 0; }
+
+extern "C" int stl_det_dwconv16_bwd_weight(int xdtype, const void* x, const void* dy, float* partial, float* dw, int B, int H, int W, int C,
+                                           void* stream) {
+    DET16_DTYPE("det_dwconv16_bwd_weight", xdtype);
+    STL_CHECK(B >= 1 && H >= 1 && W >= 1, "det_dwconv16_bwd_weight: B %d, %d x %d", B, H, W);
+    DET16_C8("det_dwconv16_bwd_weight", C);
+    STL_CHECK(C <= 65535 * 64, "det_dwconv16_bwd_weight: C %d", C);
+    STL_CHECK(x && dy && partial && dw, "det_dwconv16_bwd_weight: null pointer");
+    STL_CHECK(al16(x) && al16(dy), "det_dwconv16_bwd_weight: x and dy must be 16-byte aligned");
+    const int64_t npix = (int64_t)B * H * W;
+    const int parts = dw16_bwd_parts(npix);
+    const int64_t per = (npix + parts - 1) / parts;
+    const dim3 grid(parts, ceil_div(C, 64));
+    if (xdtype == STL_BF16) STL_LAUNCH(dwconv16_bwd_weight_kernel<__bf16>, grid, dim3(256), 0, ST, (const __bf16*)x, (const __bf16*)dy, partial, npix, H, W, C, per);
+    else STL_LAUNCH(dwconv16_bwd_weight_kernel<f16>, grid, dim3(256), 0, ST, (const f16*)x, (const __bf16*)dy, partial, npix, H, W, C, per);
+    STL_LAUNCH_CHECK("det_dwconv16_bwd_weight");
+    const int64_t n = 9ll * C;
+    STL_LAUNCH(sum_parts_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ST, (const float*)partial, parts, n, n, dw, dw);
+    STL_LAUNCH_CHECK("det_dwconv16_bwd_weight_sum");
     return 0;
 }

@@ -14,6 +14,13 @@ level) from the header down through csrc/detector_train.hip and produces gradien
 (s, t the frozen BN's scale and shift) per level; ``fold_chain`` carries them to W, b, gamma and beta in a few elementwise torch
 ops, and the weights shared by the five levels sum their five contributions.  The first depthwise layer of a (head, level) reads
 a frozen feature map: no data gradient is computed for it.
+
+A model with ``compute_dtype="f16"`` trains in 16 bit, by the recipe of the pose network's mixed mode: the trunk runs as the 16-bit
+inference plan's launches, the heads' forward tensors (every depthwise output d, pre-activation z and swish output t) are f16, the
+gradients in flight are bf16, every sum is fp32, and the folded gradients come out in the same fp32 ``grads`` tensors, so
+``fold_chain`` and ``raw_grads`` do not change (the contract is stated in include/stlpose_hip.h at stl_det_pointwise16_train).  The
+data gradient of a pointwise layer reads a bf16 transposed pack of the folded weight (efficientdet.pack_transposed).  ``"bf16"`` does
+not train: its forward error is several times that of f16.
 """
 from __future__ import annotations
 
@@ -94,10 +101,16 @@ class HeadTrain:
         lib = capi.lib()
         h0 = plan.feats[0][1]
         m0 = B * h0 * h0
-        self.ga, self.gb = torch.empty(m0 * c, device=dev), torch.empty(m0 * c, device=dev)   # gradients in flight, reused
+        self.h16, self.code, self.adtype = plan.h16, plan.code, plan.adtype   # 16-bit: d / z / t in adtype, ga / gb bf16
+        if self.h16:
+            m._ensure_transposed()
+            self.wbufT, self.layoutT = m._wbufT16, m._layoutT
+        gdtype = torch.bfloat16 if self.h16 else torch.float32
+        self.ga, self.gb = torch.empty(m0 * c, device=dev, dtype=gdtype), torch.empty(m0 * c, device=dev, dtype=gdtype)   # gradients in flight, reused
         kmax = max(c, 9 * max(4, nc))
-        self.pw_part = torch.empty(lib.stl_det_pointwise_bwd_slabs(m0) * (c * kmax + kmax), device=dev)
-        self.dw_part = torch.empty(lib.stl_det_dwconv_bwd_parts(m0) * 9 * c, device=dev)
+        sfx = "16" if self.h16 else ""
+        self.pw_part = torch.empty(getattr(lib, f"stl_det_pointwise{sfx}_bwd_slabs")(m0) * (c * kmax + kmax), device=dev)
+        self.dw_part = torch.empty(getattr(lib, f"stl_det_dwconv{sfx}_bwd_parts")(m0) * 9 * c, device=dev)
         self.grads: Dict[str, Dict[str, torch.Tensor]] = {}
         for name, out, k, act in (("regressor", self.reg, 4, 0), ("classifier", self.cls, nc, 2)):
             lay, n = L[name], self.nlayers
@@ -108,7 +121,7 @@ class HeadTrain:
             aoff = 0
             for lv, (f, hh) in enumerate(plan.feats):
                 M = B * hh * hh
-                buf = lambda: torch.empty(B, hh, hh, c, device=dev)   # noqa: E731
+                buf = lambda: torch.empty(B, hh, hh, c, device=dev, dtype=self.adtype)   # noqa: E731
                 t, d, z = [f], [], []
                 for i in range(n):
                     d.append(buf()), z.append(buf()), t.append(buf())
@@ -128,28 +141,44 @@ class HeadTrain:
                 aoff += hh * hh * 9
 
     def _dw(self, x, y, w, h):
-        self.fwd.add("stl_det_dwconv", x, w, None, y, self.B, h, h, self.c, 3, 1, 0)
+        if self.h16:
+            self.fwd.add("stl_det_dwconv16", self.code, x, w, None, y, None, self.B, h, h, self.c, 3, 1, 0)
+        else:
+            self.fwd.add("stl_det_dwconv", x, w, None, y, self.B, h, h, self.c, 3, 1, 0)
 
     def _pw(self, plan, x, out, M, hw, ci, co, pk, act, z=None, img_stride=None, row_stride=None, off=0):
         w, b, kp, np_ = pk
-        p = capi.DetPointwise(*pointwise_fields(x, plan.wbuf[w:], plan.wbuf[b:], None, None, out, M, hw, ci, co, kp, np_, act,
-                                                img_stride, row_stride, off))
+        common = pointwise_fields(x, (plan.wbuf16 if self.h16 else plan.wbuf)[w:], plan.wbuf[b:], None, None, out, M, hw, ci, co, kp,
+                                  np_, act, img_stride, row_stride, off)
         self.fwd.keep_alive(x, out)   # the descriptor holds their addresses
-        self.fwd.add(*(("stl_det_pointwise", p) if z is None else ("stl_det_pointwise_train", p, z)))   # _train: also stores the pre-activation z
+        if self.h16:   # the inference plan's descriptor: reg / cls come out fp32, everything else in adtype
+            p, sfx = capi.DetPointwise16(*common, self.code, 1 if out.dtype == torch.float32 else 0), "16"
+        else:
+            p, sfx = capi.DetPointwise(*common), ""
+        self.fwd.add(*((f"stl_det_pointwise{sfx}", p) if z is None else (f"stl_det_pointwise{sfx}_train", p, z)))   # _train: also stores the pre-activation z
 
     def _pw_bwd(self, plan, x, dy, dx, M, hw, ci, co, pk, gw, gb, img_stride=None, row_stride=None, off=0):
-        """Weight and data gradient of one pointwise layer; dy None: a header, whose dy (dreg / dlogit) set_grads fills in."""
+        """Weight and data gradient of one pointwise layer; dy None: a header, whose dy (dreg / dlogit, fp32) set_grads fills in."""
         w, _, kp, np_ = pk
-        p = capi.DetPointwiseBwd(x.data_ptr(), plan.wbuf[w:].data_ptr(), None if dy is None else dy.data_ptr(), dx.data_ptr(),
-                                 gw.data_ptr(), gb.data_ptr(), self.pw_part.data_ptr(), M, hw * co if img_stride is None else img_stride,
-                                 co if row_stride is None else row_stride, off, hw, ci, co, kp, np_, 0)
+        ptrs = (None if dy is None else dy.data_ptr(), dx.data_ptr(), gw.data_ptr(), gb.data_ptr(), self.pw_part.data_ptr(), M,
+                hw * co if img_stride is None else img_stride, co if row_stride is None else row_stride, off, hw, ci, co)
+        if self.h16:
+            wt, kt, nt = self.layoutT[w]
+            p, sfx = capi.DetPointwise16Bwd(x.data_ptr(), self.wbufT[wt:].data_ptr(), *ptrs, kt, nt, self.code, 1 if dy is None else 0, 0), "16"
+        else:
+            p, sfx = capi.DetPointwiseBwd(x.data_ptr(), plan.wbuf[w:].data_ptr(), *ptrs, kp, np_, 0), ""
         self.bwd.keep_alive(x, gw, gb)   # the descriptor holds their addresses
-        self.bwd.add("stl_det_pointwise_bwd_weight", p)
-        self.bwd.add("stl_det_pointwise_bwd_data", p)
+        self.bwd.add(f"stl_det_pointwise{sfx}_bwd_weight", p)
+        self.bwd.add(f"stl_det_pointwise{sfx}_bwd_data", p)
         return p
 
     def _dw_bwd(self, x, dy, w, gw, z, dx, h):
         """Weight gradient of one depthwise layer and, with dx, its data gradient times swish'(z) of the layer below."""
+        if self.h16:
+            self.bwd.add("stl_det_dwconv16_bwd_weight", self.code, x, dy, self.dw_part, gw, self.B, h, h, self.c)
+            if dx is not None:
+                self.bwd.add("stl_det_dwconv16_bwd_data", dy, w, z, dx, self.B, h, h, self.c, self.code)
+            return
         self.bwd.add("stl_det_dwconv_bwd_weight", x, dy, self.dw_part, gw, self.B, h, h, self.c)
         if dx is not None:
             self.bwd.add("stl_det_dwconv_bwd_data", dy, w, z, dx, self.B, h, h, self.c)
@@ -225,8 +254,9 @@ class _DetLossFn(torch.autograd.Function):
 
 def detection_loss(m, inputs, targets, alpha: float = 0.25, gamma: float = 2.0, box_weight: float = 50.0) -> Dict[str, torch.Tensor]:
     """EfficientDetBackbone.detection_loss (documented there)."""
-    if m.compute_dtype != "fp32":
-        raise NotImplementedError(f"EfficientDet.detection_loss: compute_dtype {m.compute_dtype!r}; the heads train in \"fp32\" only")
+    if m.compute_dtype not in ("fp32", "f16"):
+        raise NotImplementedError(f"EfficientDet.detection_loss: compute_dtype {m.compute_dtype!r}; the heads train in \"fp32\" or "
+                                  "\"f16\" (f16 forward, bf16 gradients)")
     dev = torch.device("cuda", torch.cuda.current_device())
     srcs = m._float_sources(inputs, dev)
     gt, offsets = pack_targets(targets, [(int(s.shape[1]), int(s.shape[2])) for s in srcs], m.num_classes)
@@ -239,6 +269,9 @@ def detection_loss(m, inputs, targets, alpha: float = 0.25, gamma: float = 2.0, 
         p.run(st, upto=p.head_start)
         tr.forward(st)
         p._inflight = keep
+        if tr.h16 and not bool((torch.isfinite(tr.reg).all() & torch.isfinite(tr.cls).all()).item()):
+            raise FloatingPointError("EfficientDet.detection_loss: non-finite head outputs in compute_dtype='f16': activations left "
+                                     "f16's range (largest finite value 65504); fine-tune the detector with compute_dtype=\"fp32\"")
         losses, dreg, dlogit, npos = torch.ops.stlpose.det_loss(tr.reg, tr.cls, m._anchor_dev, torch.from_numpy(gt).to(dev),
                                                                 torch.from_numpy(offsets).to(dev), float(alpha), float(gamma),
                                                                 float(box_weight))

@@ -17,7 +17,8 @@ keeps every other weight, every bias and every sum in fp32.  The depthwise kerne
 squeeze-excitation pooling sums, so a 16-bit plan has no pooling pass.  In "f16" a forward whose head outputs hold a non-finite
 value raises FloatingPointError (activations left f16's range: use "bf16"), as HRNet's "mixed" mode does.
 
-``detection_loss(inputs, targets)`` (fp32 only; stlpose_amd/detector_train.py, csrc/detector_train.hip) is the first stage of
+``detection_loss(inputs, targets)`` ("fp32", or "f16" with bf16 gradients in flight and fp32 ``.grad``; "bf16" raises;
+stlpose_amd/detector_train.py, csrc/detector_train.hip) is the first stage of
 EfficientDet fine-tuning, the counterpart of ``loss_dict = model(imgs / 255, targets)`` in ``02_train_faster_rcnn.py:212``: the
 backbone and the BiFPN are frozen, every BN stays on its running statistics, and ``sum(loss_dict.values()).backward()`` fills
 ``.grad`` of the ``regressor.*`` and ``classifier.*`` parameters.
@@ -220,11 +221,14 @@ def _fold(bn: nn.BatchNorm2d):
 
 class _Packer:
     """Packs folded weights into one fp32 device buffer; every piece starts on a 16-float boundary.  With a 16-bit ``dtype`` the
-    pointwise weights go into a second buffer of that type, in the layout of stl_det_pointwise16."""
+    pointwise weights go into a second buffer of that type, in the layout of stl_det_pointwise16.  ``transposed`` (16-bit only, the
+    heads of a model that trains): every pointwise layer also gets the bf16 transposed pack of stl_det_pointwise16_bwd_data, in a
+    buffer of its own; ``tmap`` maps the forward pack's offset to (offset, Kp, Np) of the transposed one."""
 
-    def __init__(self, dtype: torch.dtype = torch.float32):
+    def __init__(self, dtype: torch.dtype = torch.float32, transposed: bool = False):
         self.parts, self.n = [], 0
         self.dtype, self.parts16, self.n16 = dtype, [], 0
+        self.transposed, self.partsT, self.nT, self.tmap = transposed, [], 0, {}
 
     def add(self, t: torch.Tensor) -> int:
         off = self.n
@@ -258,6 +262,11 @@ class _Packer:
             off = self.n16
             self.parts16.append(wp)
             self.n16 += wp.numel()
+            if self.transposed:
+                wt, kt, nt = pack_transposed(w)
+                self.tmap[off] = (self.nT, kt, nt)
+                self.partsT.append(wt)
+                self.nT += wt.numel()
             return off, bo, kp, np_
         kp, np_ = -(-ci // 16) * 16, -(-co // 64) * 64
         wp = w.new_zeros(kp, np_)
@@ -284,6 +293,23 @@ class _Packer:
 
     def done16(self, dev) -> Optional[torch.Tensor]:
         return torch.cat(self.parts16).to(dev).contiguous() if self.parts16 else None
+
+
+def pack_transposed(w: torch.Tensor):
+    """The folded fp64 W' [co, ci] -> (bf16 pack, Kp, Np) for the data gradient dX = dY W'^T: the forward's tile layout with the
+    roles of k and n swapped (the contraction runs over co, padded to Kp % 32 == 0; the output over ci, padded to Np % 64 == 0),
+    rounded once from the fp64 fold."""
+    co, ci = w.shape
+    kp, np_ = -(-co // 32) * 32, -(-ci // 64) * 64
+    wp = w.new_zeros(np_, kp)
+    wp[:ci, :co] = w.t()
+    return wp.reshape(np_ // 16, 16, kp // 32, 4, 8).permute(0, 2, 3, 1, 4).reshape(-1).to(torch.bfloat16), kp, np_
+
+
+def unpack_transposed(wt: torch.Tensor, ci: int, co: int) -> torch.Tensor:
+    """pack_transposed's inverse: the bf16 W'^T [ci, co]."""
+    kp, np_ = -(-co // 32) * 32, -(-ci // 64) * 64
+    return wt.reshape(np_ // 16, kp // 32, 4, 16, 8).permute(0, 3, 1, 2, 4).reshape(np_, kp)[:ci, :co]
 
 
 # ------------------------------------------------------------------------------------------------ the launch plan
@@ -526,6 +552,7 @@ class EfficientDetBackbone(nn.Module):
         self.anchors_np = anchors(cc)
         self.num_anchors_total = self.anchors_np.shape[0]
         self._version, self._plans, self._wbuf, self._wbuf16, self._anchor_dev = None, {}, None, None, None
+        self._wbufT16, self._layoutT = None, None   # the heads' bf16 transposed packs (_ensure_transposed: models that train only)
         self.eval()
 
     # ---------------------------------------------------------------- state
@@ -551,7 +578,7 @@ class EfficientDetBackbone(nn.Module):
     def _refold_heads(self) -> None:
         """Only regressor.* / classifier.* changed (an optimiser step of detection_loss): their pieces are the tail of the weight
         buffers and are rewritten in place, through the same packing as a full refold (bit-identical); the plans stay."""
-        P = _Packer(COMPUTE_DTYPES[self.compute_dtype][0])
+        P = _Packer(COMPUTE_DTYPES[self.compute_dtype][0], transposed=self._wbufT16 is not None)
         P.n, P.n16 = self._head_off
         heads = self._pack_heads(P)
         assert all(heads[k] == self._layout[k] for k in heads) and P.n == self._wbuf.numel(), "EfficientDet: head layout changed"
@@ -559,6 +586,18 @@ class EfficientDetBackbone(nn.Module):
         self._wbuf[n0:].copy_(torch.cat(P.parts).float())
         if P.parts16:
             self._wbuf16[n16:].copy_(torch.cat(P.parts16))
+        if P.partsT:
+            assert P.tmap == self._layoutT, "EfficientDet: head layout changed"
+            self._wbufT16.copy_(torch.cat(P.partsT))
+
+    def _ensure_transposed(self) -> None:
+        """16-bit models that train: the bf16 transposed packs of the heads' pointwise layers (stl_det_pointwise16_bwd_data), built
+        at the first detection_loss after a full fold and refreshed by _refold_heads; the forward buffers are not touched."""
+        if self._wbufT16 is None:
+            P = _Packer(COMPUTE_DTYPES[self.compute_dtype][0], transposed=True)
+            P.n, P.n16 = self._head_off
+            self._pack_heads(P)
+            self._wbufT16, self._layoutT = torch.cat(P.partsT).to(self._wbuf.device).contiguous(), P.tmap
 
     def ready(self, dev) -> None:
         """Fold BN and pack every weight into one fp32 device buffer (in a 16-bit mode the pointwise weights into a second one of
@@ -601,6 +640,7 @@ class EfficientDetBackbone(nn.Module):
         self._head_off = (P.n, P.n16)   # the heads are packed last: _refold_heads rewrites the buffers from here on
         heads = self._pack_heads(P)
         self._wbuf, self._wbuf16 = P.done(dev), P.done16(dev)
+        self._wbufT16, self._layoutT = None, None
         for cell in cells:   # BiFPN weight offsets -> device views
             cell["weights"] = {n: self._wbuf[o:] for n, o in cell["weights"].items()}
         self._layout = {"stem": stem, "blocks": blocks, "bifpn": cells, **heads}
@@ -672,7 +712,9 @@ class EfficientDetBackbone(nn.Module):
         forward takes them; targets one dict per image with ``boxes`` [n, 4] (x1, y1, x2, y2 in original pixels) and ``labels``
         [n] in 1 .. num_classes (n = 0 allowed).  Returns {"classification", "regression"}: fp32 device scalars whose backward
         fills ``.grad`` of every regressor.* and classifier.* parameter; the backbone and the BiFPN are frozen and every BN runs
-        on its running statistics, whatever ``.training`` is.  fp32 only.  One activation set per batch size: backward before the
+        on its running statistics, whatever ``.training`` is.  compute_dtype "fp32", or "f16" (f16 forward tensors, bf16 gradients in
+        flight, fp32 sums and fp32 ``.grad``; non-finite head outputs raise FloatingPointError); "bf16" raises
+        NotImplementedError.  One activation set per batch size: backward before the
         next detection_loss of that batch size (a stale-forward error otherwise).  See stlpose_amd/detector_train.py."""
         from . import detector_train
         return detector_train.detection_loss(self, inputs, targets, alpha, gamma, box_weight)
