@@ -380,6 +380,7 @@ int stl_selftest_mfma(float* out /* [4] max abs err: bf16 mfma, f32 mfma, tr-rea
 #define STL_POSE_TOPK_MAX 1024     /* largest k of stl_pose_topk */
 #define STL_POSE_RANK_MAX 16384    /* largest N of stl_pose_rank: one workgroup holds N (dist, idx) keys in LDS (128 KiB) */
 #define STL_POSE_RANK_LABELS_MAX 4 /* label levels scored by stl_pose_rank */
+#define STL_POSE_RANK_ANY_MAX (1 << 24) /* largest N of stl_pose_rank_any: sorted runs of STL_POSE_RANK_MAX keys merged in global memory */
 #define STL_POSE_NSCORES 10        /* p@1, p@5, p@10, p@rel, mAP, r@1, r@5, r@10, r@rel, mAR (metrics.py:25-94) */
 
 /* joints [N, 17, C >= 2] (pose n at joints + n * row_stride, keypoint k at + k * C) -> out [N, D]: the selected keypoints' (x, y),
@@ -404,6 +405,17 @@ int stl_pose_topk(const float* q, const float* conf, const float* db, int Q, int
 int stl_pose_rank(const float* q, const float* conf, const float* db, int Q, int N, int D, int method, int penalization, int k_out,
                   int64_t* idx, float* dist, const int32_t* labels, const int32_t* qlabels, int L, int k_eff, double* scores,
                   void* stream);
+/* Bytes of the `work` buffer stl_pose_rank_any needs for (Q, N): two [Q, N] arrays of 8-byte keys above N = STL_POSE_RANK_MAX, a
+ * token 16 bytes up to it.  Negative (error code) for Q < 0, N < 1 or N > STL_POSE_RANK_ANY_MAX. */
+int64_t stl_pose_rank_any_workspace(int Q, int N);
+/* stl_pose_rank for every 1 <= N <= STL_POSE_RANK_ANY_MAX: same arguments, checks, order and scores.  Up to STL_POSE_RANK_MAX rows
+ * it runs stl_pose_rank itself; above, each query's keys are sorted in runs of STL_POSE_RANK_MAX in LDS, the runs merged pairwise
+ * in `work` (merge path, ceil(log2(runs)) passes), and the scores computed from the sorted keys with stl_pose_rank's arithmetic in
+ * a fixed summation order.  Q <= 65535 per call above STL_POSE_RANK_MAX; `work` 8-byte aligned; a missing or short workspace is
+ * refused before anything is launched. */
+int stl_pose_rank_any(const float* q, const float* conf, const float* db, int Q, int N, int D, int method, int penalization, int k_out,
+                      int64_t* idx, float* dist, const int32_t* labels, const int32_t* qlabels, int L, int k_eff, double* scores,
+                      void* work, int64_t work_bytes, void* stream);
 
 /* ---- top-down pose extraction (stlpose_amd/csrc/topdown.hip): person boxes -> crops -> HRNet -> poses, the glue of
  * src/04_evaluate_vases_qualitatively.py:184-250 and src/05_create_archdata_retrieval_db.py:114-171. */

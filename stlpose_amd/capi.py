@@ -25,6 +25,7 @@ POSE_DIM = {"all_kpts": 34, "full_body": 26, "upper_body": 18}
 POSE_METHOD = {"euclidean": 0, "cosine": 1, "manhattan": 2, "confidence": 3, "oks": 4, "l2sq": 5, "cos_normalised": 6}
 POSE_PEN = {"zero_coord": 0, "none": 1, "mean": 2, "max": 3}
 POSE_TOPK_MAX, POSE_RANK_MAX, POSE_RANK_LABELS_MAX, POSE_NSCORES = 1024, 16384, 4, 10
+POSE_RANK_ANY_MAX = 1 << 24   # STL_POSE_RANK_ANY_MAX: largest N of stl_pose_rank_any
 # top-down extraction (STL_BOX_MAX, STL_RESIZE_SRC_MAX, STL_RESIZE_DST_MAX)
 BOX_MAX, RESIZE_SRC_MAX, RESIZE_DST_MAX = 4096, 16384, 2048
 # person detector (STL_DET_NMS_MAX)
@@ -219,6 +220,8 @@ SIGNATURES = {
     "stl_pose_topk_workspace": [i32, i32, i32, i32],
     "stl_pose_topk": [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, i64, vp],
     "stl_pose_rank": [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, i32, i32, vp, vp],
+    "stl_pose_rank_any_workspace": [i32, i32],
+    "stl_pose_rank_any": [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, i32, i32, vp, vp, i64, vp],
     "stl_box_select": [vp, vp, vp, vp, i32, i64, i32, i64, i32, f32, C.c_double, vp, vp, vp],
     "stl_heatmap_resize_argmax": [vp, i32, i32, i32, i32, i32, vp, vp, vp, vp],
     "stl_det_preprocess": [vp, i32, i32, vp, vp],
@@ -264,6 +267,7 @@ SIGNATURES = {
 DEBUG_SIGNATURES = {"stl_debug_conv_stamps": [vp], "stl_debug_conv_stamps2": [vp], "stl_debug_wgrad_stamps": [vp],
                     "stl_debug_wgrad_stamps2": [vp]}
 
+INT64_FUNCS = ("stl_det_nms_workspace", "stl_pose_rank_any_workspace")   # int64_t f(...)
 STRING_FUNCS = ("stl_last_error", "stl_build_id", "stl_last_kernel")   # const char* f(void)
 
 _lib = None
@@ -281,7 +285,7 @@ def lib() -> C.CDLL:
         for name, args in SIGNATURES.items():
             fn = getattr(l, name)  # AttributeError if the ABI and this table disagree
             fn.argtypes = args
-            fn.restype = C.c_int64 if name == "stl_det_nms_workspace" else C.c_int
+            fn.restype = C.c_int64 if name in INT64_FUNCS else C.c_int
         for name, args in DEBUG_SIGNATURES.items():
             if hasattr(l, name):
                 getattr(l, name).argtypes, getattr(l, name).restype = args, C.c_int

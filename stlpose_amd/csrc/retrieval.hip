@@ -437,6 +437,174 @@ __global__ __launch_bounds__(kRankThreads) void pose_rank_kernel(const RankArgs 
     }
 }
 
+// ---------------------------------------------------------------- full ranking of any N: sorted runs + merge path + scores
+// Above kRun rows one workgroup cannot hold a query's keys, so the ranking is built in a global workspace of two [Q][N] key arrays:
+//   1. pose_run_sort_kernel, grid (chunk of kRun rows, query): the keys of the chunk, formed by the calls pose_rank_kernel makes
+//      (stage_queries with the whole N, so every chunk sees the same penalty bits), bitonic-sorted in LDS; the sorted run is
+//      stored at its rows' own positions [c * kRun, min(N, (c + 1) * kRun)): the last run keeps its true length.
+//   2. pose_merge_kernel, ceil(log2(runs)) passes over the two arrays: runs of width W are merged in pairs (an unpaired run is the
+//      pair with an empty second half: a copy).  A workgroup owns kTile consecutive output positions; since 2W is a multiple of
+//      kTile a tile lies in one pair.  It finds its two input ranges by binary search on the tile's first and last diagonal, stages
+//      them in LDS (kTile keys in all), ranks every staged key in the other range by binary search -- keys are unique, so rank +
+//      own position is a permutation of the tile -- and stores the tile contiguously.
+//   3. pose_rank_write_kernel, one workgroup per query: idx / dist of the first k_out keys and the scores, with the arithmetic of
+//      pose_rank_kernel (thread t owns ranks [t * seg, (t + 1) * seg), counts scanned, fp64 sums per wave, then in wave order).
+//      Segments exceed 32 ranks here, so the relevance is recomputed in the second pass instead of kept as a bit mask.
+// Every summation order is fixed by (N, k_eff) alone: two runs give the same bits.
+constexpr int kRun = STL_POSE_RANK_MAX;
+constexpr int kTile = 2048;
+constexpr int kMergeThreads = 256;
+static_assert(kRun % kTile == 0, "a merge tile must not straddle two pairs of runs");
+
+template <int M, int P, int D>
+__global__ __launch_bounds__(kRankThreads) void pose_run_sort_kernel(const float* __restrict__ q, const float* __restrict__ conf,
+                                                                     const float* __restrict__ db, uint64_t* __restrict__ runs, int N,
+                                                                     int is_max) {
+    constexpr int DP = (D + 3) & ~3;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    uint64_t* keys = reinterpret_cast<uint64_t*>(smem);   // [kRun]
+    float* sq = reinterpret_cast<float*>(keys + kRun);    // [DP]
+    float* sc = sq + DP;                                  // [DP]
+    float* spen = sc + DP;                                // [4]
+    const int qi = blockIdx.y, tid = threadIdx.x;
+    const int r0 = blockIdx.x * kRun, n = min(kRun, N - r0);
+    int NP = 128;
+    while (NP < n) NP <<= 1;
+    stage_queries<M, P, D, DP>(q, conf, db, N, qi, 1, 1, is_max, sq, sc, spen, reinterpret_cast<float*>(keys));
+    const float pen = spen[0];
+    for (int r = tid; r < NP; r += kRankThreads) {
+        uint64_t key = kMaxKey;   // above every real key (an index is < 2^24): the padding sorts behind the run and is not stored
+        if (r < n) {
+            float x[D];
+            load_row<D>(db, r0 + r, x);
+            key = make_key(pair_dist<M, P, D>(sq, sc, x, pen), (uint32_t)(r0 + r));
+        }
+        keys[r] = key;
+    }
+    bitonic_sort(keys, NP);
+    uint64_t* out = runs + (int64_t)qi * N + r0;
+    for (int r = tid; r < n; r += kRankThreads) out[r] = keys[r];
+}
+
+// number of keys of the sorted LDS range a[0, n) below key
+__device__ __forceinline__ int lower_count(const uint64_t* a, int n, uint64_t key) {
+    int lo = 0, hi = n;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (a[mid] < key) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+
+__global__ __launch_bounds__(kMergeThreads) void pose_merge_kernel(const uint64_t* __restrict__ src, uint64_t* __restrict__ dst, int N,
+                                                                   int W) {
+    __shared__ uint64_t sin[kTile], sout[kTile];   // 32 KiB exactly: five workgroups per CU
+    int* split = reinterpret_cast<int*>(sout);     // the two diagonal splits, read by every thread before sout is written
+    const int tid = threadIdx.x;
+    const int t0 = blockIdx.x * kTile;                   // the tile's first output position within the query (< N by the grid)
+    const int base = t0 / (2 * W) * (2 * W);             // first position of the pair of runs; W <= 2^23
+    const int la = min(W, N - base), lb = max(0, min(W, N - base - W));
+    const uint64_t* A = src + (int64_t)blockIdx.y * N + base;
+    const uint64_t* B = A + W;                           // read only when lb > 0
+    const int d0 = t0 - base, d1 = min(d0 + kTile, la + lb);
+    if (tid < 2) {
+        // merge path: how many of the first d merged keys come from A.  lo >= d - lb and hi <= min(d, la) keep A[mid] and
+        // B[d - 1 - mid] inside their runs; with lb == 0 the range is the single point d and nothing is read.
+        const int d = tid ? d1 : d0;
+        int lo = max(0, d - lb), hi = min(d, la);
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if (A[mid] < B[d - 1 - mid]) lo = mid + 1;
+            else hi = mid;
+        }
+        split[tid] = lo;
+    }
+    __syncthreads();
+    const int a0 = split[0], na = split[1] - a0, b0 = d0 - a0, nt = d1 - d0, nb = nt - na;   // na + nb = nt <= kTile
+    for (int e = tid; e < nt; e += kMergeThreads) sin[e] = e < na ? A[a0 + e] : B[b0 + (e - na)];
+    __syncthreads();
+    for (int e = tid; e < nt; e += kMergeThreads) {
+        const uint64_t key = sin[e];
+        const int pos = e < na ? e + lower_count(sin + na, nb, key) : (e - na) + lower_count(sin, na, key);
+        sout[pos] = key;
+    }
+    __syncthreads();
+    uint64_t* o = dst + (int64_t)blockIdx.y * N + t0;
+    for (int e = tid; e < nt; e += kMergeThreads) o[e] = sout[e];
+}
+
+struct RankWriteArgs {
+    const uint64_t* keys;     // [Q][N] sorted
+    int64_t* idx;
+    float* dist;
+    const int32_t* labels;    // [L][N] or NULL
+    const int32_t* qlabels;   // [L][Q]
+    double* scores;           // [Q][L][10]
+    int Q, N, k_out, L, k_eff;
+};
+
+__global__ __launch_bounds__(kRankThreads) void pose_rank_write_kernel(const RankWriteArgs a) {
+    __shared__ int scan[kRankThreads];
+    __shared__ double red[kRankThreads / 64 * 2];
+    const int qi = blockIdx.x, tid = threadIdx.x;
+    const uint64_t* keys = a.keys + (int64_t)qi * a.N;
+    for (int r = tid; r < a.k_out; r += kRankThreads) {
+        const uint64_t key = keys[r];
+        a.idx[(int64_t)qi * a.k_out + r] = (int64_t)(uint32_t)key;
+        a.dist[(int64_t)qi * a.k_out + r] = key_dist(key);
+    }
+    if (!a.labels) return;
+    const int m = a.k_eff - 1;                               // retrievals scored: ranks 1 .. k_eff-1
+    const int seg = (m + kRankThreads - 1) / kRankThreads;   // <= 2^14
+    const int j0 = min(m, tid * seg), j1 = min(m, j0 + seg);
+    const int lane = tid & 63, wave = tid >> 6;
+    for (int l = 0; l < a.L; ++l) {
+        const int32_t want = a.qlabels[(int64_t)l * a.Q + qi];
+        const int32_t* lab = a.labels + (int64_t)l * a.N;
+        int cnt = 0;
+        for (int j = j0; j < j1; ++j) cnt += lab[(uint32_t)keys[j + 1]] == want;
+        scan[tid] = cnt;
+        __syncthreads();
+        for (int off = 1; off < kRankThreads; off <<= 1) {
+            const int v = tid >= off ? scan[tid - off] : 0;
+            __syncthreads();
+            scan[tid] += v;
+            __syncthreads();
+        }
+        const int nrel = scan[kRankThreads - 1];
+        int cum = scan[tid] - cnt;
+        double sp = 0.0, sr = 0.0;
+        for (int j = j0; j < j1; ++j) {
+            const int rel = lab[(uint32_t)keys[j + 1]] == want;
+            cum += rel;
+            if (rel) sp += (double)cum / (double)(j + 1), sr += (double)cum / (double)nrel;
+        }
+        for (int o = 32; o > 0; o >>= 1) sp += __shfl_xor(sp, o), sr += __shfl_xor(sr, o);
+        if (lane == 0) red[wave * 2] = sp, red[wave * 2 + 1] = sr;
+        __syncthreads();
+        if (tid == 0) {
+            double* s = a.scores + ((int64_t)qi * a.L + l) * STL_POSE_NSCORES;
+            if (nrel == 0) {
+                for (int i = 0; i < STL_POSE_NSCORES; ++i) s[i] = -1.0;
+            } else {
+                double tp = 0.0, tr = 0.0;
+                for (int w = 0; w < kRankThreads / 64; ++w) tp += red[w * 2], tr += red[w * 2 + 1];
+                auto cum_at = [&](int j) {   // relevant among scored positions 0 .. j: the scan up to j's segment plus a recount
+                    const int t = j / seg;
+                    int c = t == 0 ? 0 : scan[t - 1];
+                    for (int i = t * seg; i <= j; ++i) c += lab[(uint32_t)keys[i + 1]] == want;
+                    return c;
+                };
+                const double c1 = cum_at(0), c5 = cum_at(4), c10 = cum_at(9), cr = cum_at(nrel - 1), nr = nrel;
+                s[0] = c1 / 1.0, s[1] = c5 / 5.0, s[2] = c10 / 10.0, s[3] = cr / nr, s[4] = tp / nr;
+                s[5] = c1 / nr, s[6] = c5 / nr, s[7] = c10 / nr, s[8] = cr / nr, s[9] = tr / nr;
+            }
+        }
+        __syncthreads();
+    }
+}
+
 // ---------------------------------------------------------------- dispatch over (method, penalization, D)
 static int check_common(int D, int method, int pen) {
     STL_CHECK(D == 18 || D == 26 || D == 34, "pose: D = %d (pose vectors have 18, 26 or 34 entries)", D);
@@ -600,5 +768,55 @@ extern "C" int stl_pose_rank(const float* q, const float* conf, const float* db,
         STL_LAUNCH(kern, dim3(Q), dim3(kRankThreads), lds, ST, a);
     });
     STL_LAUNCH_CHECK("pose_rank");
+    return 0;
+}
+
+extern "C" int64_t stl_pose_rank_any_workspace(int Q, int N) {
+    STL_CHECK(Q >= 0 && N >= 1 && N <= STL_POSE_RANK_ANY_MAX, "pose_rank_any: Q = %d, N = %d (a ranking takes 1 <= N <= %d)", Q, N,
+              STL_POSE_RANK_ANY_MAX);
+    if (N <= kRun || Q == 0) return 16;   // nothing is merged: a token size, so that every (Q, N) has a buffer
+    return (int64_t)Q * N * 16;           // two [Q][N] arrays of 8-byte keys
+}
+
+extern "C" int stl_pose_rank_any(const float* q, const float* conf, const float* db, int Q, int N, int D, int method, int penalization,
+                                 int k_out, int64_t* idx, float* dist, const int32_t* labels, const int32_t* qlabels, int L, int k_eff,
+                                 double* scores, void* work, int64_t work_bytes, void* stream) {
+    if (int rc = check_common(D, method, penalization)) return rc;
+    STL_CHECK(N >= 1 && N <= STL_POSE_RANK_ANY_MAX, "pose_rank_any: N = %d (a ranking takes 1 <= N <= %d)", N, STL_POSE_RANK_ANY_MAX);
+    STL_CHECK(Q >= 0 && k_out >= 0 && k_out <= N, "pose_rank_any: k_out = %d with N = %d", k_out, N);
+    if (labels) {
+        STL_CHECK(qlabels && scores && L >= 1 && L <= STL_POSE_RANK_LABELS_MAX,
+                  "pose_rank_any: scores need qlabels, scores and 1 <= L <= %d", STL_POSE_RANK_LABELS_MAX);
+        STL_CHECK(k_eff >= 11 && k_eff <= N, "pose_rank_any: scores need 11 <= k_eff <= N (k_eff = %d, N = %d): p@10 reads rank 10",
+                  k_eff, N);
+    }
+    if (Q == 0) return 0;
+    STL_CHECK(q && db && (k_out == 0 || (idx && dist)), "pose_rank_any: null pointer");
+    const int64_t need = stl_pose_rank_any_workspace(Q, N);
+    STL_CHECK(work && work_bytes >= need, "pose_rank_any: workspace of %lld bytes, %lld needed", (long long)(work ? work_bytes : 0),
+              (long long)need);
+    if (N <= kRun) return stl_pose_rank(q, conf, db, Q, N, D, method, penalization, k_out, idx, dist, labels, qlabels, L, k_eff, scores,
+                                        stream);
+    STL_CHECK(Q <= 65535, "pose_rank_any: Q = %d (at most 65535 queries per call above N = %d)", Q, kRun);
+    STL_CHECK(((uintptr_t)work & 7) == 0, "pose_rank_any: workspace must be 8-byte aligned");
+    uint64_t* buf[2] = {(uint64_t*)work, (uint64_t*)work + (int64_t)Q * N};
+    const int is_max = penalization == STL_POSE_PEN_MAX;
+    const int DP = (D + 3) & ~3;
+    const size_t lds = (size_t)kRun * 8 + 2 * DP * 4 + 16;
+    dispatch(method, penalization, D, [&](auto m, auto pp, auto d) {
+        auto* kern = &pose_run_sort_kernel<decltype(m)::value, decltype(pp)::value, decltype(d)::value>;
+        hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        STL_LAUNCH(kern, dim3(ceil_div(N, kRun), Q), dim3(kRankThreads), lds, ST, q, conf, db, buf[0], N, is_max);
+    });
+    STL_LAUNCH_CHECK("pose_run_sort");
+    int cur = 0;
+    for (int W = kRun; W < N; W <<= 1, cur ^= 1) {   // W <= 2^23: the loop ends before W could overflow
+        STL_LAUNCH(pose_merge_kernel, dim3(ceil_div(N, kTile), Q), dim3(kMergeThreads), 0, ST, (const uint64_t*)buf[cur], buf[cur ^ 1], N,
+                   W);
+        STL_LAUNCH_CHECK("pose_merge");
+    }
+    RankWriteArgs a{buf[cur], idx, dist, labels, qlabels, scores, Q, N, k_out, labels ? L : 0, k_eff};
+    STL_LAUNCH(pose_rank_write_kernel, dim3(Q), dim3(kRankThreads), 0, ST, a);
+    STL_LAUNCH_CHECK("pose_rank_write");
     return 0;
 }

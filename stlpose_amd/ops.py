@@ -305,6 +305,29 @@ def _pose_rank_fake(q, c, db, m, p, k_out, labels, qlabels, k_eff):
 _define("pose_rank(Tensor query, Tensor? conf, Tensor database, str method, str penalization, int k_out, Tensor? labels, "
         "Tensor? qlabels, int k_eff) -> (Tensor, Tensor, Tensor)", _pose_rank, _pose_rank_fake)
 
+
+def _pose_rank_any(query, conf, database, method: str, penalization: str, k_out: int, labels, qlabels, k_eff: int):
+    """pose_rank at any N <= capi.POSE_RANK_ANY_MAX; the workspace (two [Q, N] key arrays above N = POSE_RANK_MAX) is allocated here."""
+    _check_pose_shapes(query, conf, database, labels, qlabels)
+    q, c, db, m, p = _pose_args(query, conf, database, method, penalization)
+    nq, n, d = q.shape[0], db.shape[0], q.shape[1]
+    need = capi.lib().stl_pose_rank_any_workspace(nq, n)
+    capi.check(min(need, 0), "stl_pose_rank_any")
+    work = torch.empty(need, dtype=torch.uint8, device=q.device)
+    idx = torch.empty(nq, k_out, dtype=torch.int64, device=q.device)
+    dist = torch.empty(nq, k_out, dtype=torch.float32, device=q.device)
+    lab = labels.contiguous().to(torch.int32) if labels is not None else None
+    qlab = qlabels.contiguous().to(torch.int32) if qlabels is not None else None
+    nl = lab.shape[0] if lab is not None else 0
+    scores = torch.empty(nq, nl, capi.POSE_NSCORES, dtype=torch.float64, device=q.device)
+    capi.call("stl_pose_rank_any", q.data_ptr(), _ptr(c), db.data_ptr(), nq, n, d, m, p, k_out, idx.data_ptr(), dist.data_ptr(),
+              _ptr(lab), _ptr(qlab), nl, k_eff, scores.data_ptr(), work.data_ptr(), work.numel(), _st())
+    return idx, dist, scores
+
+
+_define("pose_rank_any(Tensor query, Tensor? conf, Tensor database, str method, str penalization, int k_out, Tensor? labels, "
+        "Tensor? qlabels, int k_eff) -> (Tensor, Tensor, Tensor)", _pose_rank_any, _pose_rank_fake)
+
 # ------------------------------------------------------------------ top-down extraction (lib/bounding_box.py, lib/pose_parsing.py)
 # Every shape, dtype, device and cap the kernels rely on is checked here, before anything is launched.
 def _box_select(boxes, scores, labels, offsets, label: int, score_thr: Optional[float], iou_thr: float) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -460,5 +483,5 @@ _define("det_loss(Tensor regression, Tensor classification, Tensor anchors, Tens
                                            r.new_empty(r.shape[0], dtype=torch.int32)))
 
 OPS = ["person_mse", "heatmap_argmax", "final_preds", "flip_merge", "flip_merge_backward", "gaussian_targets", "affine_crop",
-       "hrnet_forward", "hrnet_backward", "hrnet_backward_input", "pose_vectors", "pose_distances", "pose_topk", "pose_rank",
+       "hrnet_forward", "hrnet_backward", "hrnet_backward_input", "pose_vectors", "pose_distances", "pose_topk", "pose_rank", "pose_rank_any",
        "box_select", "heatmap_resize_argmax", "det_decode", "det_nms", "det_loss"]

@@ -2,8 +2,11 @@
 (``src/06_fit_knn_tree.py``).
 
 Every distance, selection and sort runs in the HIP kernels of ``csrc/retrieval.hip`` (ops ``stlpose::pose_vectors``,
-``pose_distances``, ``pose_topk``, ``pose_rank``).  The search is EXACT: the neighbours are the first k of a stable argsort of all
-distances (ties by ascending database index, NaN last), where the reference's hnswlib graph is approximate.
+``pose_distances``, ``pose_topk``, ``pose_rank``, ``pose_rank_any``).  The search is EXACT: the neighbours are the first k of a
+stable argsort of all distances (ties by ascending database index, NaN last), where the reference's hnswlib graph is approximate.
+Any k <= N is served at any N <= 2^24: k <= 1024 by the fused top-k kernel, larger k by a full ranking, in one workgroup's LDS up
+to N = 16384 and through sorted runs merged in a global workspace above (queries batched to keep it under
+``RANK_WORKSPACE_BUDGET``).
 
 :class:`PoseIndex` stands in for the subset of ``hnswlib.Index`` the reference uses.  Its file format (``save_index``) is our own: an
 uncompressed numpy ``.npz`` written to exactly the given path, with the arrays
@@ -34,6 +37,15 @@ METHODS = {"euclidean_distance": "euclidean", "cosine_similarity": "cosine", "ma
 PENALIZATIONS = ("zero_coord", "none", "mean", "max")
 APPROACHES = tuple(capi.POSE_APPROACH)
 SPACES = {"l2": "l2sq", "cosine": "cos_normalised"}
+RANK_WORKSPACE_BUDGET = 1 << 30   # bytes of pose_rank_any workspace (16 B per query and database row) one launch may take
+
+
+def rank_any_batch(n: int, batch: int, budget: int = None) -> int:
+    """Queries per ``pose_rank_any`` call at database size n: at most `batch`, the C ABI's 65535, and what fits the budget."""
+    per_query = capi.lib().stl_pose_rank_any_workspace(1, n)
+    capi.check(min(per_query, 0), "stl_pose_rank_any")
+    budget = RANK_WORKSPACE_BUDGET if budget is None else budget
+    return max(1, min(int(batch), 65535, budget // per_query))
 
 
 def _check_approach(approach: str) -> None:
@@ -76,7 +88,8 @@ def _num_out(num_retrievals: int, n: int) -> int:
 def search(query, database, k: int, method: str = "euclidean", penalization: str = "zero_coord", confidence=None
            ) -> Tuple[torch.Tensor, torch.Tensor]:
     """Exact first-k search on the GPU: (idx int64 [Q, k], dist float32 [Q, k]).  k <= 1024 runs the fused top-k kernel at any
-    N; larger k the full-ranking kernel (N <= 16384)."""
+    N; larger k a full ranking: ``pose_rank`` up to N = 16384, ``pose_rank_any`` above, in query batches of
+    ``rank_any_batch(N, 2048)``."""
     q, db = _dev(query), _dev(database)
     c = _dev(confidence) if confidence is not None else None
     n = db.shape[0]
@@ -85,10 +98,17 @@ def search(query, database, k: int, method: str = "euclidean", penalization: str
                 torch.empty(q.shape[0], 0, dtype=torch.float32, device=q.device))
     if k <= capi.POSE_TOPK_MAX:
         return torch.ops.stlpose.pose_topk(q, c, db, method, penalization, k)
-    if n > capi.POSE_RANK_MAX:
-        raise ValueError(f"a ranking of {k} > {capi.POSE_TOPK_MAX} entries needs N <= {capi.POSE_RANK_MAX} (N = {n})")
-    idx, dist, _ = torch.ops.stlpose.pose_rank(q, c, db, method, penalization, k, None, None, 0)
-    return idx, dist
+    if n <= capi.POSE_RANK_MAX:
+        idx, dist, _ = torch.ops.stlpose.pose_rank(q, c, db, method, penalization, k, None, None, 0)
+        return idx, dist
+    if n > capi.POSE_RANK_ANY_MAX:
+        raise ValueError(f"a ranking of {k} > {capi.POSE_TOPK_MAX} entries needs N <= {capi.POSE_RANK_ANY_MAX} (N = {n})")
+    step = rank_any_batch(n, 2048)
+    parts = [torch.ops.stlpose.pose_rank_any(q[q0:q0 + step], c[q0:q0 + step] if c is not None else None, db, method, penalization, k,
+                                             None, None, 0)[:2] for q0 in range(0, q.shape[0], step)]
+    if not parts:
+        return (torch.empty(0, k, dtype=torch.int64, device=q.device), torch.empty(0, k, dtype=torch.float32, device=q.device))
+    return torch.cat([p[0] for p in parts]), torch.cat([p[1] for p in parts])
 
 
 def get_neighbors_idxs(query, num_retrievals: int = 10, approach: str = "full_body", retrieval_method: str = "knn",

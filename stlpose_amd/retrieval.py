@@ -3,7 +3,9 @@
 
 ``retrieval_experiment`` ranks every pose against the whole database and scores the rankings per label level inside the
 ``stlpose::pose_rank`` kernel (N <= 16384): no [N, N] array is ever written.  Above that size it runs ``stlpose::pose_topk``
-(num_retrievals <= 1024) and scores the returned rankings on the host.
+and scores the returned rankings on the host when num_retrievals <= 1024, and ``stlpose::pose_rank_any`` otherwise (the full
+ranking included): sorted runs merged in a global workspace, scores on the device, queries batched so that the workspace stays
+under ``pose_database.RANK_WORKSPACE_BUDGET`` (1 GiB).
 """
 from __future__ import annotations
 
@@ -18,7 +20,7 @@ import torch
 
 from . import capi
 from . import ops  # noqa: F401
-from .pose_database import METHODS, PENALIZATIONS, _check_approach, _dev
+from .pose_database import METHODS, PENALIZATIONS, _check_approach, _dev, rank_any_batch
 
 SCORE_KEYS = ("p@1", "p@5", "p@10", "p@rel", "mAP", "r@1", "r@5", "r@10", "r@rel", "mAR")   # STL_POSE_NSCORES, kernel order
 
@@ -69,7 +71,8 @@ def retrieval_experiment(features, labels, approach: str = "full_body", method: 
 
     features: [N, D] pose vectors (every pose is a query against all of them); labels: {level: per-pose labels} (e.g.
     {"character": ..., "narrative": ...}) or a list of such sequences, at most 4 levels.  method: the reference's retrieval_method
-    names (or the kernel's own); num_retrievals = -1 scores the full ranking.  Returns {level: [score_retrievals dict per query]}
+    names (or the kernel's own); num_retrievals = -1 scores the full ranking; batch: queries per launch (fewer where the
+    workspace of a ranking above N = 16384 would pass its budget).  Returns {level: [score_retrievals dict per query]}
     in query order, and the elapsed seconds under the key "elapsed_time"."""
     _check_approach(approach)
     m = METHODS.get(method, method)
@@ -90,8 +93,11 @@ def retrieval_experiment(features, labels, approach: str = "full_body", method: 
     k_eff = n if num_retrievals < 0 else int(num_retrievals)
     if k_eff < 11 or k_eff > n:
         raise ValueError(f"num_retrievals = {num_retrievals}: scoring needs 11 <= retrievals <= N = {n} (p@10 reads rank 10)")
-    if n > capi.POSE_RANK_MAX and k_eff > capi.POSE_TOPK_MAX:
-        raise ValueError(f"N = {n} > {capi.POSE_RANK_MAX}: a ranking longer than {capi.POSE_TOPK_MAX} is not supported")
+    rank_any = n > capi.POSE_RANK_MAX and k_eff > capi.POSE_TOPK_MAX
+    if rank_any:
+        if n > capi.POSE_RANK_ANY_MAX:
+            raise ValueError(f"N = {n} > {capi.POSE_RANK_ANY_MAX}: a ranking longer than {capi.POSE_TOPK_MAX} is not supported")
+        batch = rank_any_batch(n, batch)
     start = time.time()
     db = _dev(features)
     conf = _dev(confidence) if confidence is not None else None
@@ -102,6 +108,9 @@ def retrieval_experiment(features, labels, approach: str = "full_body", method: 
         c = conf[q0:q1] if conf is not None else None
         if n <= capi.POSE_RANK_MAX:
             _, _, s = torch.ops.stlpose.pose_rank(db[q0:q1], c, db, m, penalization, 0, lab, lab[:, q0:q1], k_eff)
+            scores[q0:q1] = s.cpu().numpy()
+        elif rank_any:
+            _, _, s = torch.ops.stlpose.pose_rank_any(db[q0:q1], c, db, m, penalization, 0, lab, lab[:, q0:q1], k_eff)
             scores[q0:q1] = s.cpu().numpy()
         else:
             idx, _ = torch.ops.stlpose.pose_topk(db[q0:q1], c, db, m, penalization, k_eff)
