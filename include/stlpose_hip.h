@@ -441,6 +441,51 @@ int stl_box_select(const float* boxes, const float* scores, const int64_t* label
 int stl_heatmap_resize_argmax(const float* hm, int BJ, int H, int W, int Ho, int Wo, int32_t* idx, float* maxval, float* preds,
                               void* stream);
 
+/* ---- COCO box AP (stlpose_amd/csrc/box_ap.hip): the validation metric of src/02_train_faster_rcnn.py:241-280 and
+ * src/03_evaluate_faster_rcnn.py:119-184, i.e. the published COCOeval(..., "bbox") in two steps.  Exact: fp64 as written in that
+ * file's head, integer sums, order-free maxima; tests/box_ap_ref.py reproduces both outputs bit for bit. */
+#define STL_BOX_AP_THRS 10         /* IoU thresholds of stl_box_ap_match (.50:.05:.95) */
+#define STL_BOX_AP_AREAS 4         /* area ranges of stl_box_ap_match (all, small, medium, large) */
+#define STL_BOX_AP_DETS 100        /* detections kept per (image, category): the largest maxDets */
+#define STL_BOX_AP_GT_MAX 128      /* ground truths per (image, category): the fp64 IoU tile [100, 128] is 100 KiB of LDS at the cap */
+#define STL_BOX_AP_SCAN_TILE 1024  /* slots per scan step of stl_box_ap_accumulate (its workgroup size) */
+#define STL_BOX_AP_MAXDETS_MAX 8   /* maxDets values of one stl_box_ap_accumulate call */
+#define STL_BOX_AP_RECS_MAX 101    /* recall points of one stl_box_ap_accumulate call */
+
+/* COCOeval.evaluateImg for "bbox", one workgroup per (image, category).  Detections: boxes fp64 [N, 4] (x, y, w, h), scores fp32
+ * [N] (no NaN), labels int64 [N], det_offsets int64 [I + 1] (image i owns rows det_offsets[i] .. det_offsets[i+1]-1, at most max_n
+ * <= STL_BOX_MAX of them).  Ground truth: gt_boxes fp64 [G, 4] (x, y, w, h), gt_area fp64 [G], gt_label int64 [G], gt_crowd uint8
+ * [G], gt_offsets int64 [I + 1]; at most max_g <= STL_BOX_AP_GT_MAX rows per (image, category).  cats int64 [K], strictly
+ * ascending.  All of these are device pointers.  iou_thrs [STL_BOX_AP_THRS] and area_ranges [STL_BOX_AP_AREAS][2] (lo, hi) are
+ * HOST arrays of doubles: they travel in the kernel arguments.
+ * Per (image, category): the detections with that label in stable descending score order (ties keep input order), the first
+ * STL_BOX_AP_DETS kept; iou = maskApi.bbIou in fp64 (w = min(dx+dw, gx+gw) - max(dx, gx), <= 0 gives 0, the same for h; i = w*h;
+ * u = crowd ? dw*dh : dw*dh + gw*gh - i; i / u); per threshold t and area range the greedy match in score order: best = min(t,
+ * 1 - 1e-10), walk the ground truth (non-ignored first, stable; ignored = crowd or area < lo or area > hi), skip a matched
+ * non-crowd one, stop at the first ignored one once a non-ignored one is held, skip iou < best, else take it (a tie moves to the
+ * later one).  A matched detection inherits its match's ignore flag; an unmatched one is ignored when its w*h is outside the range.
+ * Outputs, one slot per detection row (the caller presets slot_cat to -1: rows whose label is not in cats, or beyond the first
+ * STL_BOX_AP_DETS of their category, keep it): the kept detections of (image i, category k) fill the slots det_offsets[i] + (rows
+ * of the image with a smaller label) + rank, rank = 0 .. in score order, with slot_score, slot_cat = k, slot_rank = rank and bit
+ * t * STL_BOX_AP_AREAS + a of slot_matched / slot_ignored.  npig int32 [I, K, STL_BOX_AP_AREAS]: the non-ignored ground truths
+ * (-1: the segment was refused, its offsets are inconsistent or above the caps). */
+int stl_box_ap_match(const double* boxes, const float* scores, const int64_t* labels, const int64_t* det_offsets, int64_t N, int max_n,
+                     const double* gt_boxes, const double* gt_area, const int64_t* gt_label, const uint8_t* gt_crowd,
+                     const int64_t* gt_offsets, int64_t G, int max_g, int num_images, const int64_t* cats, int K,
+                     const double* iou_thrs, const double* area_ranges, float* slot_score, int32_t* slot_cat, int32_t* slot_rank,
+                     uint64_t* slot_matched, uint64_t* slot_ignored, int32_t* npig, void* stream);
+/* COCOeval.accumulate with the reductions of summarize, one workgroup per (threshold, area range, maxDets, category); it knows
+ * nothing of boxes.  matched / ignored uint64 [S] (bit t * A + a), rank int32 [S]; order int64 [S]: the slots grouped by category,
+ * each group in stable descending score order (images ascending, ranks ascending among equal scores); cat_offsets int64 [K + 1]:
+ * category k owns order[cat_offsets[k] .. cat_offsets[k+1]-1]; npig int64 [K, A]: non-ignored ground truths over all images.
+ * max_dets [M] and rec_thrs [R] (rising from 0) are HOST arrays.  Over the group's slots with rank < max_dets[m]: tp = prefix count
+ * of matched & !ignored, fp = of !matched & !ignored, rc = tp / npig, pr = tp / (fp + tp + 2^-52) in fp64;
+ * recall fp64 [T, K, A, M] = the last rc (0 without slots); precision fp64 [T, R, K, A, M] = per recall point r the largest pr
+ * over the positions with rc >= r (0 if none): the precision envelope read at searchsorted(rc, r, "left").  npig == 0: -1. */
+int stl_box_ap_accumulate(const uint64_t* matched, const uint64_t* ignored, const int32_t* rank, const int64_t* order,
+                          const int64_t* cat_offsets, const int64_t* npig, int64_t S, int K, int T, int A, const int32_t* max_dets,
+                          int M, const double* rec_thrs, int R, double* precision, double* recall, void* stream);
+
 /* ---- EfficientDet person detector (stlpose_amd/csrc/detector.hip): src/models/EfficientDet.py with
  * models/efficientdet_utils/{model,utils}.py and models/efficientnet/{model,utils,utils_extra}.py, NHWC activations; inference, and
  * fine-tuning of the heads (further down).

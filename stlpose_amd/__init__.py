@@ -18,3 +18,4 @@ from .efficientdet import EfficientDetBackbone, EfficientDet, setup_detector  # 
 from .topdown import detect_poses  # noqa: F401,E402
 from .adain import AdaINStylizer  # noqa: F401,E402
 from .styled_coco import create_styled_dataset  # noqa: F401,E402
+from .detection_eval import box_ap, CocoEvaluator, DetectorEvaluator  # noqa: F401,E402

@@ -28,6 +28,9 @@ POSE_TOPK_MAX, POSE_RANK_MAX, POSE_RANK_LABELS_MAX, POSE_NSCORES = 1024, 16384, 
 POSE_RANK_ANY_MAX = 1 << 24   # STL_POSE_RANK_ANY_MAX: largest N of stl_pose_rank_any
 # top-down extraction (STL_BOX_MAX, STL_RESIZE_SRC_MAX, STL_RESIZE_DST_MAX)
 BOX_MAX, RESIZE_SRC_MAX, RESIZE_DST_MAX = 4096, 16384, 2048
+# COCO box AP (STL_BOX_AP_*): thresholds, area ranges, detections kept per (image, category), ground truths per (image, category),
+# scan tile, maxDets values and recall points per call
+BOX_AP_THRS, BOX_AP_AREAS, BOX_AP_DETS, BOX_AP_GT_MAX, BOX_AP_SCAN_TILE, BOX_AP_MAXDETS_MAX, BOX_AP_RECS_MAX = 10, 4, 100, 128, 1024, 8, 101
 # person detector (STL_DET_NMS_MAX)
 DET_NMS_MAX = 65536
 # AdaIN gather ops (STL_GATHER_*)
@@ -224,6 +227,9 @@ SIGNATURES = {
     "stl_pose_rank_any": [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, i32, i32, vp, vp, i64, vp],
     "stl_box_select": [vp, vp, vp, vp, i32, i64, i32, i64, i32, f32, C.c_double, vp, vp, vp],
     "stl_heatmap_resize_argmax": [vp, i32, i32, i32, i32, i32, vp, vp, vp, vp],
+    "stl_box_ap_match": [vp, vp, vp, vp, i64, i32, vp, vp, vp, vp, vp, i64, i32, i32, vp, i32, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                         vp, vp, vp, vp, vp, vp, vp],
+    "stl_box_ap_accumulate": [vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, C.POINTER(i32), i32, C.POINTER(C.c_double), i32, vp, vp, vp],
     "stl_det_preprocess": [vp, i32, i32, vp, vp],
     "stl_det_stem": [vp, vp, vp, vp, i32, i32, i32, i32, vp],
     "stl_det_dwconv": [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp],

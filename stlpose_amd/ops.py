@@ -482,6 +482,161 @@ _define("det_loss(Tensor regression, Tensor classification, Tensor anchors, Tens
         lambda r, c, a, g, o, al, ga, bw: (r.new_empty(2), r.new_empty(r.shape), c.new_empty(c.shape),
                                            r.new_empty(r.shape[0], dtype=torch.int32)))
 
+# ------------------------------------------------------------------ COCO box AP (csrc/box_ap.hip; COCOeval "bbox")
+# Every shape, dtype, device and cap the kernels rely on is checked here, before anything is launched.
+class BoxApCapError(ValueError):
+    """A cap of box_ap_match is exceeded.  ``image_index`` is the image's position in the ragged tables: the op knows no image ids
+    (detection_eval re-raises with the id)."""
+
+    def __init__(self, message: str, image_index: int):
+        super().__init__(message)
+        self.image_index = image_index
+
+
+def _ragged(op: str, name: str, offsets, n: int):
+    """offsets int64 [I + 1] rising from 0 to n, as a CPU tensor; the rows per image."""
+    if offsets.dim() != 1 or offsets.shape[0] < 1 or offsets.dtype != torch.int64:
+        raise ValueError(f"stlpose {op}: {name} must be int64 [I + 1], got {offsets.dtype} {tuple(offsets.shape)}")
+    off = offsets.cpu()
+    per = off[1:] - off[:-1]
+    if int(off[0]) != 0 or int(off[-1]) != n or bool((per < 0).any()):
+        raise ValueError(f"stlpose {op}: {name} must rise from 0 to {n}")
+    return off, per
+
+
+def _doubles(v):
+    return (capi.C.c_double * len(v))(*[float(x) for x in v])
+
+
+def _box_ap_match(boxes, scores, labels, det_offsets, gt_boxes, gt_area, gt_label, gt_crowd, gt_offsets, categories, iou_thrs, area_ranges):
+    op = "box_ap_match"
+    if boxes.dim() != 2 or boxes.shape[1] != 4 or boxes.dtype != torch.float64:
+        raise ValueError(f"stlpose {op}: boxes must be float64 [N, 4] (x, y, w, h), got {boxes.dtype} {tuple(boxes.shape)}")
+    n = boxes.shape[0]
+    if scores.dim() != 1 or scores.shape[0] != n or scores.dtype != torch.float32:
+        raise ValueError(f"stlpose {op}: scores must be float32 [N={n}], got {scores.dtype} {tuple(scores.shape)}")
+    if labels.dim() != 1 or labels.shape[0] != n or labels.dtype != torch.int64:
+        raise ValueError(f"stlpose {op}: labels must be int64 [N={n}], got {labels.dtype} {tuple(labels.shape)}")
+    if gt_boxes.dim() != 2 or gt_boxes.shape[1] != 4 or gt_boxes.dtype != torch.float64:
+        raise ValueError(f"stlpose {op}: gt_boxes must be float64 [G, 4] (x, y, w, h), got {gt_boxes.dtype} {tuple(gt_boxes.shape)}")
+    g = gt_boxes.shape[0]
+    for name, t, dt in (("gt_area", gt_area, torch.float64), ("gt_label", gt_label, torch.int64), ("gt_crowd", gt_crowd, torch.uint8)):
+        if t.dim() != 1 or t.shape[0] != g or t.dtype != dt:
+            raise ValueError(f"stlpose {op}: {name} must be {dt} [G={g}], got {t.dtype} {tuple(t.shape)}")
+    if categories.dim() != 1 or categories.dtype != torch.int64:
+        raise ValueError(f"stlpose {op}: categories must be int64 [K], got {categories.dtype} {tuple(categories.shape)}")
+    cats = categories.cpu()
+    nk = cats.shape[0]
+    if nk > 65535 or bool((cats[1:] <= cats[:-1]).any()):
+        raise ValueError(f"stlpose {op}: categories must be strictly ascending, at most 65535 of them")
+    doff, dper = _ragged(op, "det_offsets", det_offsets, n)
+    goff, gper = _ragged(op, "gt_offsets", gt_offsets, g)
+    ni = dper.numel()
+    if gper.numel() != ni:
+        raise ValueError(f"stlpose {op}: det_offsets cover {ni} images, gt_offsets {gper.numel()}")
+    if len(iou_thrs) != capi.BOX_AP_THRS or len(area_ranges) != 2 * capi.BOX_AP_AREAS:
+        raise ValueError(f"stlpose {op}: {capi.BOX_AP_THRS} IoU thresholds and {capi.BOX_AP_AREAS} (lo, hi) area ranges, got "
+                         f"{len(iou_thrs)} and {len(area_ranges)} numbers")
+    max_n = int(dper.max()) if ni else 0
+    if max_n > capi.BOX_MAX:
+        raise BoxApCapError(f"stlpose {op}: the image at table position {int(dper.argmax())} has {max_n} detections; the cap is "
+                            f"{capi.BOX_MAX} (STL_BOX_MAX) per image", int(dper.argmax()))
+    max_g = 0
+    if g and nk:   # ground truths per (image, category)
+        lab = gt_label.cpu()
+        ci = torch.searchsorted(cats, lab).clamp_(max=nk - 1)
+        known = cats[ci] == lab
+        img = torch.repeat_interleave(torch.arange(ni), gper)
+        cnt = torch.bincount((img * nk + ci)[known], minlength=ni * nk)
+        max_g = int(cnt.max())
+        if max_g > capi.BOX_AP_GT_MAX:
+            w = int(cnt.argmax())
+            raise BoxApCapError(f"stlpose {op}: the image at table position {w // nk} has {max_g} ground truths of category "
+                                f"{int(cats[w % nk])}; the cap is {capi.BOX_AP_GT_MAX} (STL_BOX_AP_GT_MAX) per image and category", w // nk)
+    if bool(torch.isnan(scores).any()):
+        raise ValueError(f"stlpose {op}: a score is NaN")
+    if not boxes.is_cuda:
+        raise RuntimeError(f"stlpose {op}: boxes must be on the GPU")
+    dev = boxes.device
+    _same_device((("scores", scores), ("labels", labels), ("gt_boxes", gt_boxes), ("gt_area", gt_area), ("gt_label", gt_label),
+                  ("gt_crowd", gt_crowd)), dev)
+    slot_score = torch.zeros(n, dtype=torch.float32, device=dev)
+    slot_cat = torch.full((n,), -1, dtype=torch.int32, device=dev)   # rows no workgroup claims stay out of every category
+    slot_rank = torch.zeros(n, dtype=torch.int32, device=dev)
+    matched = torch.zeros(n, dtype=torch.int64, device=dev)
+    ignored = torch.zeros(n, dtype=torch.int64, device=dev)
+    npig = torch.empty(ni, nk, capi.BOX_AP_AREAS, dtype=torch.int32, device=dev)
+    b, s, l = boxes.contiguous(), scores.contiguous(), labels.contiguous()
+    gb, ga, gl, gc = gt_boxes.contiguous(), gt_area.contiguous(), gt_label.contiguous(), gt_crowd.contiguous()
+    do, go, ct = doff.to(dev), goff.to(dev), cats.to(dev)
+    capi.call("stl_box_ap_match", b.data_ptr(), s.data_ptr(), l.data_ptr(), do.data_ptr(), n, max_n, gb.data_ptr(), ga.data_ptr(),
+              gl.data_ptr(), gc.data_ptr(), go.data_ptr(), g, max_g, ni, ct.data_ptr(), nk, _doubles(iou_thrs), _doubles(area_ranges),
+              slot_score.data_ptr(), slot_cat.data_ptr(), slot_rank.data_ptr(), matched.data_ptr(), ignored.data_ptr(), npig.data_ptr(),
+              _st())
+    return slot_score, slot_cat, slot_rank, matched, ignored, npig
+
+
+def _box_ap_match_fake(boxes, scores, labels, det_offsets, gt_boxes, gt_area, gt_label, gt_crowd, gt_offsets, categories, iou_thrs,
+                       area_ranges):
+    n = boxes.shape[0]
+    return (boxes.new_empty(n, dtype=torch.float32), boxes.new_empty(n, dtype=torch.int32), boxes.new_empty(n, dtype=torch.int32),
+            boxes.new_empty(n, dtype=torch.int64), boxes.new_empty(n, dtype=torch.int64),
+            boxes.new_empty(det_offsets.shape[0] - 1, categories.shape[0], capi.BOX_AP_AREAS, dtype=torch.int32))
+
+
+# slot_score, slot_cat (-1: the row is in no category's list), slot_rank, matched and ignored bits (bit t * 4 + a) per detection
+# row, npig [I, K, 4]; the slot layout is stated at stl_box_ap_match in include/stlpose_hip.h
+_define("box_ap_match(Tensor boxes, Tensor scores, Tensor labels, Tensor det_offsets, Tensor gt_boxes, Tensor gt_area, Tensor gt_label, "
+        "Tensor gt_crowd, Tensor gt_offsets, Tensor categories, float[] iou_thrs, float[] area_ranges) "
+        "-> (Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)", _box_ap_match, _box_ap_match_fake)
+
+
+def _box_ap_accumulate(matched, ignored, rank, order, cat_offsets, npig, num_thrs: int, max_dets, rec_thrs):
+    op = "box_ap_accumulate"
+    if matched.dim() != 1 or matched.dtype != torch.int64:
+        raise ValueError(f"stlpose {op}: matched must be int64 [S], got {matched.dtype} {tuple(matched.shape)}")
+    ns = matched.shape[0]
+    for name, t, dt in (("ignored", ignored, torch.int64), ("rank", rank, torch.int32), ("order", order, torch.int64)):
+        if t.dim() != 1 or t.shape[0] != ns or t.dtype != dt:
+            raise ValueError(f"stlpose {op}: {name} must be {dt} [S={ns}], got {t.dtype} {tuple(t.shape)}")
+    if npig.dim() != 2 or npig.dtype != torch.int64 or npig.shape[1] < 1:
+        raise ValueError(f"stlpose {op}: npig must be int64 [K, A], got {npig.dtype} {tuple(npig.shape)}")
+    nk, na = npig.shape
+    if cat_offsets.dim() != 1 or cat_offsets.shape[0] != nk + 1 or cat_offsets.dtype != torch.int64:
+        raise ValueError(f"stlpose {op}: cat_offsets must be int64 [K + 1 = {nk + 1}], got {cat_offsets.dtype} {tuple(cat_offsets.shape)}")
+    co = cat_offsets.cpu()
+    if int(co[0]) < 0 or int(co[-1]) > ns or bool((co[1:] < co[:-1]).any()):
+        raise ValueError(f"stlpose {op}: cat_offsets must rise within 0 .. S = {ns}")
+    if num_thrs < 1 or num_thrs * na > 64:
+        raise ValueError(f"stlpose {op}: {num_thrs} thresholds x {na} area ranges; a slot has 64 bits")
+    if not 1 <= len(max_dets) <= capi.BOX_AP_MAXDETS_MAX:
+        raise ValueError(f"stlpose {op}: {len(max_dets)} maxDets values; the cap is {capi.BOX_AP_MAXDETS_MAX} (STL_BOX_AP_MAXDETS_MAX)")
+    nr = len(rec_thrs)
+    if not 1 <= nr <= capi.BOX_AP_RECS_MAX:
+        raise ValueError(f"stlpose {op}: {nr} recall points; the cap is {capi.BOX_AP_RECS_MAX} (STL_BOX_AP_RECS_MAX)")
+    if rec_thrs[0] != 0.0 or not all(b > a for a, b in zip(rec_thrs[:-1], rec_thrs[1:])):
+        raise ValueError(f"stlpose {op}: the recall points must rise from 0")
+    if not matched.is_cuda:
+        raise RuntimeError(f"stlpose {op}: matched must be on the GPU")
+    dev = matched.device
+    _same_device((("ignored", ignored), ("rank", rank), ("order", order), ("npig", npig)), dev)
+    nm = len(max_dets)
+    precision = torch.empty(num_thrs, nr, nk, na, nm, dtype=torch.float64, device=dev)
+    recall = torch.empty(num_thrs, nk, na, nm, dtype=torch.float64, device=dev)
+    m, i, r, o, p = matched.contiguous(), ignored.contiguous(), rank.contiguous(), order.contiguous(), npig.contiguous()
+    c = co.to(dev)
+    capi.call("stl_box_ap_accumulate", m.data_ptr(), i.data_ptr(), r.data_ptr(), o.data_ptr(), c.data_ptr(), p.data_ptr(), ns, nk,
+              int(num_thrs), na, (capi.i32 * nm)(*[int(v) for v in max_dets]), nm, _doubles(rec_thrs), nr, precision.data_ptr(),
+              recall.data_ptr(), _st())
+    return precision, recall
+
+
+# precision [T, R, K, A, M] and recall [T, K, A, M] (COCOeval.eval's), -1 where a (category, area range) has no ground truth to find
+_define("box_ap_accumulate(Tensor matched, Tensor ignored, Tensor rank, Tensor order, Tensor cat_offsets, Tensor npig, int num_thrs, "
+        "int[] max_dets, float[] rec_thrs) -> (Tensor, Tensor)", _box_ap_accumulate,
+        lambda m, i, r, o, c, p, t, md, rt: (m.new_empty(t, len(rt), p.shape[0], p.shape[1], len(md), dtype=torch.float64),
+                                             m.new_empty(t, p.shape[0], p.shape[1], len(md), dtype=torch.float64)))
+
 OPS = ["person_mse", "heatmap_argmax", "final_preds", "flip_merge", "flip_merge_backward", "gaussian_targets", "affine_crop",
        "hrnet_forward", "hrnet_backward", "hrnet_backward_input", "pose_vectors", "pose_distances", "pose_topk", "pose_rank", "pose_rank_any",
-       "box_select", "heatmap_resize_argmax", "det_decode", "det_nms", "det_loss"]
+       "box_select", "heatmap_resize_argmax", "det_decode", "det_nms", "det_loss", "box_ap_match", "box_ap_accumulate"]
