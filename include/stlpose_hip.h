@@ -486,6 +486,53 @@ int stl_box_ap_accumulate(const uint64_t* matched, const uint64_t* ignored, cons
                           const int64_t* cat_offsets, const int64_t* npig, int64_t S, int K, int T, int A, const int32_t* max_dets,
                           int M, const double* rec_thrs, int R, double* precision, double* recall, void* stream);
 
+/* ---- Pose scoring (stlpose_amd/csrc/keypoint_eval.hip): the tail of src/03_evaluate.py, i.e. rescoring + OKS-NMS
+ * (lib/metrics.py:211-262, lib/nms.py) and the published COCOeval(..., "keypoints").evaluateImg; the accumulate step above
+ * finishes keypoint AP unchanged (T = 10, A = 3).  17 joints.  Exact up to exp: every operation is fp64 as written in that file's
+ * head; the device's fp64 exp and the sum of at most 17 terms may differ from numpy's in the last bits (one OKS by less than
+ * 1e-13), and OKS values are only compared, so the outputs equal the host's whenever no comparison is closer than that. */
+#define STL_POSE_JOINTS 17         /* joints of a pose in this section */
+#define STL_POSE_NMS_MAX 1024      /* persons per image of the rescoring + NMS entry point */
+#define STL_POSE_SUM_NUMPY 0       /* sum_order of the rescoring: numpy's pairwise order */
+#define STL_POSE_SUM_SERIAL 1      /* ... one running sum, the reference's loop */
+#define STL_OKS_AP_THRS 10         /* OKS thresholds of the match (.50:.05:.95) */
+#define STL_OKS_AP_AREAS 3         /* area ranges of the match (all, medium, large) */
+#define STL_OKS_AP_DETS 20         /* detections kept per image: the largest maxDets */
+
+/* Rescoring and greedy OKS suppression over a ragged table, one workgroup per image.  preds [P, 17, 3] (x, y, confidence) of
+ * fp32 (preds_f64 = 0) or fp64 (1), boxes fp64 [P, 6] (centre x, y, scale x, y, area, box score), offsets int64 [I + 1]: image i
+ * owns rows offsets[i] .. offsets[i+1]-1, at most max_n <= STL_POSE_NMS_MAX of them (an image above max_n gets count -1).
+ * score fp64 [P] = box score x mean confidence of the joints with confidence > in_vis_thr (compared in the dtype of preds), 0 if
+ * there is none; the mean in that dtype, divided by n, the product in fp64.  sum_order STL_POSE_SUM_NUMPY: numpy's order, what
+ * conf[good].mean() of the host function gives (n < 8: a running sum; else eight running sums over the first 8 * (n / 8)
+ * values, ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7)), then the rest in order); STL_POSE_SUM_SERIAL: one running sum over the joints
+ * in order, what the reference's loop gives (lib/metrics.py:242-250).  The two differ by an ulp for some n >= 8.
+ * Suppression: descending score, equal scores in descending input position; a candidate goes when its OKS with a kept person
+ * exceeds oks_thr.  OKS = sum_k exp(-e_k) / 17, e_k = (dx^2 + dy^2) / var[k] / ((area_kept + area_cand) / 2 + 2^-52) / 2, fp64,
+ * var [17] a HOST array ((2 sigma)^2).  keep int32 [P]: per image segment the image-local rows of the kept persons in that
+ * order, then -1; count int32 [I]. */
+int stl_pose_rescore_nms(const void* preds, int preds_f64, int sum_order, const double* boxes, const int64_t* offsets, int num_images, int64_t P,
+                         int max_n, double in_vis_thr, double oks_thr, const double* var, double* score, int32_t* keep,
+                         int32_t* count, void* stream);
+/* COCOeval.evaluateImg for "keypoints", one workgroup per image.  Detections: kpts fp64 [N, 17, 3], scores fp64 [N] (no NaN), area
+ * fp64 [N] or NULL (then (max x - min x) * (max y - min y) over the 17 joints), det_offsets int64 [I + 1], at most max_n <=
+ * STL_BOX_MAX rows per image.  Ground truth: gt_kpts fp64 [G, 17, 3] (x, y, visibility), gt_area fp64 [G], gt_bbox fp64 [G, 4]
+ * (x, y, w, h), gt_crowd uint8 [G], gt_numkp int32 [G], gt_offsets int64 [I + 1], at most max_g <= STL_BOX_AP_GT_MAX rows per
+ * image.  oks_thrs [STL_OKS_AP_THRS], area_ranges [STL_OKS_AP_AREAS][2] (lo, hi, both inclusive) and var [17] are HOST arrays.
+ * Per image: the detections in stable descending score order (-0 == +0), the first STL_OKS_AP_DETS kept; the ground truth per
+ * area range with the ignored last, stable (ignored: crowd, or gt_numkp == 0, or area outside the range); OKS as computeOks
+ * writes it: over the joints with visibility > 0 when there is one (dx = xd - xg), else over all 17 with the distance to the
+ * doubled box (dx = max(0, x0 - xd) + max(0, xd - x1), x0 = x - w, x1 = x + 2 w); e = (dx^2 + dy^2) / var / (gt_area + 2^-52) / 2,
+ * the mean of exp(-e).  The greedy match is that of the box match above with OKS for IoU (a crowd can be matched again; an
+ * unmatched detection whose area is outside the range is ignored).  Outputs as there with K = 1: the kept detections of image i
+ * fill the slots det_offsets[i] + rank with slot_score (fp64), slot_cat = 0 (the caller presets -1), slot_rank and bit
+ * t * STL_OKS_AP_AREAS + a of slot_matched / slot_ignored; npig int32 [I, 1, STL_OKS_AP_AREAS] (-1: the image was refused). */
+int stl_oks_ap_match(const double* kpts, const double* scores, const double* area, const int64_t* det_offsets, int64_t N, int max_n,
+                     const double* gt_kpts, const double* gt_area, const double* gt_bbox, const uint8_t* gt_crowd,
+                     const int32_t* gt_numkp, const int64_t* gt_offsets, int64_t G, int max_g, int num_images,
+                     const double* oks_thrs, const double* area_ranges, const double* var, double* slot_score, int32_t* slot_cat,
+                     int32_t* slot_rank, uint64_t* slot_matched, uint64_t* slot_ignored, int32_t* npig, void* stream);
+
 /* ---- EfficientDet person detector (stlpose_amd/csrc/detector.hip): src/models/EfficientDet.py with
  * models/efficientdet_utils/{model,utils}.py and models/efficientnet/{model,utils,utils_extra}.py, NHWC activations; inference, and
  * fine-tuning of the heads (further down).

@@ -31,6 +31,10 @@ BOX_MAX, RESIZE_SRC_MAX, RESIZE_DST_MAX = 4096, 16384, 2048
 # COCO box AP (STL_BOX_AP_*): thresholds, area ranges, detections kept per (image, category), ground truths per (image, category),
 # scan tile, maxDets values and recall points per call
 BOX_AP_THRS, BOX_AP_AREAS, BOX_AP_DETS, BOX_AP_GT_MAX, BOX_AP_SCAN_TILE, BOX_AP_MAXDETS_MAX, BOX_AP_RECS_MAX = 10, 4, 100, 128, 1024, 8, 101
+# pose scoring (STL_POSE_JOINTS, STL_POSE_NMS_MAX, STL_OKS_AP_*): joints, persons per image of the NMS, OKS thresholds, area ranges,
+# detections kept per image
+POSE_JOINTS, POSE_NMS_MAX, OKS_AP_THRS, OKS_AP_AREAS, OKS_AP_DETS = 17, 1024, 10, 3, 20
+POSE_SUM_ORDER = {"numpy": 0, "reference": 1}   # STL_POSE_SUM_NUMPY, STL_POSE_SUM_SERIAL
 # person detector (STL_DET_NMS_MAX)
 DET_NMS_MAX = 65536
 # AdaIN gather ops (STL_GATHER_*)
@@ -230,6 +234,9 @@ SIGNATURES = {
     "stl_box_ap_match": [vp, vp, vp, vp, i64, i32, vp, vp, vp, vp, vp, i64, i32, i32, vp, i32, C.POINTER(C.c_double), C.POINTER(C.c_double),
                          vp, vp, vp, vp, vp, vp, vp],
     "stl_box_ap_accumulate": [vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, C.POINTER(i32), i32, C.POINTER(C.c_double), i32, vp, vp, vp],
+    "stl_pose_rescore_nms": [vp, i32, i32, vp, vp, i32, i64, i32, C.c_double, C.c_double, C.POINTER(C.c_double), vp, vp, vp, vp],
+    "stl_oks_ap_match": [vp, vp, vp, vp, i64, i32, vp, vp, vp, vp, vp, vp, i64, i32, i32, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                         C.POINTER(C.c_double), vp, vp, vp, vp, vp, vp, vp],
     "stl_det_preprocess": [vp, i32, i32, vp, vp],
     "stl_det_stem": [vp, vp, vp, vp, i32, i32, i32, i32, vp],
     "stl_det_dwconv": [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp],

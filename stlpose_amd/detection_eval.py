@@ -11,7 +11,7 @@ hand-computed cases of ``tests/test_box_ap_cpu.py`` -- and runs it on the device
 
 and the 12 means of ``summarize`` on the host.  Scores are float32, as a detector returns them; the ground truth and the boxes
 are float64.  Caps: ``capi.BOX_MAX`` detections per image, ``capi.BOX_AP_GT_MAX`` ground truths per (image, category).
-Keypoint AP stays ``evaluate.oks_ap``.
+Keypoint AP is ``keypoint_eval.keypoint_ap`` (on the device, through the same accumulate kernel) or ``evaluate.oks_ap`` (host).
 """
 from __future__ import annotations
 

@@ -4,7 +4,8 @@
   * flip-test forward + quarter-pixel / affine decode on the device (``forward_pass(flip=True)``,
     ``get_final_preds_hrnet``);
   * box re-scoring and OKS-NMS of ``lib/metrics.py:188-262`` (``generate_submission_hrnet``) and
-    ``lib/nms.py:10-74`` -- host numpy, a few hundred persons per batch;
+    ``lib/nms.py:10-74`` -- host numpy here; ``Evaluator(scoring="device")`` runs them and the AP below on the device
+    (``keypoint_eval.py``);
   * keypoint AP/AR.  The reference delegates to ``pycocotools.cocoeval.COCOeval(..., "keypoints")``
     (``lib/metrics.py:154-187``), a third-party dependency (pycocotools 2.0.0, ``environment.yml:366``)
     that is neither vendored in the reference tree nor installed here.  ``oks_ap`` below restates its
@@ -234,11 +235,18 @@ class Evaluator:
     With ``process_group`` (one process per GPU) rank r evaluates batches r, r + world, ... of the loader
     (``shard_loader=True``; pass False when the loader is already sharded by a DistributedSampler and give
     each batch's global index in ``metadata['batch_index']``), the per-person results are all-gathered
-    (``gather_eval_shards``) and every rank scores the full set; only rank 0 writes ``preds_file``."""
+    (``gather_eval_shards``) and every rank scores the full set; only rank 0 writes ``preds_file``.
+
+    ``scoring="host"`` rescores, suppresses and scores with the numpy functions above; ``scoring="device"`` with their
+    counterparts of ``keypoint_eval`` (``rescore_and_nms_device``, ``keypoint_ap``).  The returned dict and ``preds_file``
+    have the same format either way."""
 
     def __init__(self, model, device="cuda", model_name: str = "HRNet", flip: bool = True, process_group=None,
-                 shard_loader: bool = True):
+                 shard_loader: bool = True, scoring: str = "host"):
         from .loss import PersonMSELoss
+        if scoring not in ("host", "device"):
+            raise ValueError(f"Evaluator: scoring {scoring!r} ('host' or 'device')")
+        self.scoring = scoring
         self.model, self.device, self.model_name, self.flip = model, torch.device(device), model_name, flip
         self.loss_function = PersonMSELoss()
         self.pg, self.shard_loader = process_group, shard_loader
@@ -309,14 +317,26 @@ class Evaluator:
         if self.world > 1:
             preds, boxes, image_ids, sums = gather_eval_shards(self.pg, np.asarray(seq, np.int64).reshape(-1, 2), preds, boxes,
                                                                image_ids, sums)
-        results = rescore_and_nms(preds, boxes, image_ids) if len(preds) else []
+        on_device = getattr(self, "scoring", "host") == "device"
+        if on_device:
+            from .keypoint_eval import keypoint_ap, rescore_and_nms_device
+            kept = rescore_and_nms_device(preds, boxes, image_ids, device=getattr(self, "device", None)) if len(preds) else None
+            results = kept.to_list() if kept is not None else []
+        else:
+            results = rescore_and_nms(preds, boxes, image_ids) if len(preds) else []
         if preds_file and self.rank == 0:
             with open(preds_file, "w") as f:
                 json.dump(results, f)
         if gt_annotations is None and labels_file is not None:
             with open(labels_file) as f:
                 gt_annotations = json.load(f)["annotations"]
-        stats = oks_ap(gt_annotations, results, img_ids=sorted(set(image_ids))) if gt_annotations is not None else None
+        if gt_annotations is None:
+            stats = None
+        elif on_device:
+            stats = keypoint_ap(gt_annotations, kept if kept is not None else [], img_ids=sorted(set(image_ids)),
+                                device=getattr(self, "device", None))
+        else:
+            stats = oks_ap(gt_annotations, results, img_ids=sorted(set(image_ids)))
         nbt = sums[2]
         return dict(loss=sums[0] / nbt if nbt else float("nan"), accuracy=sums[1] / nbt if nbt else 0.0,
                     results=results, stats=stats)

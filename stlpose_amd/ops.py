@@ -637,6 +637,126 @@ _define("box_ap_accumulate(Tensor matched, Tensor ignored, Tensor rank, Tensor o
         lambda m, i, r, o, c, p, t, md, rt: (m.new_empty(t, len(rt), p.shape[0], p.shape[1], len(md), dtype=torch.float64),
                                              m.new_empty(t, p.shape[0], p.shape[1], len(md), dtype=torch.float64)))
 
+# ------------------------------------------------------------------ pose scoring (csrc/keypoint_eval.hip; rescoring + OKS-NMS, COCOeval "keypoints")
+# Every shape, dtype, device and cap the kernels rely on is checked here, before anything is launched.
+def _pose_var(op: str, sigmas):
+    """(2 sigma)^2 as the host code forms it, for exactly 17 joints."""
+    import numpy as np
+    if len(sigmas) != capi.POSE_JOINTS:
+        raise ValueError(f"stlpose {op}: {len(sigmas)} sigmas; the device path is built for {capi.POSE_JOINTS} joints (use evaluate.oks_ap "
+                         "on the host for another count)")
+    return _doubles((np.asarray([float(v) for v in sigmas], np.float64) * 2) ** 2)
+
+
+def _pose_rescore_nms(preds, boxes, offsets, in_vis_thr: float, oks_thr: float, sigmas, serial_sum: bool = False):
+    op = "pose_rescore_nms"
+    j = capi.POSE_JOINTS
+    if preds.dim() != 3 or tuple(preds.shape[1:]) != (j, 3) or preds.dtype not in (torch.float32, torch.float64):
+        raise ValueError(f"stlpose {op}: preds must be float32 or float64 [P, {j}, 3], got {preds.dtype} {tuple(preds.shape)}")
+    n = preds.shape[0]
+    if boxes.dim() != 2 or tuple(boxes.shape) != (n, 6) or boxes.dtype != torch.float64:
+        raise ValueError(f"stlpose {op}: boxes must be float64 [P={n}, 6] (centre, scale, area, score), got {boxes.dtype} {tuple(boxes.shape)}")
+    var = _pose_var(op, sigmas)
+    off, per = _ragged(op, "offsets", offsets, n)
+    ni = per.numel()
+    max_n = int(per.max()) if ni else 0
+    if max_n > capi.POSE_NMS_MAX:
+        raise BoxApCapError(f"stlpose {op}: the image at table position {int(per.argmax())} has {max_n} persons; the cap is "
+                            f"{capi.POSE_NMS_MAX} (STL_POSE_NMS_MAX) per image", int(per.argmax()))
+    if not preds.is_cuda:
+        raise RuntimeError(f"stlpose {op}: preds must be on the GPU")
+    dev = preds.device
+    _same_device((("boxes", boxes),), dev)
+    score = torch.empty(n, dtype=torch.float64, device=dev)
+    keep = torch.empty(n, dtype=torch.int32, device=dev)
+    count = torch.empty(ni, dtype=torch.int32, device=dev)
+    p, b, o = preds.contiguous(), boxes.contiguous(), off.to(dev)
+    capi.call("stl_pose_rescore_nms", p.data_ptr(), int(preds.dtype == torch.float64), int(bool(serial_sum)), b.data_ptr(), o.data_ptr(), ni, n, max_n,
+              float(in_vis_thr), float(oks_thr), var, score.data_ptr(), keep.data_ptr(), count.data_ptr(), _st())
+    return score, keep, count
+
+
+# serial_sum: the mean confidence as one running sum (the reference's loop) instead of numpy's order (the host function's mean())
+# score fp64 [P]; keep int32 [P]: per image segment the image-local rows of the kept persons in NMS order, then -1; count int32 [I]
+_define("pose_rescore_nms(Tensor preds, Tensor boxes, Tensor offsets, float in_vis_thr, float oks_thr, float[] sigmas, "
+        "bool serial_sum=False) "
+        "-> (Tensor, Tensor, Tensor)", _pose_rescore_nms,
+        lambda p, b, o, iv, ot, sg, ss=False: (p.new_empty(p.shape[0], dtype=torch.float64), p.new_empty(p.shape[0], dtype=torch.int32),
+                                     p.new_empty(o.shape[0] - 1, dtype=torch.int32)))
+
+
+def _oks_ap_match(kpts, scores, area, det_offsets, gt_kpts, gt_area, gt_bbox, gt_crowd, gt_numkp, gt_offsets, oks_thrs, area_ranges, sigmas):
+    op = "oks_ap_match"
+    j = capi.POSE_JOINTS
+    if kpts.dim() != 3 or tuple(kpts.shape[1:]) != (j, 3) or kpts.dtype != torch.float64:
+        raise ValueError(f"stlpose {op}: kpts must be float64 [N, {j}, 3], got {kpts.dtype} {tuple(kpts.shape)}")
+    n = kpts.shape[0]
+    for name, t in (("scores", scores), ("area", area)):
+        if t is not None and (t.dim() != 1 or t.shape[0] != n or t.dtype != torch.float64):
+            raise ValueError(f"stlpose {op}: {name} must be float64 [N={n}], got {t.dtype} {tuple(t.shape)}")
+    if gt_kpts.dim() != 3 or tuple(gt_kpts.shape[1:]) != (j, 3) or gt_kpts.dtype != torch.float64:
+        raise ValueError(f"stlpose {op}: gt_kpts must be float64 [G, {j}, 3], got {gt_kpts.dtype} {tuple(gt_kpts.shape)}")
+    g = gt_kpts.shape[0]
+    if gt_bbox.dim() != 2 or tuple(gt_bbox.shape) != (g, 4) or gt_bbox.dtype != torch.float64:
+        raise ValueError(f"stlpose {op}: gt_bbox must be float64 [G={g}, 4] (x, y, w, h), got {gt_bbox.dtype} {tuple(gt_bbox.shape)}")
+    for name, t, dt in (("gt_area", gt_area, torch.float64), ("gt_crowd", gt_crowd, torch.uint8), ("gt_numkp", gt_numkp, torch.int32)):
+        if t.dim() != 1 or t.shape[0] != g or t.dtype != dt:
+            raise ValueError(f"stlpose {op}: {name} must be {dt} [G={g}], got {t.dtype} {tuple(t.shape)}")
+    var = _pose_var(op, sigmas)
+    doff, dper = _ragged(op, "det_offsets", det_offsets, n)
+    goff, gper = _ragged(op, "gt_offsets", gt_offsets, g)
+    ni = dper.numel()
+    if gper.numel() != ni:
+        raise ValueError(f"stlpose {op}: det_offsets cover {ni} images, gt_offsets {gper.numel()}")
+    if len(oks_thrs) != capi.OKS_AP_THRS or len(area_ranges) != 2 * capi.OKS_AP_AREAS:
+        raise ValueError(f"stlpose {op}: {capi.OKS_AP_THRS} OKS thresholds and {capi.OKS_AP_AREAS} (lo, hi) area ranges, got "
+                         f"{len(oks_thrs)} and {len(area_ranges)} numbers")
+    max_n = int(dper.max()) if ni else 0
+    if max_n > capi.BOX_MAX:
+        raise BoxApCapError(f"stlpose {op}: the image at table position {int(dper.argmax())} has {max_n} detections; the cap is "
+                            f"{capi.BOX_MAX} (STL_BOX_MAX) per image", int(dper.argmax()))
+    max_g = int(gper.max()) if ni else 0
+    if max_g > capi.BOX_AP_GT_MAX:
+        raise BoxApCapError(f"stlpose {op}: the image at table position {int(gper.argmax())} has {max_g} ground truths; the cap is "
+                            f"{capi.BOX_AP_GT_MAX} (STL_BOX_AP_GT_MAX) per image", int(gper.argmax()))
+    if bool(torch.isnan(scores).any()):
+        raise ValueError(f"stlpose {op}: a score is NaN")
+    if not kpts.is_cuda:
+        raise RuntimeError(f"stlpose {op}: kpts must be on the GPU")
+    dev = kpts.device
+    _same_device((("scores", scores), ("gt_kpts", gt_kpts), ("gt_area", gt_area), ("gt_bbox", gt_bbox), ("gt_crowd", gt_crowd),
+                  ("gt_numkp", gt_numkp)) + ((("area", area),) if area is not None else ()), dev)
+    slot_score = torch.zeros(n, dtype=torch.float64, device=dev)
+    slot_cat = torch.full((n,), -1, dtype=torch.int32, device=dev)   # rows beyond the first STL_OKS_AP_DETS stay out of the category
+    slot_rank = torch.zeros(n, dtype=torch.int32, device=dev)
+    matched = torch.zeros(n, dtype=torch.int64, device=dev)
+    ignored = torch.zeros(n, dtype=torch.int64, device=dev)
+    npig = torch.empty(ni, 1, capi.OKS_AP_AREAS, dtype=torch.int32, device=dev)
+    k, s, ar = kpts.contiguous(), scores.contiguous(), (area.contiguous() if area is not None else None)
+    gk, ga, gb, gc, gn = gt_kpts.contiguous(), gt_area.contiguous(), gt_bbox.contiguous(), gt_crowd.contiguous(), gt_numkp.contiguous()
+    do, go = doff.to(dev), goff.to(dev)
+    capi.call("stl_oks_ap_match", k.data_ptr(), s.data_ptr(), ar.data_ptr() if ar is not None else None, do.data_ptr(), n, max_n,
+              gk.data_ptr(), ga.data_ptr(), gb.data_ptr(), gc.data_ptr(), gn.data_ptr(), go.data_ptr(), g, max_g, ni, _doubles(oks_thrs),
+              _doubles(area_ranges), var, slot_score.data_ptr(), slot_cat.data_ptr(), slot_rank.data_ptr(), matched.data_ptr(),
+              ignored.data_ptr(), npig.data_ptr(), _st())
+    return slot_score, slot_cat, slot_rank, matched, ignored, npig
+
+
+def _oks_ap_match_fake(kpts, scores, area, det_offsets, gt_kpts, gt_area, gt_bbox, gt_crowd, gt_numkp, gt_offsets, oks_thrs, area_ranges,
+                       sigmas):
+    n = kpts.shape[0]
+    return (kpts.new_empty(n, dtype=torch.float64), kpts.new_empty(n, dtype=torch.int32), kpts.new_empty(n, dtype=torch.int32),
+            kpts.new_empty(n, dtype=torch.int64), kpts.new_empty(n, dtype=torch.int64),
+            kpts.new_empty(det_offsets.shape[0] - 1, 1, capi.OKS_AP_AREAS, dtype=torch.int32))
+
+
+# the slots of box_ap_match for one category (0) and three area ranges (bit t * 3 + a), slot_score fp64; the layout is stated at
+# stl_oks_ap_match in include/stlpose_hip.h.  area None: the area of the keypoints' bounding box
+_define("oks_ap_match(Tensor kpts, Tensor scores, Tensor? area, Tensor det_offsets, Tensor gt_kpts, Tensor gt_area, Tensor gt_bbox, "
+        "Tensor gt_crowd, Tensor gt_numkp, Tensor gt_offsets, float[] oks_thrs, float[] area_ranges, float[] sigmas) "
+        "-> (Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)", _oks_ap_match, _oks_ap_match_fake)
+
 OPS = ["person_mse", "heatmap_argmax", "final_preds", "flip_merge", "flip_merge_backward", "gaussian_targets", "affine_crop",
        "hrnet_forward", "hrnet_backward", "hrnet_backward_input", "pose_vectors", "pose_distances", "pose_topk", "pose_rank", "pose_rank_any",
-       "box_select", "heatmap_resize_argmax", "det_decode", "det_nms", "det_loss", "box_ap_match", "box_ap_accumulate"]
+       "box_select", "heatmap_resize_argmax", "det_decode", "det_nms", "det_loss", "box_ap_match", "box_ap_accumulate",
+       "pose_rescore_nms", "oks_ap_match"]
