@@ -441,7 +441,7 @@ int stl_box_select(const float* boxes, const float* scores, const int64_t* label
 int stl_heatmap_resize_argmax(const float* hm, int BJ, int H, int W, int Ho, int Wo, int32_t* idx, float* maxval, float* preds,
                               void* stream);
 
-/* ---- COCO box AP (stlpose_amd/csrc/box_ap.hip): the validation metric of src/02_train_faster_rcnn.py:241-280 and
+/* ---- COCO box AP (stlpose_amd/csrc/box_ap.hip, coco_match.inc): the validation metric of src/02_train_faster_rcnn.py:241-280 and
  * src/03_evaluate_faster_rcnn.py:119-184, i.e. the published COCOeval(..., "bbox") in two steps.  Exact: fp64 as written in that
  * file's head, integer sums, order-free maxima; tests/box_ap_ref.py reproduces both outputs bit for bit. */
 #define STL_BOX_AP_THRS 10         /* IoU thresholds of stl_box_ap_match (.50:.05:.95) */
@@ -486,7 +486,7 @@ int stl_box_ap_accumulate(const uint64_t* matched, const uint64_t* ignored, cons
                           const int64_t* cat_offsets, const int64_t* npig, int64_t S, int K, int T, int A, const int32_t* max_dets,
                           int M, const double* rec_thrs, int R, double* precision, double* recall, void* stream);
 
-/* ---- Pose scoring (stlpose_amd/csrc/keypoint_eval.hip): the tail of src/03_evaluate.py, i.e. rescoring + OKS-NMS
+/* ---- Pose scoring (stlpose_amd/csrc/keypoint_eval.hip, coco_match.inc): the tail of src/03_evaluate.py, i.e. rescoring + OKS-NMS
  * (lib/metrics.py:211-262, lib/nms.py) and the published COCOeval(..., "keypoints").evaluateImg; the accumulate step above
  * finishes keypoint AP unchanged (T = 10, A = 3).  17 joints.  Exact up to exp: every operation is fp64 as written in that file's
  * head; the device's fp64 exp and the sum of at most 17 terms may differ from numpy's in the last bits (one OKS by less than

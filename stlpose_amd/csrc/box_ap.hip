@@ -16,21 +16,16 @@
 
 #pragma clang fp contract(off)
 
+#include "coco_match.inc"
+
 namespace {
 
-constexpr int kMatchThreads = 256;
-constexpr int kT = STL_BOX_AP_THRS, kA = STL_BOX_AP_AREAS, kChains = kT * kA;   // 40 chains: one lane each, bit t * kA + a
+constexpr int kT = STL_BOX_AP_THRS, kA = STL_BOX_AP_AREAS;   // 40 chains
 constexpr int kDets = STL_BOX_AP_DETS;
-static_assert(kChains <= 64, "one wave runs the chains and one 64-bit word per slot holds their bits");
-static_assert(STL_BOX_AP_GT_MAX <= 128, "a chain keeps its matched flags in two 64-bit registers");
 
-// Ascending order of this key = descending score, -0 == +0 (NaN is refused by the wrapper).  With the image-local row in the low
-// 32 bits the keys are unique: any sort on them is the stable order of argsort(-score, kind="mergesort").
-__device__ __forceinline__ uint64_t score_key(float s, uint32_t row) {
-    uint32_t b = s == 0.f ? 0u : __float_as_uint(s);
-    b = (b & 0x80000000u) ? ~b : (b | 0x80000000u);   // ascending with the score
-    return ((uint64_t)~b << 32) | row;
-}
+// Ascending order of this key = descending score (NaN is refused by the wrapper).  With the image-local row in the low 32 bits the
+// keys are unique: any sort on them is the stable order of argsort(-score, kind="mergesort").
+__device__ __forceinline__ uint64_t score_key(float s, uint32_t row) { return ((uint64_t)(uint32_t)~score_bits(s) << 32) | row; }
 
 // maskApi.bbIou for one (detection, ground truth) pair, boxes as (x, y, w, h).
 __device__ __forceinline__ double bb_iou(const double* d, const double* g, bool crowd) {
@@ -47,31 +42,19 @@ __device__ __forceinline__ double bb_iou(const double* d, const double* g, bool 
     return i / u;
 }
 
-struct MatchArgs {
+struct MatchArgs : MatchBase<kT, kA, float> {
     const double* boxes;         // [N, 4] xywh
-    const float* scores;         // [N]
     const int64_t* labels;       // [N]
-    const int64_t* det_offsets;  // [I + 1]
     const double* gt_boxes;      // [G, 4] xywh
     const double* gt_area;       // [G]
     const int64_t* gt_label;     // [G]
     const uint8_t* gt_crowd;     // [G]
-    const int64_t* gt_offsets;   // [I + 1]
     const int64_t* cats;         // [K]
-    int64_t N, G;
-    int K, max_n, key_cap, max_g;
-    double thr[kT], lo[kA], hi[kA];
-    float* slot_score;           // [N]
-    int32_t* slot_cat;           // [N]
-    int32_t* slot_rank;          // [N]
-    uint64_t* slot_matched;      // [N]
-    uint64_t* slot_ignored;      // [N]
-    int32_t* npig;               // [I, K, kA]
 };
 
 // LDS: skey [key_cap] u64 | siou [kDets * max_g] f64 | sgbox [max_g * 4] f64 | sgarea [max_g] f64 | sdbox [kDets * 4] f64
 //      | sgrow [max_g] i32 | sgord [kA * max_g] u8 | sgcrowd [max_g] u8
-__global__ __launch_bounds__(kMatchThreads) void box_ap_match_kernel(const MatchArgs a) {
+__global__ __launch_bounds__(kThreads) void box_ap_match_kernel(const MatchArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int mg = a.max_g;
     uint64_t* skey = reinterpret_cast<uint64_t*>(smem);
@@ -88,7 +71,7 @@ __global__ __launch_bounds__(kMatchThreads) void box_ap_match_kernel(const Match
     int32_t* npig_out = a.npig + ((size_t)img * a.K + k) * kA;
     const int64_t o0 = a.det_offsets[img], o1 = a.det_offsets[img + 1];
     const int64_t g0 = a.gt_offsets[img], g1 = a.gt_offsets[img + 1];
-    if (o0 < 0 || o1 < o0 || o1 > a.N || o1 - o0 > a.max_n || g0 < 0 || g1 < g0 || g1 > a.G) {   // refused: the wrapper checks first
+    if (offsets_refused(a, o0, o1, g0, g1)) {   // the wrapper checks first
         if (tid < kA) npig_out[tid] = -1;
         return;
     }
@@ -99,7 +82,7 @@ __global__ __launch_bounds__(kMatchThreads) void box_ap_match_kernel(const Match
 
     // 1. the image's detections of this category.  The keys are unique, so the order in which they are collected is immaterial.
     //    The category's slots start behind those of every smaller label: the slot ranges of one image never overlap.
-    for (int r = tid; r < n; r += kMatchThreads) {
+    for (int r = tid; r < n; r += kThreads) {
         const int64_t l = a.labels[o0 + r];
         if (l == cat) skey[atomicAdd(&s_m, 1)] = score_key(a.scores[o0 + r], (uint32_t)r);
         else if (l < cat) atomicAdd(&s_before, 1);
@@ -124,94 +107,32 @@ __global__ __launch_bounds__(kMatchThreads) void box_ap_match_kernel(const Match
         return;
     }
 
-    // 3. stable sort by descending score: bitonic over the keys padded to a power of two (padding sorts last)
-    int np = 1;
-    while (np < m) np <<= 1;
-    for (int p = m + tid; p < np; p += kMatchThreads) skey[p] = ~0ull;
-    __syncthreads();
-    for (int kk = 2; kk <= np; kk <<= 1) {
-        for (int j = kk >> 1; j > 0; j >>= 1) {
-            for (int i = tid; i < (np >> 1); i += kMatchThreads) {
-                const int lo = ((i & ~(j - 1)) << 1) | (i & (j - 1)), hi = lo + j;
-                const uint64_t x = skey[lo], y = skey[hi];
-                if ((x > y) == ((lo & kk) == 0)) skey[lo] = y, skey[hi] = x;
-            }
-            __syncthreads();
-        }
-    }
+    // 3. stable sort by descending score
+    bitonic_sort<false>(skey, nullptr, m, tid);
     const int nd = m < kDets ? m : kDets;
 
     // 4. stage the kept detections and the ground truth
-    for (int e = tid; e < nd * 4; e += kMatchThreads) sdbox[e] = a.boxes[(o0 + (int)(uint32_t)skey[e >> 2]) * 4 + (e & 3)];
-    for (int e = tid; e < ng * 4; e += kMatchThreads) sgbox[e] = a.gt_boxes[(g0 + sgrow[e >> 2]) * 4 + (e & 3)];
-    for (int g = tid; g < ng; g += kMatchThreads) {
+    for (int e = tid; e < nd * 4; e += kThreads) sdbox[e] = a.boxes[(o0 + (int)(uint32_t)skey[e >> 2]) * 4 + (e & 3)];
+    for (int e = tid; e < ng * 4; e += kThreads) sgbox[e] = a.gt_boxes[(g0 + sgrow[e >> 2]) * 4 + (e & 3)];
+    for (int g = tid; g < ng; g += kThreads) {
         sgarea[g] = a.gt_area[g0 + sgrow[g]];
         sgcrowd[g] = a.gt_crowd[g0 + sgrow[g]] != 0;
     }
     __syncthreads();
 
-    // 5. per area range: the ground truth with the non-ignored entries first, stable (ignored: crowd, or area outside the range)
-    if (tid < kA) {
-        const double lo = a.lo[tid], hi = a.hi[tid];
-        uint8_t* ord = sgord + tid * mg;
-        int c = 0;
-        for (int g = 0; g < ng; ++g)
-            if (!(sgcrowd[g] || sgarea[g] < lo || sgarea[g] > hi)) ord[c++] = (uint8_t)g;
-        s_npig[tid] = c;
-        for (int g = 0; g < ng; ++g)
-            if (sgcrowd[g] || sgarea[g] < lo || sgarea[g] > hi) ord[c++] = (uint8_t)g;
-        npig_out[tid] = s_npig[tid];
-    }
+    // 5. the ground truth in each area range's order (ignored: a crowd, or outside the range)
+    order_ground_truth(a, sgcrowd, sgarea, ng, sgord, s_npig, npig_out, tid);
     // 6. the IoU tile, fp64
-    for (int e = tid; e < nd * ng; e += kMatchThreads) {
+    for (int e = tid; e < nd * ng; e += kThreads) {
         const int d = e / ng, g = e - d * ng;
         siou[e] = bb_iou(sdbox + d * 4, sgbox + g * 4, sgcrowd[g]);
     }
     __syncthreads();
     if (tid >= 64) return;
 
-    // 7. the greedy match: lane c runs the chain of threshold c / kA and area range c % kA over the detections in score order;
-    //    its matched flags (by position in that range's order) live in two registers
-    const bool chain = lane < kChains;
-    const int t = chain ? lane / kA : 0, ar = chain ? lane % kA : 0;
-    const double thr0 = a.thr[t] < 1 - 1e-10 ? a.thr[t] : 1 - 1e-10;
-    const double lo = a.lo[ar], hi = a.hi[ar];
-    const uint8_t* ord = sgord + ar * mg;
-    const int nreg = s_npig[ar];          // positions >= nreg are the ignored ones
-    const int walk = chain ? ng : 0;
-    uint64_t gtm0 = 0, gtm1 = 0;
-    const int64_t base = o0 + s_before;
-    for (int d = 0; d < nd; ++d) {
-        double best = thr0;
-        int mt = -1;
-        for (int gi = 0; gi < walk; ++gi) {
-            const int g = ord[gi];
-            if ((((gi < 64 ? gtm0 : gtm1) >> (gi & 63)) & 1) && !sgcrowd[g]) continue;   // already matched, and not a crowd
-            if (mt > -1 && mt < nreg && gi >= nreg) break;                                  // matched a regular one: stop at the ignored
-            const double v = siou[d * ng + g];
-            if (v < best) continue;
-            best = v, mt = gi;                                                              // a tie moves to the later ground truth
-        }
-        bool ign;
-        if (mt > -1) {
-            ign = mt >= nreg;
-            if (mt < 64) gtm0 |= 1ull << mt;
-            else gtm1 |= 1ull << (mt - 64);
-        } else {
-            const double da = sdbox[d * 4 + 2] * sdbox[d * 4 + 3];
-            ign = da < lo || da > hi;
-        }
-        const uint64_t mb = __ballot(chain && mt > -1), ib = __ballot(chain && ign);
-        if (lane == 0) {
-            const uint64_t key = skey[d];
-            const int r = (int)(uint32_t)key;
-            a.slot_score[base + d] = a.scores[o0 + r];
-            a.slot_cat[base + d] = k;
-            a.slot_rank[base + d] = d;
-            a.slot_matched[base + d] = mb;
-            a.slot_ignored[base + d] = ib;
-        }
-    }
+    // 7. the greedy match
+    greedy_match(a, siou, sgcrowd, sgord, s_npig, nd, ng, o0, o0 + s_before, k,
+                 [&](int d) { return sdbox[d * 4 + 2] * sdbox[d * 4 + 3]; }, [&](int d) { return (int)(uint32_t)skey[d]; }, lane);
 }
 
 constexpr int kAccThreads = STL_BOX_AP_SCAN_TILE;   // one slot per thread and tile
@@ -340,29 +261,16 @@ extern "C" int stl_box_ap_match(const double* boxes, const float* scores, const 
     MatchArgs a{};
     a.boxes = boxes, a.scores = scores, a.labels = labels, a.det_offsets = det_offsets;
     a.gt_boxes = gt_boxes, a.gt_area = gt_area, a.gt_label = gt_label, a.gt_crowd = gt_crowd, a.gt_offsets = gt_offsets, a.cats = cats;
-    a.N = N, a.G = G, a.K = K, a.max_n = max_n, a.max_g = max_g > 0 ? max_g : 1;
-    a.key_cap = 1;
-    while (a.key_cap < (max_n > 0 ? max_n : 1)) a.key_cap <<= 1;
-    for (int t = 0; t < kT; ++t) a.thr[t] = iou_thrs[t];
-    for (int r = 0; r < kA; ++r) a.lo[r] = area_ranges[2 * r], a.hi[r] = area_ranges[2 * r + 1];
+    a.N = N, a.G = G;
     a.slot_score = slot_score, a.slot_cat = slot_cat, a.slot_rank = slot_rank, a.slot_matched = slot_matched;
     a.slot_ignored = slot_ignored, a.npig = npig;
-    const size_t mg = (size_t)a.max_g;
     // 32 KiB of keys and 100 KiB of IoU at the two caps (141 KiB with the staged boxes, of the 160 KiB a workgroup can have); 1 KiB and 13 KiB at 100 detections and 16
     // ground truths per image
-    const size_t lds = (size_t)a.key_cap * 8 + (size_t)kDets * mg * 8 + mg * 4 * 8 + mg * 8 + (size_t)kDets * 4 * 8 + mg * 4 + kA * mg + mg;
-    const hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(&box_ap_match_kernel),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    STL_CHECK(ea == hipSuccess, "box_ap_match: %zu bytes of dynamic LDS refused (max_n = %d, max_g = %d): %s", lds, max_n, max_g,
-              hipGetErrorString(ea));
-    for (int i0 = 0; i0 < num_images; i0 += 1 << 20) {   // grid.x is the image: any number of them
-        MatchArgs b = a;
-        const int ni = num_images - i0 < (1 << 20) ? num_images - i0 : (1 << 20);
-        b.det_offsets += i0, b.gt_offsets += i0, b.npig += (size_t)i0 * K * kA;
-        STL_LAUNCH(box_ap_match_kernel, dim3(ni, K), dim3(kMatchThreads), lds, ST, b);
-        STL_LAUNCH_CHECK("box_ap_match");
-    }
-    return 0;
+    const auto lds_of = [](const MatchArgs& m) {
+        const size_t mg = (size_t)m.max_g;
+        return (size_t)m.key_cap * 8 + (size_t)kDets * mg * 8 + mg * 4 * 8 + mg * 8 + (size_t)kDets * 4 * 8 + mg * 4 + kA * mg + mg;
+    };
+    return launch_match("box_ap_match", box_ap_match_kernel, a, iou_thrs, area_ranges, max_n, max_g, num_images, K, lds_of, ST);
 }
 
 extern "C" int stl_box_ap_accumulate(const uint64_t* matched, const uint64_t* ignored, const int32_t* rank, const int64_t* order,

@@ -9,7 +9,7 @@
 //   stl_oks_ap_match      COCOeval.evaluateImg for iouType "keypoints": one workgroup per image sorts the image's detections
 //                         (stable, descending fp64 score, the first STL_OKS_AP_DETS kept), computes their OKS with the image's
 //                         ground truth as computeOks does and runs the greedy match for every (threshold, area range).  Its slots
-//                         have the layout of stl_box_ap_match, so stl_box_ap_accumulate (box_ap.hip) finishes the job.
+//                         have the layout of stl_box_ap_match (both end in greedy_match of coco_match.inc), so stl_box_ap_accumulate (box_ap.hip) finishes the job.
 //
 // Exactness.  fp contract is off for this file and every operation is fp64 in the order the host code writes it, so everything
 // except exp is reproducible bit for bit.  The device's fp64 exp, and hence the sum of up to 17 of them, need not equal numpy's to
@@ -20,37 +20,14 @@
 
 #pragma clang fp contract(off)
 
+#include "coco_match.inc"
+
 namespace {
 
 constexpr int kJ = STL_POSE_JOINTS;
-constexpr int kThreads = 256;
-constexpr int kT = STL_OKS_AP_THRS, kA = STL_OKS_AP_AREAS, kChains = kT * kA;   // 30 chains: one lane each, bit t * kA + a
+constexpr int kT = STL_OKS_AP_THRS, kA = STL_OKS_AP_AREAS;   // 30 chains
 constexpr int kDets = STL_OKS_AP_DETS;
-static_assert(kChains <= 64, "one wave runs the chains and one 64-bit word per slot holds their bits");
-static_assert(STL_BOX_AP_GT_MAX <= 128, "a chain keeps its matched flags in two 64-bit registers");
 static_assert(kJ == 17, "the joint count is fixed");
-
-// Ascending with the score, -0 == +0, every NaN above +inf.
-__device__ __forceinline__ uint64_t score_bits(double s) {
-    uint64_t b = s == 0.0 ? 0ull : (s != s ? 0x7ff8000000000000ull : (uint64_t)__double_as_longlong(s));
-    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
-
-// Ascending bitonic sort of the pairs (key, idx), np a power of two; pairs are unique, so this is a total order.
-__device__ __forceinline__ void sort_pairs(uint64_t* skey, uint32_t* sidx, int np, int tid) {
-    for (int kk = 2; kk <= np; kk <<= 1) {
-        for (int j = kk >> 1; j > 0; j >>= 1) {
-            for (int i = tid; i < (np >> 1); i += kThreads) {
-                const int lo = ((i & ~(j - 1)) << 1) | (i & (j - 1)), hi = lo + j;
-                const uint64_t x = skey[lo], y = skey[hi];
-                const uint32_t xi = sidx[lo], yi = sidx[hi];
-                const bool gt = x > y || (x == y && xi > yi);
-                if (gt == ((lo & kk) == 0)) skey[lo] = y, skey[hi] = x, sidx[lo] = yi, sidx[hi] = xi;
-            }
-            __syncthreads();
-        }
-    }
-}
 
 // numpy's add.reduce over the values v[k] with bit k of mask set, in index order (pairwise sum below its block size): n < 8 a running
 // sum from 0; else eight running sums over the first 8 * (n / 8), combined pairwise, then the rest in order.  Static indices only.
@@ -144,20 +121,13 @@ __global__ __launch_bounds__(kThreads) void pose_rescore_nms_kernel(const NmsArg
     const double* boxes = a.boxes + o0 * 6;
 
     // 1. the scores, and the sort keys: descending score, equal scores in descending input position
-    int np = 1;
-    while (np < n) np <<= 1;
-    for (int r = tid; r < np; r += kThreads) {
-        if (r < n) {
-            const double s = mean_confidence<T>(preds + (size_t)r * (kJ * 3), (T)a.in_vis_thr, a.serial_sum != 0) * boxes[r * 6 + 5];
-            a.score[o0 + r] = s;
-            skey[r] = ~score_bits(s), sidx[r] = (uint32_t)(n - 1 - r);
-            sgone[r] = 0;
-        } else {
-            skey[r] = ~0ull, sidx[r] = ~0u;   // padding sorts last
-        }
+    for (int r = tid; r < n; r += kThreads) {
+        const double s = mean_confidence<T>(preds + (size_t)r * (kJ * 3), (T)a.in_vis_thr, a.serial_sum != 0) * boxes[r * 6 + 5];
+        a.score[o0 + r] = s;
+        skey[r] = ~score_bits(s), sidx[r] = (uint32_t)(n - 1 - r);
+        sgone[r] = 0;
     }
-    __syncthreads();
-    sort_pairs(skey, sidx, np, tid);
+    bitonic_sort<true>(skey, sidx, n, tid);
 
     // 2. the greedy suppression: position i is kept unless an earlier kept one took it; then its row over the positions behind it
     for (int i = 0; i < n; ++i) {
@@ -190,26 +160,15 @@ __global__ __launch_bounds__(kThreads) void pose_rescore_nms_kernel(const NmsArg
 }
 
 // ------------------------------------------------------------------------------------------------ keypoint AP match
-struct MatchArgs {
+struct MatchArgs : MatchBase<kT, kA, double> {
     const double* kpts;          // [N, 17, 3]
-    const double* scores;        // [N]
     const double* area;          // [N] or null
-    const int64_t* det_offsets;  // [I + 1]
     const double* gt_kpts;       // [G, 17, 3]
     const double* gt_area;       // [G]
     const double* gt_bbox;       // [G, 4] xywh
     const uint8_t* gt_crowd;     // [G]
     const int32_t* gt_numkp;     // [G]
-    const int64_t* gt_offsets;   // [I + 1]
-    int64_t N, G;
-    int max_n, key_cap, max_g;
-    double thr[kT], lo[kA], hi[kA], var[kJ];
-    double* slot_score;          // [N]
-    int32_t* slot_cat;           // [N]
-    int32_t* slot_rank;          // [N]
-    uint64_t* slot_matched;      // [N]
-    uint64_t* slot_ignored;      // [N]
-    int32_t* npig;               // [I, 1, kA]
+    double var[kJ];
 };
 
 // computeOks for one (detection, ground truth) pair
@@ -256,31 +215,25 @@ __global__ __launch_bounds__(kThreads) void oks_ap_match_kernel(const MatchArgs 
     uint8_t* sgign = sgcrowd + mg;
     __shared__ int s_npig[kA];
 
-    const int img = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
+    const int img = blockIdx.x, tid = threadIdx.x;
     int32_t* npig_out = a.npig + (size_t)img * kA;
     const int64_t o0 = a.det_offsets[img], o1 = a.det_offsets[img + 1];
     const int64_t g0 = a.gt_offsets[img], g1 = a.gt_offsets[img + 1];
-    if (o0 < 0 || o1 < o0 || o1 > a.N || o1 - o0 > a.max_n || g0 < 0 || g1 < g0 || g1 > a.G || g1 - g0 > mg) {   // refused: the wrapper checks first
+    if (offsets_refused(a, o0, o1, g0, g1) || g1 - g0 > mg) {   // the wrapper checks first
         if (tid < kA) npig_out[tid] = -1;
         return;
     }
     const int m = (int)(o1 - o0), ng = (int)(g1 - g0);
 
     // 1. stable sort by descending score: the image-local row breaks ties
-    int np = 1;
-    while (np < m) np <<= 1;
-    for (int r = tid; r < np; r += kThreads) {
-        if (r < m) skey[r] = ~score_bits(a.scores[o0 + r]), sidx[r] = (uint32_t)r;
-        else skey[r] = ~0ull, sidx[r] = ~0u;
-    }
+    for (int r = tid; r < m; r += kThreads) skey[r] = ~score_bits(a.scores[o0 + r]), sidx[r] = (uint32_t)r;
     // 2. the ground truth's flags
     for (int g = tid; g < ng; g += kThreads) {
         sgarea[g] = a.gt_area[g0 + g];
         sgcrowd[g] = a.gt_crowd[g0 + g] != 0;
         sgign[g] = a.gt_crowd[g0 + g] != 0 || a.gt_numkp[g0 + g] == 0;
     }
-    __syncthreads();
-    sort_pairs(skey, sidx, np, tid);
+    bitonic_sort<true>(skey, sidx, m, tid);
     const int nd = m < kDets ? m : kDets;
 
     // 3. the kept detections' areas
@@ -302,18 +255,8 @@ __global__ __launch_bounds__(kThreads) void oks_ap_match_kernel(const MatchArgs 
         }
         sdarea[d] = ar;
     }
-    // 4. per area range: the ground truth with the non-ignored entries first, stable
-    if (tid < kA) {
-        const double lo = a.lo[tid], hi = a.hi[tid];
-        uint8_t* ord = sgord + tid * mg;
-        int c = 0;
-        for (int g = 0; g < ng; ++g)
-            if (!(sgign[g] || sgarea[g] < lo || sgarea[g] > hi)) ord[c++] = (uint8_t)g;
-        s_npig[tid] = c;
-        npig_out[tid] = c;
-        for (int g = 0; g < ng; ++g)
-            if (sgign[g] || sgarea[g] < lo || sgarea[g] > hi) ord[c++] = (uint8_t)g;
-    }
+    // 4. the ground truth in each area range's order (ignored: a crowd, no labelled joint, or outside the range)
+    order_ground_truth(a, sgign, sgarea, ng, sgord, s_npig, npig_out, tid);
     // 5. the OKS tile, fp64
     for (int e = tid; e < nd * ng; e += kThreads) {
         const int d = e / ng, g = e - d * ng;
@@ -322,54 +265,13 @@ __global__ __launch_bounds__(kThreads) void oks_ap_match_kernel(const MatchArgs 
     __syncthreads();
     if (tid >= 64) return;
 
-    // 6. the greedy match (step 7 of box_ap_match_kernel): lane c runs the chain of threshold c / kA and area range c % kA
-    const bool chain = lane < kChains;
-    const int t = chain ? lane / kA : 0, ar = chain ? lane % kA : 0;
-    const double thr0 = a.thr[t] < 1 - 1e-10 ? a.thr[t] : 1 - 1e-10;
-    const double lo = a.lo[ar], hi = a.hi[ar];
-    const uint8_t* ord = sgord + ar * mg;
-    const int nreg = s_npig[ar];          // positions >= nreg are the ignored ones
-    const int walk = chain ? ng : 0;
-    uint64_t gtm0 = 0, gtm1 = 0;
-    for (int d = 0; d < nd; ++d) {
-        double best = thr0;
-        int mt = -1;
-        for (int gi = 0; gi < walk; ++gi) {
-            const int g = ord[gi];
-            if ((((gi < 64 ? gtm0 : gtm1) >> (gi & 63)) & 1) && !sgcrowd[g]) continue;   // already matched, and not a crowd
-            if (mt > -1 && mt < nreg && gi >= nreg) break;                                  // matched a regular one: stop at the ignored
-            const double v = soks[d * ng + g];
-            if (v < best) continue;
-            best = v, mt = gi;                                                              // a tie moves to the later ground truth
-        }
-        bool ign;
-        if (mt > -1) {
-            ign = mt >= nreg;
-            if (mt < 64) gtm0 |= 1ull << mt;
-            else gtm1 |= 1ull << (mt - 64);
-        } else {
-            ign = sdarea[d] < lo || sdarea[d] > hi;
-        }
-        const uint64_t mb = __ballot(chain && mt > -1), ib = __ballot(chain && ign);
-        if (lane == 0) {
-            a.slot_score[o0 + d] = a.scores[o0 + sidx[d]];
-            a.slot_cat[o0 + d] = 0;
-            a.slot_rank[o0 + d] = d;
-            a.slot_matched[o0 + d] = mb;
-            a.slot_ignored[o0 + d] = ib;
-        }
-    }
+    // 6. the greedy match
+    greedy_match(a, soks, sgcrowd, sgord, s_npig, nd, ng, o0, o0, 0, [&](int d) { return sdarea[d]; }, [&](int d) { return sidx[d]; }, tid);
 }
 
 }  // namespace
 
 #define ST ((hipStream_t)stream)
-
-static inline int pow2_at_least(int n) {
-    int p = 1;
-    while (p < n) p <<= 1;
-    return p;
-}
 
 extern "C" int stl_pose_rescore_nms(const void* preds, int preds_f64, int sum_order, const double* boxes, const int64_t* offsets, int num_images,
                                     int64_t P, int max_n, double in_vis_thr, double oks_thr, const double* var, double* score,
@@ -420,25 +322,14 @@ extern "C" int stl_oks_ap_match(const double* kpts, const double* scores, const 
     MatchArgs a{};
     a.kpts = kpts, a.scores = scores, a.area = area, a.det_offsets = det_offsets;
     a.gt_kpts = gt_kpts, a.gt_area = gt_area, a.gt_bbox = gt_bbox, a.gt_crowd = gt_crowd, a.gt_numkp = gt_numkp, a.gt_offsets = gt_offsets;
-    a.N = N, a.G = G, a.max_n = max_n, a.max_g = max_g > 0 ? max_g : 1, a.key_cap = pow2_at_least(max_n > 0 ? max_n : 1);
-    for (int t = 0; t < kT; ++t) a.thr[t] = oks_thrs[t];
-    for (int r = 0; r < kA; ++r) a.lo[r] = area_ranges[2 * r], a.hi[r] = area_ranges[2 * r + 1];
+    a.N = N, a.G = G;
     for (int k = 0; k < kJ; ++k) a.var[k] = var[k];
     a.slot_score = slot_score, a.slot_cat = slot_cat, a.slot_rank = slot_rank, a.slot_matched = slot_matched;
     a.slot_ignored = slot_ignored, a.npig = npig;
-    const size_t mg = (size_t)a.max_g;
     // 48 KiB of keys and 20 KiB of OKS at the two caps (71 KiB in all, of the 160 KiB a workgroup can have)
-    const size_t lds = (size_t)a.key_cap * 12 + (size_t)kDets * mg * 8 + mg * 8 + (size_t)kDets * 8 + kA * mg + 2 * mg;
-    const hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(&oks_ap_match_kernel),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    STL_CHECK(ea == hipSuccess, "oks_ap_match: %zu bytes of dynamic LDS refused (max_n = %d, max_g = %d): %s", lds, max_n, max_g,
-              hipGetErrorString(ea));
-    for (int i0 = 0; i0 < num_images; i0 += 1 << 20) {   // grid.x is the image: any number of them
-        MatchArgs b = a;
-        const int ni = num_images - i0 < (1 << 20) ? num_images - i0 : (1 << 20);
-        b.det_offsets += i0, b.gt_offsets += i0, b.npig += (size_t)i0 * kA;
-        STL_LAUNCH(oks_ap_match_kernel, dim3(ni), dim3(kThreads), lds, ST, b);
-        STL_LAUNCH_CHECK("oks_ap_match");
-    }
-    return 0;
+    const auto lds_of = [](const MatchArgs& m) {
+        const size_t mg = (size_t)m.max_g;
+        return (size_t)m.key_cap * 12 + (size_t)kDets * mg * 8 + mg * 8 + (size_t)kDets * 8 + kA * mg + 2 * mg;
+    };
+    return launch_match("oks_ap_match", oks_ap_match_kernel, a, oks_thrs, area_ranges, max_n, max_g, num_images, 1, lds_of, ST);
 }

@@ -22,15 +22,11 @@ import numpy as np
 import torch
 
 from . import capi
+from .coco_tables import REC_THRS, device_of, match_and_accumulate, mean_valid as mean, offsets_of, segment_rows, take_images
 
 IOU_THRS = np.linspace(.5, 0.95, 10)
-REC_THRS = np.linspace(.0, 1.0, 101)
 AREA_RANGES = ((0.0, 1e10), (0.0, 32.0 ** 2), (32.0 ** 2, 96.0 ** 2), (96.0 ** 2, 1e10))   # all, small, medium, large
 STAT_NAMES = ("AP", "AP50", "AP75", "AP(S)", "AP(M)", "AP(L)", "AR@1", "AR@10", "AR@100", "AR(S)", "AR(M)", "AR(L)")
-
-
-def _device(device) -> torch.device:
-    return torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
 
 
 class GroundTruth:
@@ -40,10 +36,9 @@ class GroundTruth:
         anns = sorted(annotations, key=lambda a: a["image_id"])   # stable: annotation order within an image
         ids = np.asarray([a["image_id"] for a in anns], np.int64)
         self.img_ids, self.counts = np.unique(ids, return_counts=True)
-        self.starts = np.concatenate([[0], np.cumsum(self.counts)]).astype(np.int64)
         self.labels_host = np.asarray([a["category_id"] for a in anns], np.int64)
         self.cat_ids = sorted(set(int(c) for c in cat_ids)) if cat_ids is not None else None
-        self.device = _device(device)
+        self.device = device_of(device)
         box = np.asarray([a["bbox"] for a in anns], np.float64).reshape(-1, 4)
         self.boxes = torch.from_numpy(box).to(self.device)
         self.area = torch.from_numpy(np.asarray([a["area"] for a in anns], np.float64)).to(self.device)
@@ -51,26 +46,11 @@ class GroundTruth:
         self.crowd = torch.from_numpy(np.asarray([bool(a.get("iscrowd", 0)) for a in anns], np.uint8)).to(self.device)
 
     def select(self, img_ids: np.ndarray):
-        """The rows of the given images (ascending ids; an image without annotations has none): tensors and offsets."""
-        img_ids = np.asarray(img_ids, np.int64)
-        pos = np.searchsorted(self.img_ids, img_ids)
-        has = pos < len(self.img_ids)
-        has[has] = self.img_ids[pos[has]] == img_ids[has]
-        cnt, start = np.zeros(len(img_ids), np.int64), np.zeros(len(img_ids), np.int64)
-        cnt[has], start[has] = self.counts[pos[has]], self.starts[pos[has]]
-        offsets = np.concatenate([[0], np.cumsum(cnt)]).astype(np.int64)
-        rows = _segment_rows(start, cnt)
-        r = torch.from_numpy(rows).to(self.device)
-        return self.boxes[r], self.area[r], self.labels[r], self.crowd[r], torch.from_numpy(offsets), self.labels_host[rows]
-
-
-def _segment_rows(start: np.ndarray, cnt: np.ndarray) -> np.ndarray:
-    """concatenate(arange(start[i], start[i] + cnt[i]))"""
-    total = int(cnt.sum())
-    if total == 0:
-        return np.zeros(0, np.int64)
-    first = np.cumsum(cnt) - cnt
-    return np.repeat(start - first, cnt) + np.arange(total, dtype=np.int64)
+        """The rows of the given images (ascending ids; an image without annotations has none): tensors and offsets.  For every
+        image of the table, in order, these are the stored tables themselves, not copies."""
+        (boxes, area, labels, crowd, labels_host), offsets = take_images(
+            (self.boxes, self.area, self.labels, self.crowd, self.labels_host), self.img_ids, self.counts, img_ids, self.device)
+        return boxes, area, labels, crowd, offsets, labels_host
 
 
 class BoxEval:
@@ -88,35 +68,16 @@ def evaluate_tables(boxes, scores, labels, det_offsets, gt: tuple, cat_ids: Sequ
     xywh, scores float32 [N], labels int64 [N], det_offsets int64 [I + 1] (CPU); gt = (boxes, area, labels, crowd, offsets).
     Returns (precision, recall) as device tensors.  img_ids (the tables' image ids, in table order): an exceeded cap is reported
     with the image's id instead of its position alone."""
-    from . import ops  # registers the stlpose:: ops
     gb, ga, gl, gc, goff = gt
     cats = torch.tensor([int(c) for c in cat_ids], dtype=torch.int64)
-    nk = cats.shape[0]
-    try:
-        score, cat, rank, matched, ignored, npig = torch.ops.stlpose.box_ap_match(
-            boxes, scores, labels, det_offsets, gb, ga, gl, gc, goff, cats, [float(t) for t in IOU_THRS],
-            [float(v) for r in AREA_RANGES for v in r])
-    except ops.BoxApCapError as e:
-        if img_ids is None:
-            raise
-        raise ValueError(f"image_id {int(img_ids[e.image_index])}: {e}") from None
-    # one global order: stable by descending score, then stable by category.  The slots lie image by image (ascending ids) and rank
-    # by rank within a category, so equal scores keep that order; slots of no category (-1) sort to the front and are skipped
-    by_score = torch.sort(score, descending=True, stable=True).indices
-    by_cat = torch.sort(cat[by_score], stable=True).indices
-    order = by_score[by_cat]
-    cat_offsets = torch.cumsum(torch.bincount((cat + 1).long(), minlength=nk + 1), 0)   # [K + 1]: where each category's slots begin
-    precision, recall = torch.ops.stlpose.box_ap_accumulate(matched, ignored, rank, order, cat_offsets, npig.sum(0, dtype=torch.int64),
-                                                            len(IOU_THRS), [int(m) for m in max_dets], [float(r) for r in REC_THRS])
-    return precision, recall
+    return match_and_accumulate(lambda: torch.ops.stlpose.box_ap_match(
+        boxes, scores, labels, det_offsets, gb, ga, gl, gc, goff, cats, [float(t) for t in IOU_THRS],
+        [float(v) for r in AREA_RANGES for v in r]), cats.shape[0], len(IOU_THRS), max_dets, img_ids)
 
 
 def summarize(precision: np.ndarray, recall: np.ndarray) -> np.ndarray:
     """COCOeval.summarize for "bbox": the 12 numbers of ``STAT_NAMES``, each the mean of the entries > -1, or -1.  AP and the
     per-area numbers are read at the last maxDets, AR at each of the three."""
-    def mean(x):
-        x = x[x > -1]
-        return float(np.mean(x)) if x.size else -1.0
     t50, t75 = 0, 5
     last = precision.shape[4] - 1
     return np.array([mean(precision[:, :, :, 0, last]), mean(precision[t50, :, :, 0, last]), mean(precision[t75, :, :, 0, last]),
@@ -140,7 +101,7 @@ def box_ap(gt_annotations: Sequence[dict], results: Sequence[dict], img_ids: Opt
     ground truth yields -1 entries, which no mean counts).  Returns the 12 numbers of COCOeval.stats for bbox: AP, AP50, AP75,
     AP(S), AP(M), AP(L), AR@1, AR@10, AR@100, AR(S), AR(M), AR(L)."""
     md = _check_max_dets(max_dets)
-    dev = _device(device)
+    dev = device_of(device)
     if img_ids is None:
         img_ids = {a["image_id"] for a in gt_annotations} | {r["image_id"] for r in results}
     if cat_ids is None:
@@ -156,7 +117,7 @@ def box_ap(gt_annotations: Sequence[dict], results: Sequence[dict], img_ids: Opt
     boxes = torch.from_numpy(np.asarray([r["bbox"] for r in res], np.float64).reshape(-1, 4)).to(dev)
     scores = torch.from_numpy(np.asarray([r["score"] for r in res], np.float32)).to(dev)
     labels = torch.from_numpy(np.asarray([r["category_id"] for r in res], np.int64)).to(dev)
-    offsets = torch.from_numpy(np.concatenate([[0], np.cumsum(cnt)]).astype(np.int64))
+    offsets = torch.from_numpy(offsets_of(cnt))
     precision, recall = evaluate_tables(boxes, scores, labels, offsets, table.select(ids)[:5], cats, md, img_ids=ids)
     return summarize(precision.cpu().numpy(), recall.cpu().numpy())
 
@@ -186,7 +147,7 @@ class CocoEvaluator:
                 raise NotImplementedError(f"CocoEvaluator: iou_type {t!r}; box AP only ('bbox').  Keypoint AP is "
                                           "stlpose_amd.evaluate.oks_ap; 'segm' is not provided")
         self.iou_types = iou_types
-        self.device = _device(device)
+        self.device = device_of(device)
         # a GroundTruth built earlier is taken as it is: a training loop that validates every epoch uploads it once
         self.gt = coco_gt if isinstance(coco_gt, GroundTruth) else GroundTruth(*_annotations_of(coco_gt), device=self.device)
         self.coco_eval: Dict[str, BoxEval] = {"bbox": BoxEval()}
@@ -240,8 +201,8 @@ class CocoEvaluator:
             boxes, scores, labels = (torch.from_numpy(np.concatenate([p[i] for p in parts])).to(self.device) for i in (2, 3, 4))
         uniq, first = np.unique(ids, return_index=True)     # ascending ids, first occurrence of each
         start = (np.cumsum(cnt) - cnt)[first]
-        rows = torch.from_numpy(_segment_rows(start, cnt[first])).to(self.device)
-        offsets = torch.from_numpy(np.concatenate([[0], np.cumsum(cnt[first])]).astype(np.int64))
+        rows = torch.from_numpy(segment_rows(start, cnt[first])).to(self.device)
+        offsets = torch.from_numpy(offsets_of(cnt[first]))
         self._tables = (uniq, boxes[rows], scores[rows], labels[rows], offsets)
         self.img_ids = [int(i) for i in uniq]
 
@@ -289,7 +250,7 @@ class DetectorEvaluator:
     batches of the others; a plain iterable can only be skipped through, which loads them all."""
 
     def __init__(self, model, process_group=None, device=None):
-        self.model, self.pg, self.device = model, process_group, _device(device)
+        self.model, self.pg, self.device = model, process_group, device_of(device)
         self.rank, self.world = 0, 1
         if process_group is not None:
             import torch.distributed as dist

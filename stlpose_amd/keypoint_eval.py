@@ -27,7 +27,7 @@ import numpy as np
 import torch
 
 from . import capi
-from .detection_eval import REC_THRS, _device, _segment_rows
+from .coco_tables import REC_THRS, device_of, image_rows, match_and_accumulate, mean_valid as _mean, offsets_of, take_images  # noqa: F401
 from .evaluate import COCO_SIGMAS
 
 OKS_THRS = np.linspace(.5, 0.95, 10)
@@ -41,10 +41,6 @@ def _sigmas(sigmas) -> List[float]:
         raise ValueError(f"keypoint scoring on the device is built for {capi.POSE_JOINTS} joints, got {len(s)} sigmas; "
                          "evaluate.oks_ap on the host takes any count")
     return [float(v) for v in s]
-
-
-def _offsets(cnt: np.ndarray) -> np.ndarray:
-    return np.concatenate([[0], np.cumsum(cnt)]).astype(np.int64)
 
 
 class PoseResults:
@@ -73,7 +69,7 @@ class PoseResults:
     @classmethod
     def from_list(cls, results: Sequence[dict], device=None) -> "PoseResults":
         """A result list whose images lie in one run each (what ``to_list`` gives) as tables."""
-        dev = _device(device)
+        dev = device_of(device)
         ids = np.asarray([r["image_id"] for r in results], np.int64)
         start = np.flatnonzero(np.concatenate([[True], ids[1:] != ids[:-1]])) if len(ids) else np.zeros(0, np.int64)
         if len(np.unique(ids[start])) != len(start):
@@ -94,7 +90,7 @@ def rescore_and_nms_device(all_preds, all_boxes, image_ids: Sequence, in_vis_thr
     if mean_order not in capi.POSE_SUM_ORDER:
         raise ValueError(f"rescore_and_nms_device: mean_order {mean_order!r} ('numpy' or 'reference')")
     from . import ops  # noqa: F401  (registers the stlpose:: ops)
-    dev = _device(device)
+    dev = device_of(device)
     preds = torch.as_tensor(all_preds)
     if preds.dtype not in (torch.float32, torch.float64):
         raise ValueError(f"rescore_and_nms_device: all_preds must be float32 or float64, got {preds.dtype}")
@@ -111,7 +107,7 @@ def rescore_and_nms_device(all_preds, all_boxes, image_ids: Sequence, in_vis_thr
     rank_of[by_first] = np.arange(len(uniq))
     perm = np.argsort(rank_of[inv.reshape(-1)], kind="stable")
     img_ids, cnt = uniq[by_first], cnt[by_first]
-    offsets = _offsets(cnt)
+    offsets = offsets_of(cnt)
     if len(cnt) and int(cnt.max()) > capi.POSE_NMS_MAX:
         w = int(cnt.argmax())
         raise ValueError(f"image_id {int(img_ids[w])}: {int(cnt[w])} persons; the cap of the device NMS is {capi.POSE_NMS_MAX} "
@@ -125,7 +121,7 @@ def rescore_and_nms_device(all_preds, all_boxes, image_ids: Sequence, in_vis_thr
                                                             _sigmas(None), mean_order == "reference")
     kept = count.cpu().numpy().astype(np.int64)
     rows = (keep.long() + torch.from_numpy(np.repeat(offsets[:-1], cnt)).to(dev))[keep >= 0]
-    return PoseResults(preds[rows].to(torch.float64), score[rows], img_ids, _offsets(kept))
+    return PoseResults(preds[rows].to(torch.float64), score[rows], img_ids, offsets_of(kept))
 
 
 class KeypointGroundTruth:
@@ -135,8 +131,7 @@ class KeypointGroundTruth:
         anns = sorted(annotations, key=lambda a: a["image_id"])   # stable: annotation order within an image
         ids = np.asarray([a["image_id"] for a in anns], np.int64)
         self.img_ids, self.counts = np.unique(ids, return_counts=True)
-        self.starts = _offsets(self.counts)
-        self.device = dev = _device(device)
+        self.device = dev = device_of(device)
         j = capi.POSE_JOINTS
         for a in anns:
             if len(a["keypoints"]) != 3 * j:
@@ -149,17 +144,11 @@ class KeypointGroundTruth:
         self.numkp = torch.from_numpy(np.asarray([int(a.get("num_keypoints", 1)) for a in anns], np.int32)).to(dev)
 
     def select(self, img_ids: np.ndarray):
-        """The rows of the given images (ascending ids; an image without annotations has none): tensors and offsets."""
-        img_ids = np.asarray(img_ids, np.int64)
-        pos = np.searchsorted(self.img_ids, img_ids)
-        has = pos < len(self.img_ids)
-        has[has] = self.img_ids[pos[has]] == img_ids[has]
-        cnt, start = np.zeros(len(img_ids), np.int64), np.zeros(len(img_ids), np.int64)
-        cnt[has], start[has] = self.counts[pos[has]], self.starts[pos[has]]
-        if len(cnt) == len(self.img_ids) and bool(has.all()):   # every image, in order: the tables as they are
-            return self.kpts, self.area, self.bbox, self.crowd, self.numkp, torch.from_numpy(_offsets(cnt))
-        r = torch.from_numpy(_segment_rows(start, cnt)).to(self.device)
-        return self.kpts[r], self.area[r], self.bbox[r], self.crowd[r], self.numkp[r], torch.from_numpy(_offsets(cnt))
+        """The rows of the given images (ascending ids; an image without annotations has none): tensors and offsets.  For every
+        image of the table, in order, these are the stored tables themselves, not copies."""
+        tables, offsets = take_images((self.kpts, self.area, self.bbox, self.crowd, self.numkp), self.img_ids, self.counts, img_ids,
+                                      self.device)
+        return (*tables, offsets)
 
 
 class KeypointEval:
@@ -173,9 +162,6 @@ class KeypointEval:
 
 def summarize(precision: np.ndarray, recall: np.ndarray) -> np.ndarray:
     """The 10 numbers of ``STAT_NAMES`` with the slicing and the mean of ``oks_ap``."""
-    def _mean(x):
-        x = x[x > -1]
-        return float(x.mean()) if x.size else -1.0
     t50, t75 = 0, 5
     return np.array([_mean(precision[:, :, 0]), _mean(precision[t50, :, 0]), _mean(precision[t75, :, 0]),
                      _mean(precision[:, :, 1]), _mean(precision[:, :, 2]),
@@ -187,24 +173,10 @@ def evaluate_tables(kpts, scores, area, det_offsets, gt: tuple, sigmas: Sequence
     """match + order + accumulate on the device for ragged tables whose images are in ascending id order.  kpts float64 [N, 17, 3],
     scores float64 [N], area float64 [N] or None, det_offsets int64 [I + 1] (CPU); gt = (kpts, area, bbox, crowd, numkp, offsets).
     Returns (precision [T, R, A], recall [T, A]) as device tensors.  img_ids: an exceeded cap is reported with the image's id."""
-    from . import ops  # registers the stlpose:: ops
     gk, ga, gb, gc, gn, goff = gt
-    try:
-        score, cat, rank, matched, ignored, npig = torch.ops.stlpose.oks_ap_match(
-            kpts, scores, area, det_offsets, gk, ga, gb, gc, gn, goff, [float(t) for t in OKS_THRS],
-            [float(v) for r in AREA_RANGES for v in r], [float(s) for s in sigmas])
-    except ops.BoxApCapError as e:
-        if img_ids is None:
-            raise
-        raise ValueError(f"image_id {int(img_ids[e.image_index])}: {e}") from None
-    # one global order: stable by descending score over the slots, which lie image by image (ascending ids) and rank by rank; the
-    # rows beyond the first STL_OKS_AP_DETS of an image (category -1) go to the front and are skipped
-    by_score = torch.sort(score, descending=True, stable=True).indices
-    by_cat = torch.sort(cat[by_score], stable=True).indices
-    order = by_score[by_cat]
-    cat_offsets = torch.cumsum(torch.bincount((cat + 1).long(), minlength=2), 0)
-    precision, recall = torch.ops.stlpose.box_ap_accumulate(matched, ignored, rank, order, cat_offsets, npig.sum(0, dtype=torch.int64),
-                                                            len(OKS_THRS), [int(max_dets)], [float(r) for r in REC_THRS])
+    precision, recall = match_and_accumulate(lambda: torch.ops.stlpose.oks_ap_match(
+        kpts, scores, area, det_offsets, gk, ga, gb, gc, gn, goff, [float(t) for t in OKS_THRS],
+        [float(v) for r in AREA_RANGES for v in r], [float(s) for s in sigmas]), 1, len(OKS_THRS), [int(max_dets)], img_ids)
     return precision[:, :, 0, :, 0], recall[:, 0, :, 0]
 
 
@@ -215,7 +187,7 @@ def keypoint_ap_tables(gt_annotations: Union[Sequence[dict], KeypointGroundTruth
     if not 1 <= int(max_dets) <= capi.OKS_AP_DETS:
         raise ValueError(f"keypoint AP: max_dets must be in 1 .. {capi.OKS_AP_DETS} (STL_OKS_AP_DETS), got {max_dets}")
     table = gt_annotations if isinstance(gt_annotations, KeypointGroundTruth) else None
-    dev = table.device if table is not None and device is None else _device(device)
+    dev = table.device if table is not None and device is None else device_of(device)
     j = capi.POSE_JOINTS
     if isinstance(results, PoseResults):
         by_id = np.argsort(results.image_ids, kind="stable")
@@ -226,18 +198,13 @@ def keypoint_ap_tables(gt_annotations: Union[Sequence[dict], KeypointGroundTruth
         results = sorted(results, key=lambda r: r["image_id"])    # stable: result order within an image
         rid = np.asarray([r["image_id"] for r in results], np.int64)
         rid_img, rcnt = np.unique(rid, return_counts=True)
-        rstart = _offsets(rcnt)[:-1]
+        rstart = offsets_of(rcnt)[:-1]
     gt_ids = table.img_ids if table is not None else np.asarray(sorted({int(a["image_id"]) for a in gt_annotations}), np.int64)
     ids = np.union1d(gt_ids, rid_img) if img_ids is None else np.asarray(sorted(set(int(i) for i in img_ids)), np.int64)
     if table is None:
         table = KeypointGroundTruth(gt_annotations, device=dev)
     # the results of the scored images, images ascending by id
-    pos = np.searchsorted(rid_img, ids)
-    has = pos < len(rid_img)
-    has[has] = rid_img[pos[has]] == ids[has]
-    cnt, start = np.zeros(len(ids), np.int64), np.zeros(len(ids), np.int64)
-    cnt[has], start[has] = rcnt[pos[has]], rstart[pos[has]]
-    rows = _segment_rows(start, cnt)
+    rows, offsets = image_rows(rid_img, rcnt, rstart, ids)
     if isinstance(results, PoseResults):
         r = torch.from_numpy(rows).to(results.keypoints.device)
         kpts, scores, area = results.keypoints[r].to(dev), results.scores[r].to(dev), None
@@ -258,7 +225,7 @@ def keypoint_ap_tables(gt_annotations: Union[Sequence[dict], KeypointGroundTruth
                 derived = (x.max(1).values - x.min(1).values) * (y.max(1).values - y.min(1).values)
                 a = torch.where(torch.from_numpy(given).to(dev), a, derived)
             area = a
-    precision, recall = evaluate_tables(kpts, scores, area, torch.from_numpy(_offsets(cnt)), table.select(ids), sg, int(max_dets),
+    precision, recall = evaluate_tables(kpts, scores, area, torch.from_numpy(offsets), table.select(ids), sg, int(max_dets),
                                         img_ids=ids)
     return KeypointEval(np.ascontiguousarray(precision.cpu().numpy()), np.ascontiguousarray(recall.cpu().numpy()))
 

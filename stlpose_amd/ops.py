@@ -482,7 +482,7 @@ _define("det_loss(Tensor regression, Tensor classification, Tensor anchors, Tens
         lambda r, c, a, g, o, al, ga, bw: (r.new_empty(2), r.new_empty(r.shape), c.new_empty(c.shape),
                                            r.new_empty(r.shape[0], dtype=torch.int32)))
 
-# ------------------------------------------------------------------ COCO box AP (csrc/box_ap.hip; COCOeval "bbox")
+# ------------------------------------------------------------------ COCO box AP (csrc/box_ap.hip, csrc/coco_match.inc; COCOeval "bbox")
 # Every shape, dtype, device and cap the kernels rely on is checked here, before anything is launched.
 class BoxApCapError(ValueError):
     """A cap of box_ap_match is exceeded.  ``image_index`` is the image's position in the ragged tables: the op knows no image ids
@@ -508,40 +508,65 @@ def _doubles(v):
     return (capi.C.c_double * len(v))(*[float(x) for x in v])
 
 
-def _box_ap_match(boxes, scores, labels, det_offsets, gt_boxes, gt_area, gt_label, gt_crowd, gt_offsets, categories, iou_thrs, area_ranges):
-    op = "box_ap_match"
-    if boxes.dim() != 2 or boxes.shape[1] != 4 or boxes.dtype != torch.float64:
-        raise ValueError(f"stlpose {op}: boxes must be float64 [N, 4] (x, y, w, h), got {boxes.dtype} {tuple(boxes.shape)}")
-    n = boxes.shape[0]
-    if scores.dim() != 1 or scores.shape[0] != n or scores.dtype != torch.float32:
-        raise ValueError(f"stlpose {op}: scores must be float32 [N={n}], got {scores.dtype} {tuple(scores.shape)}")
-    if labels.dim() != 1 or labels.shape[0] != n or labels.dtype != torch.int64:
-        raise ValueError(f"stlpose {op}: labels must be int64 [N={n}], got {labels.dtype} {tuple(labels.shape)}")
-    if gt_boxes.dim() != 2 or gt_boxes.shape[1] != 4 or gt_boxes.dtype != torch.float64:
-        raise ValueError(f"stlpose {op}: gt_boxes must be float64 [G, 4] (x, y, w, h), got {gt_boxes.dtype} {tuple(gt_boxes.shape)}")
-    g = gt_boxes.shape[0]
-    for name, t, dt in (("gt_area", gt_area, torch.float64), ("gt_label", gt_label, torch.int64), ("gt_crowd", gt_crowd, torch.uint8)):
-        if t.dim() != 1 or t.shape[0] != g or t.dtype != dt:
-            raise ValueError(f"stlpose {op}: {name} must be {dt} [G={g}], got {t.dtype} {tuple(t.shape)}")
-    if categories.dim() != 1 or categories.dtype != torch.int64:
-        raise ValueError(f"stlpose {op}: categories must be int64 [K], got {categories.dtype} {tuple(categories.shape)}")
-    cats = categories.cpu()
-    nk = cats.shape[0]
-    if nk > 65535 or bool((cats[1:] <= cats[:-1]).any()):
-        raise ValueError(f"stlpose {op}: categories must be strictly ascending, at most 65535 of them")
+def _table(op: str, name: str, t, dtype, rows: str, n=None, tail=(), note: str = "") -> int:
+    """t must be `dtype` [rows, *tail] with n rows (None: any number); its row count."""
+    if t.dim() != 1 + len(tail) or tuple(t.shape[1:]) != tuple(tail) or (n is not None and t.shape[0] != n) or t.dtype != dtype:
+        dims = ", ".join([rows if n is None else f"{rows}={n}"] + [str(d) for d in tail])
+        raise ValueError(f"stlpose {op}: {name} must be {str(dtype).removeprefix('torch.')} [{dims}]{note}, got {t.dtype} {tuple(t.shape)}")
+    return t.shape[0]
+
+
+def _match_images(op: str, n: int, g: int, det_offsets, gt_offsets, thrs, area_ranges, metric: str, num_thrs: int, num_areas: int):
+    """The checks box_ap_match and oks_ap_match share once their tables have the right shapes: both offsets over the same images,
+    the threshold and area-range counts, the detection cap.  Returns (det_offsets, gt_offsets) on the CPU, the ground truths per
+    image and the largest detection count."""
     doff, dper = _ragged(op, "det_offsets", det_offsets, n)
     goff, gper = _ragged(op, "gt_offsets", gt_offsets, g)
     ni = dper.numel()
     if gper.numel() != ni:
         raise ValueError(f"stlpose {op}: det_offsets cover {ni} images, gt_offsets {gper.numel()}")
-    if len(iou_thrs) != capi.BOX_AP_THRS or len(area_ranges) != 2 * capi.BOX_AP_AREAS:
-        raise ValueError(f"stlpose {op}: {capi.BOX_AP_THRS} IoU thresholds and {capi.BOX_AP_AREAS} (lo, hi) area ranges, got "
-                         f"{len(iou_thrs)} and {len(area_ranges)} numbers")
+    if len(thrs) != num_thrs or len(area_ranges) != 2 * num_areas:
+        raise ValueError(f"stlpose {op}: {num_thrs} {metric} thresholds and {num_areas} (lo, hi) area ranges, got "
+                         f"{len(thrs)} and {len(area_ranges)} numbers")
     max_n = int(dper.max()) if ni else 0
     if max_n > capi.BOX_MAX:
         raise BoxApCapError(f"stlpose {op}: the image at table position {int(dper.argmax())} has {max_n} detections; the cap is "
                             f"{capi.BOX_MAX} (STL_BOX_MAX) per image", int(dper.argmax()))
-    max_g = 0
+    return doff, goff, gper, max_n
+
+
+def _match_slots(op: str, name: str, det, scores, others, ni: int, nk: int, num_areas: int):
+    """The last checks (no NaN score, everything on the GPU of `det`, the table called `name`) and the six outputs of a match op."""
+    if bool(torch.isnan(scores).any()):
+        raise ValueError(f"stlpose {op}: a score is NaN")
+    if not det.is_cuda:
+        raise RuntimeError(f"stlpose {op}: {name} must be on the GPU")
+    dev, n = det.device, det.shape[0]
+    _same_device((("scores", scores),) + tuple(others), dev)
+    return (torch.zeros(n, dtype=scores.dtype, device=dev),            # slot_score
+            torch.full((n,), -1, dtype=torch.int32, device=dev),       # slot_cat: rows no workgroup claims stay out of every category
+            torch.zeros(n, dtype=torch.int32, device=dev),             # slot_rank
+            torch.zeros(n, dtype=torch.int64, device=dev),             # matched
+            torch.zeros(n, dtype=torch.int64, device=dev),             # ignored
+            torch.empty(ni, nk, num_areas, dtype=torch.int32, device=dev))   # npig
+
+
+def _box_ap_match(boxes, scores, labels, det_offsets, gt_boxes, gt_area, gt_label, gt_crowd, gt_offsets, categories, iou_thrs, area_ranges):
+    op = "box_ap_match"
+    n = _table(op, "boxes", boxes, torch.float64, "N", tail=(4,), note=" (x, y, w, h)")
+    _table(op, "scores", scores, torch.float32, "N", n)
+    _table(op, "labels", labels, torch.int64, "N", n)
+    g = _table(op, "gt_boxes", gt_boxes, torch.float64, "G", tail=(4,), note=" (x, y, w, h)")
+    for name, t, dt in (("gt_area", gt_area, torch.float64), ("gt_label", gt_label, torch.int64), ("gt_crowd", gt_crowd, torch.uint8)):
+        if t.dim() != 1 or t.shape[0] != g or t.dtype != dt:
+            raise ValueError(f"stlpose {op}: {name} must be {dt} [G={g}], got {t.dtype} {tuple(t.shape)}")
+    nk = _table(op, "categories", categories, torch.int64, "K")
+    cats = categories.cpu()
+    if nk > 65535 or bool((cats[1:] <= cats[:-1]).any()):
+        raise ValueError(f"stlpose {op}: categories must be strictly ascending, at most 65535 of them")
+    doff, goff, gper, max_n = _match_images(op, n, g, det_offsets, gt_offsets, iou_thrs, area_ranges, "IoU", capi.BOX_AP_THRS,
+                                            capi.BOX_AP_AREAS)
+    ni, max_g = gper.numel(), 0
     if g and nk:   # ground truths per (image, category)
         lab = gt_label.cpu()
         ci = torch.searchsorted(cats, lab).clamp_(max=nk - 1)
@@ -553,49 +578,36 @@ def _box_ap_match(boxes, scores, labels, det_offsets, gt_boxes, gt_area, gt_labe
             w = int(cnt.argmax())
             raise BoxApCapError(f"stlpose {op}: the image at table position {w // nk} has {max_g} ground truths of category "
                                 f"{int(cats[w % nk])}; the cap is {capi.BOX_AP_GT_MAX} (STL_BOX_AP_GT_MAX) per image and category", w // nk)
-    if bool(torch.isnan(scores).any()):
-        raise ValueError(f"stlpose {op}: a score is NaN")
-    if not boxes.is_cuda:
-        raise RuntimeError(f"stlpose {op}: boxes must be on the GPU")
+    slots = _match_slots(op, "boxes", boxes, scores, (("labels", labels), ("gt_boxes", gt_boxes), ("gt_area", gt_area),
+                                                      ("gt_label", gt_label), ("gt_crowd", gt_crowd)), ni, nk, capi.BOX_AP_AREAS)
     dev = boxes.device
-    _same_device((("scores", scores), ("labels", labels), ("gt_boxes", gt_boxes), ("gt_area", gt_area), ("gt_label", gt_label),
-                  ("gt_crowd", gt_crowd)), dev)
-    slot_score = torch.zeros(n, dtype=torch.float32, device=dev)
-    slot_cat = torch.full((n,), -1, dtype=torch.int32, device=dev)   # rows no workgroup claims stay out of every category
-    slot_rank = torch.zeros(n, dtype=torch.int32, device=dev)
-    matched = torch.zeros(n, dtype=torch.int64, device=dev)
-    ignored = torch.zeros(n, dtype=torch.int64, device=dev)
-    npig = torch.empty(ni, nk, capi.BOX_AP_AREAS, dtype=torch.int32, device=dev)
     b, s, l = boxes.contiguous(), scores.contiguous(), labels.contiguous()
     gb, ga, gl, gc = gt_boxes.contiguous(), gt_area.contiguous(), gt_label.contiguous(), gt_crowd.contiguous()
     do, go, ct = doff.to(dev), goff.to(dev), cats.to(dev)
     capi.call("stl_box_ap_match", b.data_ptr(), s.data_ptr(), l.data_ptr(), do.data_ptr(), n, max_n, gb.data_ptr(), ga.data_ptr(),
               gl.data_ptr(), gc.data_ptr(), go.data_ptr(), g, max_g, ni, ct.data_ptr(), nk, _doubles(iou_thrs), _doubles(area_ranges),
-              slot_score.data_ptr(), slot_cat.data_ptr(), slot_rank.data_ptr(), matched.data_ptr(), ignored.data_ptr(), npig.data_ptr(),
-              _st())
-    return slot_score, slot_cat, slot_rank, matched, ignored, npig
+              *(t.data_ptr() for t in slots), _st())
+    return slots
 
 
-def _box_ap_match_fake(boxes, scores, labels, det_offsets, gt_boxes, gt_area, gt_label, gt_crowd, gt_offsets, categories, iou_thrs,
-                       area_ranges):
-    n = boxes.shape[0]
-    return (boxes.new_empty(n, dtype=torch.float32), boxes.new_empty(n, dtype=torch.int32), boxes.new_empty(n, dtype=torch.int32),
-            boxes.new_empty(n, dtype=torch.int64), boxes.new_empty(n, dtype=torch.int64),
-            boxes.new_empty(det_offsets.shape[0] - 1, categories.shape[0], capi.BOX_AP_AREAS, dtype=torch.int32))
+def _match_fake(det, scores, det_offsets, nk: int, num_areas: int):
+    n = det.shape[0]
+    return (det.new_empty(n, dtype=scores.dtype), det.new_empty(n, dtype=torch.int32), det.new_empty(n, dtype=torch.int32),
+            det.new_empty(n, dtype=torch.int64), det.new_empty(n, dtype=torch.int64),
+            det.new_empty(det_offsets.shape[0] - 1, nk, num_areas, dtype=torch.int32))
 
 
 # slot_score, slot_cat (-1: the row is in no category's list), slot_rank, matched and ignored bits (bit t * 4 + a) per detection
 # row, npig [I, K, 4]; the slot layout is stated at stl_box_ap_match in include/stlpose_hip.h
 _define("box_ap_match(Tensor boxes, Tensor scores, Tensor labels, Tensor det_offsets, Tensor gt_boxes, Tensor gt_area, Tensor gt_label, "
         "Tensor gt_crowd, Tensor gt_offsets, Tensor categories, float[] iou_thrs, float[] area_ranges) "
-        "-> (Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)", _box_ap_match, _box_ap_match_fake)
+        "-> (Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)", _box_ap_match,
+        lambda b, s, l, do, gb, ga, gl, gc, go, cats, thrs, rng: _match_fake(b, s, do, cats.shape[0], capi.BOX_AP_AREAS))
 
 
 def _box_ap_accumulate(matched, ignored, rank, order, cat_offsets, npig, num_thrs: int, max_dets, rec_thrs):
     op = "box_ap_accumulate"
-    if matched.dim() != 1 or matched.dtype != torch.int64:
-        raise ValueError(f"stlpose {op}: matched must be int64 [S], got {matched.dtype} {tuple(matched.shape)}")
-    ns = matched.shape[0]
+    ns = _table(op, "matched", matched, torch.int64, "S")
     for name, t, dt in (("ignored", ignored, torch.int64), ("rank", rank, torch.int32), ("order", order, torch.int64)):
         if t.dim() != 1 or t.shape[0] != ns or t.dtype != dt:
             raise ValueError(f"stlpose {op}: {name} must be {dt} [S={ns}], got {t.dtype} {tuple(t.shape)}")
@@ -637,7 +649,7 @@ _define("box_ap_accumulate(Tensor matched, Tensor ignored, Tensor rank, Tensor o
         lambda m, i, r, o, c, p, t, md, rt: (m.new_empty(t, len(rt), p.shape[0], p.shape[1], len(md), dtype=torch.float64),
                                              m.new_empty(t, p.shape[0], p.shape[1], len(md), dtype=torch.float64)))
 
-# ------------------------------------------------------------------ pose scoring (csrc/keypoint_eval.hip; rescoring + OKS-NMS, COCOeval "keypoints")
+# ------------------------------------------------------------------ pose scoring (csrc/keypoint_eval.hip, csrc/coco_match.inc; rescoring + OKS-NMS, COCOeval "keypoints")
 # Every shape, dtype, device and cap the kernels rely on is checked here, before anything is launched.
 def _pose_var(op: str, sigmas):
     """(2 sigma)^2 as the host code forms it, for exactly 17 joints."""
@@ -654,8 +666,7 @@ def _pose_rescore_nms(preds, boxes, offsets, in_vis_thr: float, oks_thr: float, 
     if preds.dim() != 3 or tuple(preds.shape[1:]) != (j, 3) or preds.dtype not in (torch.float32, torch.float64):
         raise ValueError(f"stlpose {op}: preds must be float32 or float64 [P, {j}, 3], got {preds.dtype} {tuple(preds.shape)}")
     n = preds.shape[0]
-    if boxes.dim() != 2 or tuple(boxes.shape) != (n, 6) or boxes.dtype != torch.float64:
-        raise ValueError(f"stlpose {op}: boxes must be float64 [P={n}, 6] (centre, scale, area, score), got {boxes.dtype} {tuple(boxes.shape)}")
+    _table(op, "boxes", boxes, torch.float64, "P", n, tail=(6,), note=" (centre, scale, area, score)")
     var = _pose_var(op, sigmas)
     off, per = _ragged(op, "offsets", offsets, n)
     ni = per.numel()
@@ -688,73 +699,43 @@ _define("pose_rescore_nms(Tensor preds, Tensor boxes, Tensor offsets, float in_v
 def _oks_ap_match(kpts, scores, area, det_offsets, gt_kpts, gt_area, gt_bbox, gt_crowd, gt_numkp, gt_offsets, oks_thrs, area_ranges, sigmas):
     op = "oks_ap_match"
     j = capi.POSE_JOINTS
-    if kpts.dim() != 3 or tuple(kpts.shape[1:]) != (j, 3) or kpts.dtype != torch.float64:
-        raise ValueError(f"stlpose {op}: kpts must be float64 [N, {j}, 3], got {kpts.dtype} {tuple(kpts.shape)}")
-    n = kpts.shape[0]
+    n = _table(op, "kpts", kpts, torch.float64, "N", tail=(j, 3))
     for name, t in (("scores", scores), ("area", area)):
-        if t is not None and (t.dim() != 1 or t.shape[0] != n or t.dtype != torch.float64):
-            raise ValueError(f"stlpose {op}: {name} must be float64 [N={n}], got {t.dtype} {tuple(t.shape)}")
-    if gt_kpts.dim() != 3 or tuple(gt_kpts.shape[1:]) != (j, 3) or gt_kpts.dtype != torch.float64:
-        raise ValueError(f"stlpose {op}: gt_kpts must be float64 [G, {j}, 3], got {gt_kpts.dtype} {tuple(gt_kpts.shape)}")
-    g = gt_kpts.shape[0]
-    if gt_bbox.dim() != 2 or tuple(gt_bbox.shape) != (g, 4) or gt_bbox.dtype != torch.float64:
-        raise ValueError(f"stlpose {op}: gt_bbox must be float64 [G={g}, 4] (x, y, w, h), got {gt_bbox.dtype} {tuple(gt_bbox.shape)}")
+        if t is not None:
+            _table(op, name, t, torch.float64, "N", n)
+    g = _table(op, "gt_kpts", gt_kpts, torch.float64, "G", tail=(j, 3))
+    _table(op, "gt_bbox", gt_bbox, torch.float64, "G", g, tail=(4,), note=" (x, y, w, h)")
     for name, t, dt in (("gt_area", gt_area, torch.float64), ("gt_crowd", gt_crowd, torch.uint8), ("gt_numkp", gt_numkp, torch.int32)):
         if t.dim() != 1 or t.shape[0] != g or t.dtype != dt:
             raise ValueError(f"stlpose {op}: {name} must be {dt} [G={g}], got {t.dtype} {tuple(t.shape)}")
     var = _pose_var(op, sigmas)
-    doff, dper = _ragged(op, "det_offsets", det_offsets, n)
-    goff, gper = _ragged(op, "gt_offsets", gt_offsets, g)
-    ni = dper.numel()
-    if gper.numel() != ni:
-        raise ValueError(f"stlpose {op}: det_offsets cover {ni} images, gt_offsets {gper.numel()}")
-    if len(oks_thrs) != capi.OKS_AP_THRS or len(area_ranges) != 2 * capi.OKS_AP_AREAS:
-        raise ValueError(f"stlpose {op}: {capi.OKS_AP_THRS} OKS thresholds and {capi.OKS_AP_AREAS} (lo, hi) area ranges, got "
-                         f"{len(oks_thrs)} and {len(area_ranges)} numbers")
-    max_n = int(dper.max()) if ni else 0
-    if max_n > capi.BOX_MAX:
-        raise BoxApCapError(f"stlpose {op}: the image at table position {int(dper.argmax())} has {max_n} detections; the cap is "
-                            f"{capi.BOX_MAX} (STL_BOX_MAX) per image", int(dper.argmax()))
+    doff, goff, gper, max_n = _match_images(op, n, g, det_offsets, gt_offsets, oks_thrs, area_ranges, "OKS", capi.OKS_AP_THRS,
+                                            capi.OKS_AP_AREAS)
+    ni = gper.numel()
     max_g = int(gper.max()) if ni else 0
     if max_g > capi.BOX_AP_GT_MAX:
         raise BoxApCapError(f"stlpose {op}: the image at table position {int(gper.argmax())} has {max_g} ground truths; the cap is "
                             f"{capi.BOX_AP_GT_MAX} (STL_BOX_AP_GT_MAX) per image", int(gper.argmax()))
-    if bool(torch.isnan(scores).any()):
-        raise ValueError(f"stlpose {op}: a score is NaN")
-    if not kpts.is_cuda:
-        raise RuntimeError(f"stlpose {op}: kpts must be on the GPU")
+    # slot_cat: the rows beyond the first STL_OKS_AP_DETS of an image stay out of the category
+    slots = _match_slots(op, "kpts", kpts, scores, (("gt_kpts", gt_kpts), ("gt_area", gt_area), ("gt_bbox", gt_bbox), ("gt_crowd", gt_crowd),
+                                                    ("gt_numkp", gt_numkp)) + ((("area", area),) if area is not None else ()), ni, 1,
+                         capi.OKS_AP_AREAS)
     dev = kpts.device
-    _same_device((("scores", scores), ("gt_kpts", gt_kpts), ("gt_area", gt_area), ("gt_bbox", gt_bbox), ("gt_crowd", gt_crowd),
-                  ("gt_numkp", gt_numkp)) + ((("area", area),) if area is not None else ()), dev)
-    slot_score = torch.zeros(n, dtype=torch.float64, device=dev)
-    slot_cat = torch.full((n,), -1, dtype=torch.int32, device=dev)   # rows beyond the first STL_OKS_AP_DETS stay out of the category
-    slot_rank = torch.zeros(n, dtype=torch.int32, device=dev)
-    matched = torch.zeros(n, dtype=torch.int64, device=dev)
-    ignored = torch.zeros(n, dtype=torch.int64, device=dev)
-    npig = torch.empty(ni, 1, capi.OKS_AP_AREAS, dtype=torch.int32, device=dev)
     k, s, ar = kpts.contiguous(), scores.contiguous(), (area.contiguous() if area is not None else None)
     gk, ga, gb, gc, gn = gt_kpts.contiguous(), gt_area.contiguous(), gt_bbox.contiguous(), gt_crowd.contiguous(), gt_numkp.contiguous()
     do, go = doff.to(dev), goff.to(dev)
     capi.call("stl_oks_ap_match", k.data_ptr(), s.data_ptr(), ar.data_ptr() if ar is not None else None, do.data_ptr(), n, max_n,
               gk.data_ptr(), ga.data_ptr(), gb.data_ptr(), gc.data_ptr(), gn.data_ptr(), go.data_ptr(), g, max_g, ni, _doubles(oks_thrs),
-              _doubles(area_ranges), var, slot_score.data_ptr(), slot_cat.data_ptr(), slot_rank.data_ptr(), matched.data_ptr(),
-              ignored.data_ptr(), npig.data_ptr(), _st())
-    return slot_score, slot_cat, slot_rank, matched, ignored, npig
-
-
-def _oks_ap_match_fake(kpts, scores, area, det_offsets, gt_kpts, gt_area, gt_bbox, gt_crowd, gt_numkp, gt_offsets, oks_thrs, area_ranges,
-                       sigmas):
-    n = kpts.shape[0]
-    return (kpts.new_empty(n, dtype=torch.float64), kpts.new_empty(n, dtype=torch.int32), kpts.new_empty(n, dtype=torch.int32),
-            kpts.new_empty(n, dtype=torch.int64), kpts.new_empty(n, dtype=torch.int64),
-            kpts.new_empty(det_offsets.shape[0] - 1, 1, capi.OKS_AP_AREAS, dtype=torch.int32))
+              _doubles(area_ranges), var, *(t.data_ptr() for t in slots), _st())
+    return slots
 
 
 # the slots of box_ap_match for one category (0) and three area ranges (bit t * 3 + a), slot_score fp64; the layout is stated at
 # stl_oks_ap_match in include/stlpose_hip.h.  area None: the area of the keypoints' bounding box
 _define("oks_ap_match(Tensor kpts, Tensor scores, Tensor? area, Tensor det_offsets, Tensor gt_kpts, Tensor gt_area, Tensor gt_bbox, "
         "Tensor gt_crowd, Tensor gt_numkp, Tensor gt_offsets, float[] oks_thrs, float[] area_ranges, float[] sigmas) "
-        "-> (Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)", _oks_ap_match, _oks_ap_match_fake)
+        "-> (Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)", _oks_ap_match,
+        lambda k, s, a, do, gk, ga, gb, gc, gn, go, thrs, rng, sg: _match_fake(k, s, do, 1, capi.OKS_AP_AREAS))
 
 OPS = ["person_mse", "heatmap_argmax", "final_preds", "flip_merge", "flip_merge_backward", "gaussian_targets", "affine_crop",
        "hrnet_forward", "hrnet_backward", "hrnet_backward_input", "pose_vectors", "pose_distances", "pose_topk", "pose_rank", "pose_rank_any",
