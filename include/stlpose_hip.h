@@ -223,6 +223,23 @@ int stl_flip_merge_backward(const float* g, float* da, float* dbf, const int32_t
 int stl_final_preds(const float* hm, const float* center, const float* scale, float* preds,
                     float* maxval, int B, int J, int H, int W, void* stream);
 
+/* The per-batch tail of an evaluation in one pass over the maps (eval_tail.hip).  a, bflip, target fp32 [B, J, H, W]: the network's
+ * output for the batch, its output for the mirrored batch (NULL: no flip test) and the target; perm int32 [J] as for
+ * stl_flip_merge (an entry outside [0, J) reads the joint itself); tweight fp32 [B, J].  The merged map 0.5 * (a + shift(flip(bflip)))
+ * of stl_flip_merge is formed in registers and not stored.  Written at rows row0 .. row0 + B - 1 of the caller's tables (the caller
+ * keeps them large enough): pred_xy, tgt_xy fp32 [., J, 2]: the arg-max of the merged map and of the target as
+ * stl_heatmap_argmax writes preds (zeroed where max <= 0); coords fp32 [., J, 2]: pred_xy after the +-0.25 px refinement of
+ * stl_final_preds; maxval fp32 [., J].  partial fp64 [B * J] (not offset by row0): per map the sum of ((merged - target) * w)^2,
+ * the difference in fp32, squares and sum in fp64 in a fixed order; the batch's PersonMSELoss is
+ * stl_sum_partials(partial, B * J, 0.5 / (B * J * H * W), loss, 0, stream).  H * W <= 2^22. */
+int stl_eval_tail(const float* a, const float* bflip, const int32_t* perm, const float* target, const float* tweight,
+                  float* pred_xy, float* tgt_xy, float* coords, float* maxval, double* partial, int B, int J, int H, int W,
+                  int64_t row0, void* stream);
+/* Inverse crop transform of stl_final_preds over N table rows: preds fp32 [N, J, 3] = (x, y of coords [N, J, 2] in image
+ * coordinates, maxval [N, J]); center, scale fp32 [N, 2]; H, W: the heat maps' size. */
+int stl_eval_affine(const float* coords, const float* maxval, const float* center, const float* scale, float* preds, int64_t N,
+                    int J, int H, int W, void* stream);
+
 /* Table-driven batched helpers (one launch for the whole network). */
 typedef struct stl_wprep { /* one conv weight: OIHW fp32 master -> kernel layouts */
     int64_t src_off;  /* element offset in master */

@@ -199,6 +199,8 @@ SIGNATURES = {
     "stl_flip_merge": [vp, vp, vp, vp, i32, i32, i32, i32, vp],
     "stl_flip_merge_backward": [vp, vp, vp, vp, i32, i32, i32, i32, vp],
     "stl_final_preds": [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp],
+    "stl_eval_tail": [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i64, vp],
+    "stl_eval_affine": [vp, vp, vp, vp, vp, i64, i32, i32, i32, vp],
     "stl_weight_prep": [i32, vp, vp, vp, i32, i32, vp],
     "stl_reduce_slabs": [vp, vp, vp, i32, i32, vp],
     "stl_reduce_slabs_range": [C.POINTER(ReduceRange), vp],

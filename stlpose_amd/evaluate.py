@@ -239,14 +239,22 @@ class Evaluator:
 
     ``scoring="host"`` rescores, suppresses and scores with the numpy functions above; ``scoring="device"`` with their
     counterparts of ``keypoint_eval`` (``rescore_and_nms_device``, ``keypoint_ap``).  The returned dict and ``preds_file``
-    have the same format either way."""
+    have the same format either way.
+
+    ``tail="host"`` finishes every batch on the host (``_batch_outputs``: loss, PCK and decode each copy their result back, so
+    the device idles while the host catches up); ``tail="device"`` keeps the batches' results in tables on the device
+    (``eval_tail.EvalTables``: one fused pass over the heat maps per batch, no host sync between the first and the last batch) and
+    copies them back once.  Results, PCK and AP are those of the host tail bit for bit; a batch's fp32 loss may be the neighbouring
+    float32 (another fp64 summation order)."""
 
     def __init__(self, model, device="cuda", model_name: str = "HRNet", flip: bool = True, process_group=None,
-                 shard_loader: bool = True, scoring: str = "host"):
+                 shard_loader: bool = True, scoring: str = "host", tail: str = "host"):
         from .loss import PersonMSELoss
         if scoring not in ("host", "device"):
             raise ValueError(f"Evaluator: scoring {scoring!r} ('host' or 'device')")
-        self.scoring = scoring
+        if tail not in ("host", "device"):
+            raise ValueError(f"Evaluator: tail {tail!r} ('host' or 'device')")
+        self.scoring, self.tail = scoring, tail
         self.model, self.device, self.model_name, self.flip = model, torch.device(device), model_name, flip
         self.loss_function = PersonMSELoss()
         self.pg, self.shard_loader = process_group, shard_loader
@@ -288,6 +296,21 @@ class Evaluator:
                 "badly scaled checkpoint overflows; evaluate it with compute_dtype='bf16' or 'fp32'.")
         return loss, float(accuracy(output, target)[1]), keypoints, max_vals
 
+    def _batch_to_tables(self, tables, imgs, target, target_weight):
+        """tail="device": the two forwards of the flip test and the two launches of ``EvalTables.add``; nothing comes back.  The
+        network is called directly -- ``forward_pass`` would write the merged map, which the fused tail never stores."""
+        from .eval_tail import EvalTables
+        if self.model_name != "HRNet":
+            raise NotImplementedError("Wrong model name. Only ['HRNet'] supported")
+        imgs = imgs.float().to(self.device, non_blocking=True)
+        out = self.model(imgs)
+        out_flipped = self.model(imgs.flip(3)) if self.flip is True else None
+        if tables is None:
+            tables = EvalTables(self.device, joints=out.shape[1])
+        tables.add(out, out_flipped, target.float().to(self.device, non_blocking=True),
+                   target_weight.float().to(self.device, non_blocking=True))
+        return tables
+
     @torch.no_grad()
     def evaluate_model(self, loader: Iterable, gt_annotations: Optional[Sequence[dict]] = None, labels_file: Optional[str] = None,
                        preds_file: Optional[str] = None) -> dict:
@@ -296,21 +319,34 @@ class Evaluator:
         loss_sum = acc_sum = 0.0
         nb = 0
         all_preds, all_boxes, image_ids, seq = [], [], [], []
+        on_tables = getattr(self, "tail", "host") == "device"
+        tables, all_centers, all_scales = None, [], []
         for bi, (imgs, target, target_weight, metadata) in self._my_batches(loader):
             gbi = bi if (self.world == 1 or self.shard_loader) else int(metadata.get("batch_index", bi * self.world + self.rank))
             centers, scales = np.asarray(metadata["center"], np.float64), np.asarray(metadata["scale"], np.float64)
             score = np.asarray(metadata["score"], np.float64)
-            loss, acc, keypoints, max_vals = self._batch_outputs(imgs, target, target_weight, centers, scales)
-            loss_sum, acc_sum, nb = loss_sum + loss, acc_sum + acc, nb + 1
-            n = keypoints.shape[0]
-            preds = np.zeros((n, keypoints.shape[1], 3), np.float32)
-            preds[:, :, :2], preds[:, :, 2:3] = keypoints[:, :, :2], max_vals
+            if on_tables:
+                tables = self._batch_to_tables(tables, imgs, target, target_weight)
+                n = len(centers)
+                all_centers.append(centers), all_scales.append(scales)
+            else:
+                loss, acc, keypoints, max_vals = self._batch_outputs(imgs, target, target_weight, centers, scales)
+                loss_sum, acc_sum, nb = loss_sum + loss, acc_sum + acc, nb + 1
+                n = keypoints.shape[0]
+                preds = np.zeros((n, keypoints.shape[1], 3), np.float32)
+                preds[:, :, :2], preds[:, :, 2:3] = keypoints[:, :, :2], max_vals
+                all_preds.append(preds)
             boxes = np.zeros((n, 6))
             boxes[:, 0:2], boxes[:, 2:4] = centers[:, 0:2], scales[:, 0:2]
             boxes[:, 4], boxes[:, 5] = np.prod(scales * 200, 1), score
-            all_preds.append(preds), all_boxes.append(boxes)
+            all_boxes.append(boxes)
             image_ids += [int(v) for v in np.asarray(metadata["image_id"]).tolist()]
             seq += [(gbi, i) for i in range(n)]
+        if tables is not None:   # the epoch's one copy from the device; the sums run in batch order like the host tail's
+            epoch_preds, losses, pcks = tables.finish(np.concatenate(all_centers), np.concatenate(all_scales))
+            all_preds = [epoch_preds]
+            for loss, acc in zip(losses, pcks):
+                loss_sum, acc_sum, nb = loss_sum + loss, acc_sum + acc, nb + 1
         preds = np.concatenate(all_preds) if all_preds else np.zeros((0, 17, 3), np.float32)
         boxes = np.concatenate(all_boxes) if all_boxes else np.zeros((0, 6))
         sums = [loss_sum, acc_sum, float(nb)]
@@ -320,7 +356,9 @@ class Evaluator:
         on_device = getattr(self, "scoring", "host") == "device"
         if on_device:
             from .keypoint_eval import keypoint_ap, rescore_and_nms_device
-            kept = rescore_and_nms_device(preds, boxes, image_ids, device=getattr(self, "device", None)) if len(preds) else None
+            # the device tail's preds are on the device already (one process: the gathered set is the local one)
+            dev_preds = tables.preds if tables is not None and self.world == 1 else preds
+            kept = rescore_and_nms_device(dev_preds, boxes, image_ids, device=getattr(self, "device", None)) if len(preds) else None
             results = kept.to_list() if kept is not None else []
         else:
             results = rescore_and_nms(preds, boxes, image_ids) if len(preds) else []

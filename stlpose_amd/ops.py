@@ -116,6 +116,69 @@ def _flip_merge_autograd(ctx, grad):
 torch.library.register_autograd("stlpose::flip_merge", _flip_merge_autograd, setup_context=_flip_merge_setup, lib=_LIB)
 
 
+# ------------------------------------------------------------------ evaluation tail (eval_tail.py: the epoch tables)
+def _f32_table(op: str, name: str, t: torch.Tensor, rows: int, tail: tuple, dtype=torch.float32) -> None:
+    if t.dtype != dtype or not t.is_contiguous() or t.dim() != 1 + len(tail) or tuple(t.shape[1:]) != tail or t.shape[0] < rows:
+        raise ValueError(f"stlpose {op}: {name} must be a contiguous {dtype} [>= {rows}, {', '.join(map(str, tail))}] table, got "
+                         f"{t.dtype} {tuple(t.shape)}")
+
+
+def _eval_tail(out: torch.Tensor, out_flipped: Optional[torch.Tensor], perm: torch.Tensor, target: torch.Tensor, target_weight: torch.Tensor,
+               pred_xy: torch.Tensor, tgt_xy: torch.Tensor, coords: torch.Tensor, maxval: torch.Tensor, partial: torch.Tensor,
+               losses: torch.Tensor, row0: int, slot: int) -> None:
+    """Two launches, no allocation of results and no sync: stl_eval_tail into rows row0.. of the tables and into partial [B * J],
+    stl_sum_partials of those into losses[slot]."""
+    op = "eval_tail"
+    a, t = out.contiguous().float(), target.contiguous().float()
+    f = out_flipped.contiguous().float() if out_flipped is not None else None
+    if a.dim() != 4 or t.shape != a.shape or (f is not None and f.shape != a.shape):
+        raise ValueError(f"stlpose {op}: out {tuple(out.shape)}, out_flipped {None if f is None else tuple(f.shape)} and target "
+                         f"{tuple(target.shape)} must be one [B, J, H, W]")
+    b, j, h, w = a.shape
+    if target_weight.numel() != b * j:
+        raise ValueError(f"stlpose {op}: target_weight {tuple(target_weight.shape)} for {b} x {j} maps")
+    if perm.numel() != j:
+        raise ValueError(f"stlpose {op}: perm of {perm.numel()} entries for {j} joints")
+    if row0 < 0 or slot < 0 or slot >= losses.numel() or losses.dtype != torch.float32 or not losses.is_contiguous():
+        raise ValueError(f"stlpose {op}: row0 {row0}, slot {slot} of a float32 loss table of {losses.numel()}")
+    for name, tab, tail in (("pred_xy", pred_xy, (j, 2)), ("tgt_xy", tgt_xy, (j, 2)), ("coords", coords, (j, 2)), ("maxval", maxval, (j,))):
+        _f32_table(op, name, tab, row0 + b, tail)
+    if partial.dtype != torch.float64 or not partial.is_contiguous() or partial.numel() < b * j:
+        raise ValueError(f"stlpose {op}: partial must be contiguous float64 with at least {b * j} entries")
+    if b * j == 0:
+        return
+    tw = target_weight.float().reshape(b, j).contiguous()
+    p = perm.to(torch.int32).contiguous()
+    capi.call("stl_eval_tail", a.data_ptr(), f.data_ptr() if f is not None else None, p.data_ptr(), t.data_ptr(), tw.data_ptr(),
+              pred_xy.data_ptr(), tgt_xy.data_ptr(), coords.data_ptr(), maxval.data_ptr(), partial.data_ptr(), b, j, h, w, row0, _st())
+    capi.call("stl_sum_partials", partial.data_ptr(), b * j, 0.5 / float(b * j * h * w), losses.data_ptr() + 4 * slot, 0, _st())
+
+
+_define("eval_tail(Tensor out, Tensor? out_flipped, Tensor perm, Tensor target, Tensor target_weight, Tensor(a!) pred_xy, "
+        "Tensor(b!) tgt_xy, Tensor(c!) coords, Tensor(d!) maxval, Tensor(e!) partial, Tensor(f!) losses, int row0, int slot) -> ()",
+        _eval_tail, lambda *a: None)
+
+
+def _eval_affine(coords: torch.Tensor, maxval: torch.Tensor, center: torch.Tensor, scale: torch.Tensor, h: int, w: int) -> torch.Tensor:
+    op = "eval_affine"
+    n = center.shape[0]
+    if coords.dim() != 3 or coords.shape[2] != 2:
+        raise ValueError(f"stlpose {op}: coords {tuple(coords.shape)} ([>= N, J, 2])")
+    j = coords.shape[1]
+    _f32_table(op, "coords", coords, n, (j, 2))
+    _f32_table(op, "maxval", maxval, n, (j,))
+    if tuple(center.shape) != (n, 2) or tuple(scale.shape) != (n, 2):
+        raise ValueError(f"stlpose {op}: center {tuple(center.shape)} and scale {tuple(scale.shape)} must be [N, 2]")
+    c, s = center.contiguous().float(), scale.contiguous().float()
+    preds = torch.empty(n, j, 3, dtype=torch.float32, device=coords.device)
+    capi.call("stl_eval_affine", coords.data_ptr(), maxval.data_ptr(), c.data_ptr(), s.data_ptr(), preds.data_ptr(), n, j, h, w, _st())
+    return preds
+
+
+_define("eval_affine(Tensor coords, Tensor maxval, Tensor center, Tensor scale, int h, int w) -> Tensor", _eval_affine,
+        lambda co, mv, c, s, h, w: co.new_empty(c.shape[0], co.shape[1], 3))
+
+
 # ------------------------------------------------------------------ data pipeline (data/JointsDataset.py:189-286)
 def _targets(joints: torch.Tensor, vis: torch.Tensor, hh: int, wh: int, sx: float, sy: float, sigma: float) -> Tuple[torch.Tensor, torch.Tensor]:
     j, v = joints.contiguous().float(), vis.contiguous().float()
@@ -740,4 +803,4 @@ _define("oks_ap_match(Tensor kpts, Tensor scores, Tensor? area, Tensor det_offse
 OPS = ["person_mse", "heatmap_argmax", "final_preds", "flip_merge", "flip_merge_backward", "gaussian_targets", "affine_crop",
        "hrnet_forward", "hrnet_backward", "hrnet_backward_input", "pose_vectors", "pose_distances", "pose_topk", "pose_rank", "pose_rank_any",
        "box_select", "heatmap_resize_argmax", "det_decode", "det_nms", "det_loss", "box_ap_match", "box_ap_accumulate",
-       "pose_rescore_nms", "oks_ap_match"]
+       "pose_rescore_nms", "oks_ap_match", "eval_tail", "eval_affine"]

@@ -47,16 +47,12 @@ def get_final_preds_hrnet(heatmaps, center, scale):
     return p, mx.cpu().numpy(), coords.astype(np.float32)
 
 
-def accuracy(output, target, hm_type="gaussian", thr=0.5):
-    """reference lib/metrics.py:321-364 (PCK on heatmap argmaxes; the corrupted line :355-356 read
-    as ``acc[i + 1] = dist_acc(dists[idx[i]])``).  Argmax runs on device; the 2*B*17 distances are
-    host arithmetic."""
-    o, t = _dev(output), _dev(target)
-    _, _, pred = max_preds_device(o)
-    _, _, tgt = max_preds_device(t)
-    pred, tgt = pred.cpu().numpy(), tgt.cpu().numpy()
+def pck_from_coords(pred, tgt, h, w, thr=0.5):
+    """The host arithmetic of ``accuracy`` behind its two arg-max calls: pred, tgt [B, J, 2] (x, y; the masked integer coordinates
+    of ``heatmap_argmax``) of maps of h x w -> (acc [J + 1], avg, cnt).  Keeps the reference's normalisation (x by h / 10, y by
+    w / 10); a joint whose target has no coordinate above 1 in any sample counts as -1 and stays out of the average."""
+    pred, tgt = np.asarray(pred), np.asarray(tgt)
     b, j = pred.shape[:2]
-    h, w = o.shape[2:]
     norm = np.ones((b, 2)) * np.array([h, w]) / 10
     ok = (tgt[..., 0] > 1) & (tgt[..., 1] > 1)
     d = np.linalg.norm(pred / norm[:, None] - tgt / norm[:, None], axis=-1)
@@ -71,6 +67,19 @@ def accuracy(output, target, hm_type="gaussian", thr=0.5):
     avg = tot / cnt if cnt else 0
     if cnt:
         acc[0] = avg
+    return acc, avg, cnt
+
+
+def accuracy(output, target, hm_type="gaussian", thr=0.5):
+    """reference lib/metrics.py:321-364 (PCK on heatmap argmaxes; the corrupted line :355-356 read
+    as ``acc[i + 1] = dist_acc(dists[idx[i]])``).  Argmax runs on device; the 2*B*17 distances are
+    host arithmetic (``pck_from_coords``)."""
+    o, t = _dev(output), _dev(target)
+    _, _, pred = max_preds_device(o)
+    _, _, tgt = max_preds_device(t)
+    pred, tgt = pred.cpu().numpy(), tgt.cpu().numpy()
+    h, w = o.shape[2:]
+    acc, avg, cnt = pck_from_coords(pred, tgt, h, w, thr)
     return acc, avg, cnt, pred
 
 
