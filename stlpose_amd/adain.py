@@ -15,7 +15,7 @@ relu4_1 features, per image and channel over the pixels: ``t = s_s * (f - m_c) /
 then ``t <- alpha * t + (1 - alpha) * f``: together ONE affine per (image, channel), ``affine_coefficients``.
 
 MI355X-first.  The 3x3 convs run on the implicit-GEMM ``stl_conv_forward`` (bias + ReLU in its epilogue) exactly as
-``vgg.Trunk.conv`` lists them.  That kernel pads with zeros, so each layer is: ``stl_reflect_gather`` writes the explicitly
+``vgg.list_conv`` lists them.  That kernel pads with zeros, so each layer is: ``stl_reflect_gather`` writes the explicitly
 reflection-padded (H+2) x (W+2) NHWC map -- with the max-pool / upsample that sits between two convs, and in front of the
 decoder the AdaIN affine, fused in -- the conv runs as a "same" conv on it, and the next gather reads only the interior of that
 output (DESIGN.md "AdaIN: the ring").  The 1x1 conv at encoder index 0 is folded into conv1_1 on the host (exact: the padding
@@ -32,7 +32,7 @@ import torch.nn as nn
 
 from . import capi
 from .launch import LaunchList
-from .vgg import Trunk, dtype_code
+from .vgg import add_conv, dtype_code, list_conv, pack_convs, prep_weights, weight_table
 
 # (Sequential index, cin, cout, op in front of the conv's reflection pad: None, "pool" or "up")
 ENCODER_LAYOUT = [(2, 3, 64, None), (5, 64, 64, None), (9, 64, 128, "pool"), (12, 128, 128, None), (16, 128, 256, "pool"),
@@ -93,21 +93,13 @@ def check_size(what: str, H: int, W: int) -> None:
                          "then equals floor pooling, and the reflection at relu4_1 has the 2 pixels it needs)")
 
 
-def _leaf(parent: nn.Module, idx: int, ci: int, co: int, ks: int) -> nn.Module:
-    leaf = nn.Module()
-    leaf.register_parameter("weight", nn.Parameter(torch.zeros(co, ci, ks, ks), requires_grad=False))
-    leaf.register_parameter("bias", nn.Parameter(torch.zeros(co), requires_grad=False))
-    parent.add_module(str(idx), leaf)
-    return leaf
-
-
 class _Plan:
     """Static launch list for nb images of H x W: the encoder up to relu4_1 with its statistics and, with ``decode``, the
     decoder behind the affine gather.  Two buffers alternate: a gather writes ``pad``, the conv reads it and writes ``act``,
     the next gather reads ``act``.  Holds every buffer the launches of ``encode`` and ``decode`` (LaunchLists, one ``keep``) point into."""
 
     def __init__(self, mod: "AdaINStylizer", nb: int, H: int, W: int, dev, decode: bool):
-        self.dt, self.esz = mod.dtype, (2 if mod.dtype == capi.BF16 else 4)
+        self.dt, self.esz = mod.dtype, capi.DTYPES[mod.dtype][0]
         self.nb, self.H, self.W = nb, H, W
         self.img = torch.zeros(nb, 3, H, W, device=dev)
         dt, nb_ = self.dt, nb
@@ -133,8 +125,8 @@ class _Plan:
         pad, act = self.pad.data_ptr(), self.act.data_ptr()
 
         def conv(ops, li, h, w, ci, co, ks, src, relu):
-            Trunk.conv(self, ops, nb_, h, w, ci, co, ks, src, mod.wk.data_ptr() + mod.wtab[li].fwd_off * self.esz, act,
-                       bias=mod.bias_flat.data_ptr() + 4 * mod.bias_off[li], out_relu=relu)
+            list_conv(ops, dt, nb_, h, w, ci, co, ks, src, mod.wk.data_ptr() + mod.wtab[li].fwd_off * self.esz, act,
+                      bias=mod.bias_flat.data_ptr() + 4 * mod.bias_off[li], out_relu=relu)
 
         # ---- encoder: conv1_1 (with the 1x1 input conv folded in) on reflection patches, then gather -> conv per layer
         self.encode = ops = LaunchList()
@@ -172,11 +164,11 @@ class AdaINStylizer(nn.Module):
             raise ValueError(f"compute_dtype must be 'fp32' or 'bf16', got {compute_dtype!r}")
         self.dtype = dtype_code(compute_dtype)
         self.encoder, self.decoder = nn.Module(), nn.Module()
-        _leaf(self.encoder, 0, 3, 3, 1)
+        add_conv(self.encoder, 0, 3, 3, 1)
         for idx, ci, co, _ in ENCODER_LAYOUT:
-            _leaf(self.encoder, idx, ci, co, 3)
+            add_conv(self.encoder, idx, ci, co)
         for idx, ci, co, _ in DECODER_LAYOUT:
-            _leaf(self.decoder, idx, ci, co, 3)
+            add_conv(self.decoder, idx, ci, co)
         self._plans: Dict = {}
         self._flat_dev = None
         if encoder_state_dict is not None:
@@ -209,52 +201,31 @@ class AdaINStylizer(nn.Module):
         e0, e2 = getattr(self.encoder, "0"), getattr(self.encoder, "2")
         return fold_input_conv(e0.weight.detach(), e0.bias.detach(), e2.weight.detach(), e2.bias.detach())
 
-    def _ready(self, dev) -> None:
-        """Pack the 18 convs in launch order on `dev` and lay them out for the conv kernel (once: the weights are frozen).
-        A repack drops the plans: their launches point into the old buffers."""
-        if self._flat_dev == dev:
-            return
+    def _pack(self, dev) -> None:
+        """The host half of ``_ready``: the 18 convs in launch order on `dev` (``vgg.pack_convs``: conv1_1 folded, the last conv's
+        Co zero-padded to the conv's minimum), their weight table and the still empty kernel-layout buffer ``wk``.  Drops the
+        plans: their launches point into the old buffers."""
         self.to(dev)
-        ws, bs, self.bias_off = [], [], []
-        rows = []   # (cin, cout as stored)
-        w, b = self.folded_conv1_1()
-        convs = [(w, b)]
-        for idx, _, _, _ in ENCODER_LAYOUT[1:]:
-            leaf = getattr(self.encoder, str(idx))
-            convs.append((leaf.weight.detach(), leaf.bias.detach()))
-        for idx, _, _, _ in DECODER_LAYOUT:
-            leaf = getattr(self.decoder, str(idx))
-            convs.append((leaf.weight.detach(), leaf.bias.detach()))
-        w, b = convs[-1]   # 64 -> 3: Co zero-padded to the conv's minimum
+        convs = [self.folded_conv1_1()]
+        for part, layout in ((self.encoder, ENCODER_LAYOUT[1:]), (self.decoder, DECODER_LAYOUT)):
+            for idx, _, _, _ in layout:
+                leaf = getattr(part, str(idx))
+                convs.append((leaf.weight.detach(), leaf.bias.detach()))
+        w, b = convs[-1]   # 64 -> 3
         convs[-1] = (torch.cat([w, w.new_zeros(OUT_CO - 3, *w.shape[1:])]), torch.cat([b, b.new_zeros(OUT_CO - 3)]))
-        off = 0
-        for w, b in convs:
-            ws.append(w.reshape(-1).float())
-            bs.append(b.float())
-            self.bias_off.append(off)
-            off += b.numel()
-            rows.append((w.shape[1], w.shape[0]))
-        self.w_flat = torch.cat(ws).to(dev).contiguous()
-        self.bias_flat = torch.cat(bs).to(dev).contiguous()
-        # kernel layouts + table, as vgg.Trunk builds them: conv1_1 is a 1x1 conv on 32-wide patches ([Co][32])
-        self.wtab = tab = (capi.WPrep * len(rows))()
-        src = off = blk = 0
-        for i, (ci, co) in enumerate(rows):
-            patch = i == 0
-            cip, kk = (32, 1) if patch else (ci, 9)
-            e = tab[i]
-            e.src_off, e.fwd_off, e.bwd_off = src, off, -1
-            e.Co, e.Ci, e.ks, e.Cip, e.patch, e.blk0 = co, ci, 3, cip, int(patch), blk
-            src += co * ci * 9
-            off += co * kk * cip
-            blk += math.ceil(co * ci * 9 / 1024)
-        self.wk = torch.zeros(off, dtype=torch.bfloat16 if self.dtype == capi.BF16 else torch.float32, device=dev)
-        wtab_dev = torch.frombuffer(bytearray(bytes(tab)), dtype=torch.uint8).clone().to(dev)
-        capi.call("stl_weight_prep", self.dtype, self.w_flat.data_ptr(), self.wk.data_ptr(), wtab_dev.data_ptr(), len(rows), blk,
-                  torch.cuda.current_stream().cuda_stream)
-        self._wtab_dev = wtab_dev
-        self._flat_dev = dev
+        self.w_flat, self.bias_flat, self.bias_off = pack_convs(convs, dev)
+        self.wtab, wk_elems, self.wblocks = weight_table([(w.shape[1], w.shape[0]) for w, _ in convs])
+        self.wk = torch.zeros(wk_elems, dtype=capi.DTYPES[self.dtype][1], device=dev)
+        self._wtab_dev = torch.frombuffer(bytearray(bytes(self.wtab)), dtype=torch.uint8).clone().to(dev)
         self._plans.clear()
+
+    def _ready(self, dev) -> None:
+        """Pack the convs on `dev` and lay them out for the conv kernel, once per (re)pack: the weights are frozen."""
+        if self._flat_dev != dev:
+            self._pack(dev)
+            prep_weights(self.dtype, self.w_flat, self.wk, self._wtab_dev, len(self.wtab), self.wblocks,
+                         torch.cuda.current_stream().cuda_stream)
+            self._flat_dev = dev
 
     # ---------------------------------------------------------------- checks shared by the entry points
     @staticmethod

@@ -8,10 +8,13 @@ from __future__ import annotations
 import ctypes as C
 import os
 
+import torch
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("STLPOSE_HIP_LIB") or os.path.join(_HERE, "libstlpose_hip.so")   # override: A/B of two builds
 
 F32, BF16, F16 = 0, 1, 2
+DTYPES = {F32: (4, torch.float32), BF16: (2, torch.bfloat16), F16: (2, torch.float16)}   # code -> (bytes per element, torch dtype)
 
 
 def dt2(grad_dtype: int, fwd_dtype: int) -> int:

@@ -30,10 +30,14 @@ import numpy as np
 import torch
 
 from . import capi, ops
-from .efficientdet import MAX_SIZE, pointwise_fields, resize_meta
+from .efficientdet import MAX_SIZE, list_dwconv, list_pointwise, resize_meta
 from .launch import LaunchList
 
 HEADS = ("regressor", "classifier")
+# the backward entry points and workspace queries: fp32 name -> its 16-bit counterpart (the forward ones: efficientdet.list_*)
+NAME16 = {"stl_det_pointwise_bwd_slabs": "stl_det_pointwise16_bwd_slabs", "stl_det_dwconv_bwd_parts": "stl_det_dwconv16_bwd_parts",
+          "stl_det_pointwise_bwd_weight": "stl_det_pointwise16_bwd_weight", "stl_det_pointwise_bwd_data": "stl_det_pointwise16_bwd_data",
+          "stl_det_dwconv_bwd_weight": "stl_det_dwconv16_bwd_weight", "stl_det_dwconv_bwd_data": "stl_det_dwconv16_bwd_data"}
 
 
 # ------------------------------------------------------------------------------------------------ targets
@@ -108,9 +112,8 @@ class HeadTrain:
         gdtype = torch.bfloat16 if self.h16 else torch.float32
         self.ga, self.gb = torch.empty(m0 * c, device=dev, dtype=gdtype), torch.empty(m0 * c, device=dev, dtype=gdtype)   # gradients in flight, reused
         kmax = max(c, 9 * max(4, nc))
-        sfx = "16" if self.h16 else ""
-        self.pw_part = torch.empty(getattr(lib, f"stl_det_pointwise{sfx}_bwd_slabs")(m0) * (c * kmax + kmax), device=dev)
-        self.dw_part = torch.empty(getattr(lib, f"stl_det_dwconv{sfx}_bwd_parts")(m0) * 9 * c, device=dev)
+        self.pw_part = torch.empty(getattr(lib, self._name("stl_det_pointwise_bwd_slabs"))(m0) * (c * kmax + kmax), device=dev)
+        self.dw_part = torch.empty(getattr(lib, self._name("stl_det_dwconv_bwd_parts"))(m0) * 9 * c, device=dev)
         self.grads: Dict[str, Dict[str, torch.Tensor]] = {}
         for name, out, k, act in (("regressor", self.reg, 4, 0), ("classifier", self.cls, nc, 2)):
             lay, n = L[name], self.nlayers
@@ -125,12 +128,13 @@ class HeadTrain:
                 t, d, z = [f], [], []
                 for i in range(n):
                     d.append(buf()), z.append(buf()), t.append(buf())
-                    self._dw(t[i], d[i], plan._w(lay["dw"][i]), hh)
-                    self._pw(plan, d[i], t[i + 1], M, hh * hh, c, c, lay["pw"][lv][i], 1, z=z[i])
+                    list_dwconv(self.fwd, self.code, t[i], plan._w(lay["dw"][i]), None, d[i], B, hh, c, 3, 1, 0)
+                    list_pointwise(self.fwd, self.code, plan.pw_fields(d[i], t[i + 1], hh * hh, c, c, lay["pw"][lv][i], 1), False, z=z[i])
                 dh = buf()
-                self._dw(t[n], dh, plan._w(lay["hdw"]), hh)
+                list_dwconv(self.fwd, self.code, t[n], plan._w(lay["hdw"]), None, dh, B, hh, c, 3, 1, 0)
                 strides = dict(img_stride=A * k, row_stride=9 * k, off=aoff * k)
-                self._pw(plan, dh, out, M, hh * hh, c, 9 * k, lay["hpw"], act, **strides)
+                list_pointwise(self.fwd, self.code, plan.pw_fields(dh, out, hh * hh, c, 9 * k, lay["hpw"], act, **strides), True)
+                self.fwd.keep_alive(*d, *t, dh)   # the pointwise descriptors hold their addresses
                 # backward, from the header down; ga / gb alternate as the gradient of a depthwise / a pointwise output
                 self.hdr[name].append(self._pw_bwd(plan, dh, None, self.ga, M, hh * hh, c, 9 * k, lay["hpw"], g["hpw_w"][lv],
                                                    g["hpw_b"][lv], **strides))
@@ -140,22 +144,8 @@ class HeadTrain:
                     self._dw_bwd(t[i], self.ga, plan._w(lay["dw"][i]), g["dw"][lv, i], z[i - 1] if i else None, self.gb if i else None, hh)
                 aoff += hh * hh * 9
 
-    def _dw(self, x, y, w, h):
-        if self.h16:
-            self.fwd.add("stl_det_dwconv16", self.code, x, w, None, y, None, self.B, h, h, self.c, 3, 1, 0)
-        else:
-            self.fwd.add("stl_det_dwconv", x, w, None, y, self.B, h, h, self.c, 3, 1, 0)
-
-    def _pw(self, plan, x, out, M, hw, ci, co, pk, act, z=None, img_stride=None, row_stride=None, off=0):
-        w, b, kp, np_ = pk
-        common = pointwise_fields(x, (plan.wbuf16 if self.h16 else plan.wbuf)[w:], plan.wbuf[b:], None, None, out, M, hw, ci, co, kp,
-                                  np_, act, img_stride, row_stride, off)
-        self.fwd.keep_alive(x, out)   # the descriptor holds their addresses
-        if self.h16:   # the inference plan's descriptor: reg / cls come out fp32, everything else in adtype
-            p, sfx = capi.DetPointwise16(*common, self.code, 1 if out.dtype == torch.float32 else 0), "16"
-        else:
-            p, sfx = capi.DetPointwise(*common), ""
-        self.fwd.add(*((f"stl_det_pointwise{sfx}", p) if z is None else (f"stl_det_pointwise{sfx}_train", p, z)))   # _train: also stores the pre-activation z
+    def _name(self, name: str) -> str:
+        return NAME16[name] if self.h16 else name
 
     def _pw_bwd(self, plan, x, dy, dx, M, hw, ci, co, pk, gw, gb, img_stride=None, row_stride=None, off=0):
         """Weight and data gradient of one pointwise layer; dy None: a header, whose dy (dreg / dlogit, fp32) set_grads fills in."""
@@ -164,24 +154,20 @@ class HeadTrain:
                 hw * co if img_stride is None else img_stride, co if row_stride is None else row_stride, off, hw, ci, co)
         if self.h16:
             wt, kt, nt = self.layoutT[w]
-            p, sfx = capi.DetPointwise16Bwd(x.data_ptr(), self.wbufT[wt:].data_ptr(), *ptrs, kt, nt, self.code, 1 if dy is None else 0, 0), "16"
+            p = capi.DetPointwise16Bwd(x.data_ptr(), self.wbufT[wt:].data_ptr(), *ptrs, kt, nt, self.code, 1 if dy is None else 0, 0)
         else:
-            p, sfx = capi.DetPointwiseBwd(x.data_ptr(), plan.wbuf[w:].data_ptr(), *ptrs, kp, np_, 0), ""
+            p = capi.DetPointwiseBwd(x.data_ptr(), plan.wbuf[w:].data_ptr(), *ptrs, kp, np_, 0)
         self.bwd.keep_alive(x, gw, gb)   # the descriptor holds their addresses
-        self.bwd.add(f"stl_det_pointwise{sfx}_bwd_weight", p)
-        self.bwd.add(f"stl_det_pointwise{sfx}_bwd_data", p)
+        self.bwd.add(self._name("stl_det_pointwise_bwd_weight"), p)
+        self.bwd.add(self._name("stl_det_pointwise_bwd_data"), p)
         return p
 
     def _dw_bwd(self, x, dy, w, gw, z, dx, h):
         """Weight gradient of one depthwise layer and, with dx, its data gradient times swish'(z) of the layer below."""
-        if self.h16:
-            self.bwd.add("stl_det_dwconv16_bwd_weight", self.code, x, dy, self.dw_part, gw, self.B, h, h, self.c)
-            if dx is not None:
-                self.bwd.add("stl_det_dwconv16_bwd_data", dy, w, z, dx, self.B, h, h, self.c, self.code)
-            return
-        self.bwd.add("stl_det_dwconv_bwd_weight", x, dy, self.dw_part, gw, self.B, h, h, self.c)
+        code = (self.code,) if self.h16 else ()   # the 16-bit entry points take the forward tensors' type: first / last argument
+        self.bwd.add(self._name("stl_det_dwconv_bwd_weight"), *code, x, dy, self.dw_part, gw, self.B, h, h, self.c)
         if dx is not None:
-            self.bwd.add("stl_det_dwconv_bwd_data", dy, w, z, dx, self.B, h, h, self.c)
+            self.bwd.add(self._name("stl_det_dwconv_bwd_data"), dy, w, z, dx, self.B, h, h, self.c, *code)
 
     def set_grads(self, dreg: torch.Tensor, dlogit: torch.Tensor) -> None:
         self.dreg, self.dlogit = dreg, dlogit

@@ -53,7 +53,7 @@ STAGES = [(3, 1, 32, 16, 1, 1), (3, 2, 16, 24, 6, 2), (5, 2, 24, 40, 6, 2), (3, 
           (5, 4, 112, 192, 6, 2), (3, 1, 192, 320, 6, 1)]
 WIDTH_DEPTH = {0: (1.0, 1.0), 3: (1.2, 1.4)}   # efficientnet-b0 / -b3
 # compute_dtype -> (activation dtype, the library's dtype code STL_F32 / STL_BF16 / STL_F16)
-COMPUTE_DTYPES = {"fp32": (torch.float32, 0), "bf16": (torch.bfloat16, 1), "f16": (torch.float16, 2)}
+COMPUTE_DTYPES = {name: (capi.DTYPES[code][1], code) for name, code in (("fp32", capi.F32), ("bf16", capi.BF16), ("f16", capi.F16))}
 
 
 def round_filters(f: int, width: float) -> int:
@@ -249,34 +249,20 @@ class _Packer:
             w = w * s[:, None]
             b = t if b is None else b * s + t
         co, ci = w.shape
-        if self.dtype != torch.float32:
-            kp, np_ = -(-ci // 32) * 32, -(-co // 64) * 64
-            wp = w.new_zeros(np_, kp)
-            wp[:co, :ci] = w
-            wp = wp.reshape(np_ // 16, 16, kp // 32, 4, 8).permute(0, 2, 3, 1, 4).reshape(-1).to(self.dtype)
-            bo = None
-            if b is not None:
-                bp = w.new_zeros(np_)
-                bp[:co] = b
-                bo = self.add(bp)
-            off = self.n16
-            self.parts16.append(wp)
-            self.n16 += wp.numel()
-            if self.transposed:
-                wt, kt, nt = pack_transposed(w)
-                self.tmap[off] = (self.nT, kt, nt)
-                self.partsT.append(wt)
-                self.nT += wt.numel()
-            return off, bo, kp, np_
-        kp, np_ = -(-ci // 16) * 16, -(-co // 64) * 64
-        wp = w.new_zeros(kp, np_)
-        wp[:ci, :co] = w.t()
-        bo = None
-        if b is not None:
-            bp = w.new_zeros(np_)
-            bp[:co] = b
-            bo = self.add(bp)
-        return self.add(wp), bo, kp, np_
+        h16 = self.dtype != torch.float32
+        kp, np_ = -(-ci // 32) * 32 if h16 else -(-ci // 16) * 16, -(-co // 64) * 64
+        bo = None if b is None else self.add(_padded(b[None], 1, np_))
+        if not h16:
+            return self.add(_padded(w.t(), kp, np_)), bo, kp, np_
+        off, wp = self.n16, _tiles(_padded(w, np_, kp), self.dtype)
+        self.parts16.append(wp)
+        self.n16 += wp.numel()
+        if self.transposed:
+            wt, kt, nt = pack_transposed(w)
+            self.tmap[off] = (self.nT, kt, nt)
+            self.partsT.append(wt)
+            self.nT += wt.numel()
+        return off, bo, kp, np_
 
     def dw(self, conv: nn.Conv2d, bn: Optional[nn.BatchNorm2d] = None):
         """depthwise k x k (+ BN) -> (w offset [k][k][C], bias offset or None)."""
@@ -295,29 +281,84 @@ class _Packer:
         return torch.cat(self.parts16).to(dev).contiguous() if self.parts16 else None
 
 
+def _padded(w: torch.Tensor, rows: int, cols: int) -> torch.Tensor:
+    """The matrix w in the top left corner of zeros [rows, cols]."""
+    out = w.new_zeros(rows, cols)
+    out[:w.shape[0], :w.shape[1]] = w
+    return out
+
+
+def _tiles(wp: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
+    """[Np, Kp] (n the output channel, k the contraction) -> flat [Np / 16][Kp / 32][4][16][8], the order of the 16-bit MFMA
+    pointwise kernels (a lane loads its 8 k of one column in 16 bytes), rounded once to `dtype`."""
+    np_, kp = wp.shape
+    return wp.reshape(np_ // 16, 16, kp // 32, 4, 8).permute(0, 2, 3, 1, 4).reshape(-1).to(dtype)
+
+
 def pack_transposed(w: torch.Tensor):
     """The folded fp64 W' [co, ci] -> (bf16 pack, Kp, Np) for the data gradient dX = dY W'^T: the forward's tile layout with the
     roles of k and n swapped (the contraction runs over co, padded to Kp % 32 == 0; the output over ci, padded to Np % 64 == 0),
     rounded once from the fp64 fold."""
     co, ci = w.shape
     kp, np_ = -(-co // 32) * 32, -(-ci // 64) * 64
-    wp = w.new_zeros(np_, kp)
-    wp[:ci, :co] = w.t()
-    return wp.reshape(np_ // 16, 16, kp // 32, 4, 8).permute(0, 2, 3, 1, 4).reshape(-1).to(torch.bfloat16), kp, np_
+    return _tiles(_padded(w.t(), np_, kp), torch.bfloat16), kp, np_
 
 
 def unpack_transposed(wt: torch.Tensor, ci: int, co: int) -> torch.Tensor:
-    """pack_transposed's inverse: the bf16 W'^T [ci, co]."""
+    """pack_transposed's inverse (``_tiles`` undone): the bf16 W'^T [ci, co]."""
     kp, np_ = -(-co // 32) * 32, -(-ci // 64) * 64
     return wt.reshape(np_ // 16, kp // 32, 4, 16, 8).permute(0, 3, 1, 2, 4).reshape(np_, kp)[:ci, :co]
 
 
 # ------------------------------------------------------------------------------------------------ the launch plan
-def pointwise_fields(x, w, bias, in_scale, residual, out, m, hw, ci, co, kp, np_, act, img_stride=None, row_stride=None, off=0):
-    """The fields of capi.DetPointwise, which DetPointwise16 starts with too: m rows of ci channels onto co, written densely
-    unless the strides and the offset place them inside a larger output.  The tensors are the caller's to keep."""
-    ptrs = [None if t is None else t.data_ptr() for t in (x, w, bias, in_scale, residual, out)]
-    return (*ptrs, m, hw * co if img_stride is None else img_stride, co if row_stride is None else row_stride, off, hw, ci, co, kp, np_, act)
+def list_stem(ops: LaunchList, code: int, canvas, w, bias, out, B, H, W, co) -> None:
+    """The stem (3x3 / 2 conv + BN + swish) of the fp32 H x W canvas onto `out`, stored in the type of `code`."""
+    if code:
+        ops.add("stl_det_stem16", code, canvas, w, bias, out, B, H, W, co)
+    else:
+        ops.add("stl_det_stem", canvas, w, bias, out, B, H, W, co)
+
+
+def list_dwconv(ops: LaunchList, code: int, x, w, bias, y, B, h, c, k, s, act, partial=None) -> None:
+    """Depthwise k x k / s on the h x h map x -> y; 16-bit with ``partial``: also the squeeze-excitation pooling sums."""
+    if code:
+        ops.add("stl_det_dwconv16", code, x, w, bias, y, partial, B, h, h, c, k, s, act)
+    else:
+        ops.add("stl_det_dwconv", x, w, bias, y, B, h, h, c, k, s, act)
+
+
+def list_se(ops: LaunchList, code: int, x, part, nparts, B, hw, c, cse, w, scale) -> None:
+    """Squeeze-excitation gate ``scale`` [B, c] of the map x; w: its four weight pieces.  fp32 pools x itself, with `part` as
+    workspace (two launches); 16-bit reads the `nparts` pooling sums per image that the depthwise launch left in `part`."""
+    if code:
+        ops.add("stl_det_se16", part, B, hw, nparts, c, cse, *w, scale)
+    else:
+        ops.add("stl_det_se", x, B, hw, c, cse, *w, part, scale)
+
+
+def list_pointwise(ops: LaunchList, code: int, fields, out_f32, z=None) -> None:
+    """The 1x1 conv described by `fields` (``_Plan.pw_fields``); out_f32 (16-bit only): the output is fp32, not the type of `code`; z: the
+    training entry point, which also stores the pre-activation there."""
+    if code:
+        p, name, train = capi.DetPointwise16(*fields, code, int(out_f32)), "stl_det_pointwise16", "stl_det_pointwise16_train"
+    else:
+        p, name, train = capi.DetPointwise(*fields), "stl_det_pointwise", "stl_det_pointwise_train"
+    ops.add(*((name, p) if z is None else (train, p, z)))
+
+
+def list_fuse(ops: LaunchList, code: int, out, terms, wparam) -> None:
+    """The BiFPN node `out` [B, H, W, C] = fast-normalised sum of terms [(map, mode)] (wparam None: a plain resample)."""
+    f = capi.DetFuse()
+    f.B, f.H, f.W, f.C, f.nterms = out.shape[0], out.shape[1], out.shape[2], out.shape[3], len(terms)
+    for i, (t, mode) in enumerate(terms):
+        f.t[i] = capi.DetTerm(t.data_ptr(), mode, t.shape[1], t.shape[2], 0)
+    f.wparam = None if wparam is None else wparam.data_ptr()
+    f.out = out.data_ptr()
+    ops.keep_alive(out, *[t for t, _ in terms])   # the descriptor holds their addresses
+    if code:
+        ops.add("stl_det_fuse16", f, code)
+    else:
+        ops.add("stl_det_fuse", f)
 
 
 class _Plan:
@@ -333,17 +374,14 @@ class _Plan:
         self.wbuf, self.wbuf16 = m._wbuf, m._wbuf16
         self.adtype, self.code = COMPUTE_DTYPES[m.compute_dtype]
         self.h16 = self.code != 0
-        self.es = 2 if self.h16 else 4   # bytes per stored activation / pointwise weight
+        self.es = capi.DTYPES[self.code][0]   # bytes per stored activation / pointwise weight
         S = MAX_SIZE
         self.canvas = torch.empty(B, S, S, 3, device=dev)
         L = m._layout
         net = m.backbone_net.model
         H = (S + 1) // 2
         x = self._buf(B, H, H, net._conv_stem.conv.out_channels)
-        if self.h16:
-            self._add("stl_det_stem16", self.code, self.canvas, self._w(L["stem"][0]), self._w(L["stem"][1]), x, B, S, S, x.shape[3])
-        else:
-            self._add("stl_det_stem", self.canvas, self._w(L["stem"][0]), self._w(L["stem"][1]), x, B, S, S, x.shape[3])
+        list_stem(self.calls, self.code, self.canvas, self._w(L["stem"][0]), self._w(L["stem"][1]), x, B, S, S, x.shape[3])
         self._cost(2 * x.numel() * 27, 4 * self.canvas.numel() + self.es * x.numel())
         h = H
         feats, specs = [], net.specs
@@ -353,30 +391,27 @@ class _Plan:
             inp = x
             if b["e"] != 1:
                 y = self._buf(B, h, h, b["mid"])
-                self._pw(x, y, B, h * h, b["ci"], b["mid"], lay["expand"], act=1)
+                self._pw(x, y, h * h, b["ci"], b["mid"], lay["expand"], act=1)
                 x = y
             ho = (h + b["s"] - 1) // b["s"]
             y = self._buf(B, ho, ho, b["mid"])
             scale = torch.empty(B, b["mid"], device=dev)
-            se = lay["se"]
+            se = [self._w(o) for o in lay["se"]]
             if self.h16:   # the depthwise kernel writes the pooling sums: no pass over its output
                 nparts = capi.lib().stl_det_dw16_parts(ho * ho)
                 part = torch.empty(B * nparts * b["mid"], device=dev)
                 self._dw(x, y, lay["dw"][0], lay["dw"][1], h, b["mid"], b["k"], b["s"], 1, part)
                 h, x = ho, y
-                self._add("stl_det_se16", part, B, h * h, nparts, b["mid"], b["se"], self._w(se[0]), self._w(se[1]), self._w(se[2]),
-                           self._w(se[3]), scale)
+                list_se(self.calls, self.code, x, part, nparts, B, h * h, b["mid"], b["se"], se, scale)
                 self._cost(part.numel() + 4 * B * b["mid"] * b["se"], 4 * part.numel())
             else:
                 self._dw(x, y, lay["dw"][0], lay["dw"][1], h, b["mid"], b["k"], b["s"], 1)
                 h, x = ho, y
                 part = torch.empty(capi.lib().stl_det_se_workspace(B) * b["mid"], device=dev)
-                self._add("stl_det_se", x, B, h * h, b["mid"], b["se"], self._w(se[0]), self._w(se[1]), self._w(se[2]), self._w(se[3]),
-                           part, scale)
-                self.launches += 1
-                self._cost(x.numel() + 4 * B * b["mid"] * b["se"], 4 * x.numel())
+                list_se(self.calls, self.code, x, part, 0, B, h * h, b["mid"], b["se"], se, scale)
+                self._cost(x.numel() + 4 * B * b["mid"] * b["se"], 4 * x.numel(), launches=2)
             y = self._buf(B, h, h, b["co"])
-            self._pw(x, y, B, h * h, b["mid"], b["co"], lay["project"], act=0, in_scale=scale, residual=inp if b["skip"] else None)
+            self._pw(x, y, h * h, b["mid"], b["co"], lay["project"], act=0, in_scale=scale, residual=inp if b["skip"] else None)
             x = y
         feats.append((x, h))
         p3, p4, p5 = feats[-3:]
@@ -399,11 +434,11 @@ class _Plan:
                     d = self._buf(B, hh, hh, c)
                     self._dw(t, d, lay["dw"][i], None, hh, c, 3, 1, 0)
                     e = self._buf(B, hh, hh, c)
-                    self._pw(d, e, B, hh * hh, c, c, lay["pw"][li][i], act=1)
+                    self._pw(d, e, hh * hh, c, c, lay["pw"][li][i], act=1)
                     t = e
                 d = self._buf(B, hh, hh, c)
                 self._dw(t, d, lay["hdw"], None, hh, c, 3, 1, 0)
-                self._pw(d, out, B, hh * hh, c, 9 * k, lay["hpw"], act=act, img_stride=A * k, row_stride=9 * k, off=aoff * k)
+                self._pw(d, out, hh * hh, c, 9 * k, lay["hpw"], act=act, img_stride=A * k, row_stride=9 * k, off=aoff * k)
                 aoff += hh * hh * 9
 
     def _buf(self, B, h, w, c):
@@ -412,55 +447,42 @@ class _Plan:
     def _w(self, off):
         return None if off is None else self.wbuf[off:]
 
-    def _cost(self, flops, nbytes):
+    def _cost(self, flops, nbytes, launches=1):
+        """Count the entry just listed."""
         self.flops += int(flops)
         self.bytes += int(nbytes)
-
-    def _add(self, name, *args):
-        self.calls.add(name, *args)
-        self.launches += 1
+        self.launches += launches
 
     def _dw(self, x, y, w, bias, h, c, k, s, act, partial=None):
-        """Depthwise k x k / s on the h x h map x -> y; 16-bit with ``partial``: also the squeeze-excitation pooling sums."""
-        if self.h16:
-            self._add("stl_det_dwconv16", self.code, x, self._w(w), self._w(bias), y, partial, self.B, h, h, c, k, s, act)
-        else:
-            self._add("stl_det_dwconv", x, self._w(w), self._w(bias), y, self.B, h, h, c, k, s, act)
+        list_dwconv(self.calls, self.code, x, self._w(w), self._w(bias), y, self.B, h, c, k, s, act, partial)
         self._cost(2 * y.numel() * k * k, self.es * (x.numel() + y.numel()) + (0 if partial is None else 4 * partial.numel()))
 
-    def _pw(self, x, out, B, hw, ci, co, pk, act, in_scale=None, residual=None, img_stride=None, row_stride=None, off=0):
+    def pw_fields(self, x, out, hw, ci, co, pk, act, in_scale=None, residual=None, img_stride=None, row_stride=None, off=0):
+        """The fields of capi.DetPointwise, which DetPointwise16 starts with too, for the layer packed as pk = (w, bias, Kp, Np) in
+        this plan's weight buffers: the B x hw rows of ci channels onto co, written densely unless the strides and the offset
+        place them inside a larger output.  The tensors are the caller's to keep."""
         w, b, kp, np_ = pk
-        m = B * hw
-        common = pointwise_fields(x, (self.wbuf16 if self.h16 else self.wbuf)[w:], self._w(b), in_scale, residual, out, m, hw, ci, co,
-                                  kp, np_, act, img_stride, row_stride, off)
+        ptrs = [None if t is None else t.data_ptr() for t in (x, (self.wbuf16 if self.h16 else self.wbuf)[w:], self._w(b), in_scale, residual, out)]
+        return (*ptrs, self.B * hw, hw * co if img_stride is None else img_stride, co if row_stride is None else row_stride, off, hw,
+                ci, co, kp, np_, act)
+
+    def _pw(self, x, out, hw, ci, co, pk, act, in_scale=None, residual=None, **place):
+        m, (_, _, kp, np_) = self.B * hw, pk
         self.calls.keep_alive(x, out, in_scale, residual)   # the descriptor holds their addresses
-        if self.h16:
-            self._add("stl_det_pointwise16", capi.DetPointwise16(*common, self.code, 1 if out.dtype == torch.float32 else 0))
-            self._cost(2 * m * ci * co, self.es * (m * ci + kp * np_ + (m * co if residual is not None else 0)) + out.element_size() * m * co)
-        else:
-            self._add("stl_det_pointwise", capi.DetPointwise(*common))
-            self._cost(2 * m * ci * co, 4 * (m * ci + m * co * (2 if residual is not None else 1) + kp * np_))
+        list_pointwise(self.calls, self.code, self.pw_fields(x, out, hw, ci, co, pk, act, in_scale, residual, **place),
+                       out.dtype == torch.float32)
+        self._cost(2 * m * ci * co, self.es * (m * ci + kp * np_ + (m * co if residual is not None else 0)) + out.element_size() * m * co)
 
     def _fuse(self, out, terms, wparam):
-        f = capi.DetFuse()
-        f.B, f.H, f.W, f.C, f.nterms = out.shape[0], out.shape[1], out.shape[2], out.shape[3], len(terms)
-        for i, (t, mode) in enumerate(terms):
-            f.t[i] = capi.DetTerm(t.data_ptr(), mode, t.shape[1], t.shape[2], 0)
-        f.wparam = None if wparam is None else wparam.data_ptr()
-        f.out = out.data_ptr()
-        self.calls.keep_alive(out, *[t for t, _ in terms])   # the descriptor holds their addresses
+        list_fuse(self.calls, self.code, out, terms, wparam)
         self._cost(out.numel() * (2 * len(terms) + 4), self.es * (out.numel() + sum(t.numel() for t, _ in terms)))
-        if self.h16:
-            self._add("stl_det_fuse16", f, self.code)
-        else:
-            self._add("stl_det_fuse", f)
 
     def _sep(self, x, pk, h, c):
         """SeparableConvBlock: depthwise 3x3 (no bias) then 1x1 with bias and BN folded, no activation."""
         d = self._buf(self.B, h, h, c)
         self._dw(x, d, pk[0], None, h, c, 3, 1, 0)
         y = self._buf(self.B, h, h, c)
-        self._pw(d, y, self.B, h * h, c, c, pk[1], act=0)
+        self._pw(d, y, h * h, c, c, pk[1], act=0)
         return y
 
     def _bifpn(self, cell, lay, levels, p3, p4, p5, c):
@@ -469,7 +491,7 @@ class _Plan:
         if levels is None:
             (x3, h3), (x4, h4), (x5, h5) = p3, p4, p5
             t = self._buf(B, h5, h5, c)
-            self._pw(x5, t, B, h5 * h5, x5.shape[3], c, lay["p5_to_p6"], act=0)
+            self._pw(x5, t, h5 * h5, x5.shape[3], c, lay["p5_to_p6"], act=0)
             h6, h7 = (h5 + 1) // 2, (h5 + 3) // 4
             p6 = self._buf(B, h6, h6, c)
             self._fuse(p6, [(t, 2)], None)
@@ -478,7 +500,7 @@ class _Plan:
             ins = []
             for (xx, hh), key in ((p3, "p3_down_channel"), (p4, "p4_down_channel"), (p5, "p5_down_channel")):
                 y = self._buf(B, hh, hh, c)
-                self._pw(xx, y, B, hh * hh, xx.shape[3], c, lay[key], act=0)
+                self._pw(xx, y, hh * hh, xx.shape[3], c, lay[key], act=0)
                 ins.append(y)
             p3_in, p4_in, p5_in = ins
             p6_in, p7_in = p6, p7
@@ -498,7 +520,7 @@ class _Plan:
             ins = []
             for (xx, hh), key in ((p4, "p4_down_channel_2"), (p5, "p5_down_channel_2")):
                 y = self._buf(B, hh, hh, c)
-                self._pw(xx, y, B, hh * hh, xx.shape[3], c, lay[key], act=0)
+                self._pw(xx, y, hh * hh, xx.shape[3], c, lay[key], act=0)
                 ins.append(y)
             p4_in, p5_in = ins
         p4_out = node("conv4_down", "p4_w2", [(p4_in, 0), (p4_up, 0), (p3_out, 2)], hs[1])

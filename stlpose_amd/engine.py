@@ -33,7 +33,7 @@ MOMENTUM = 0.1   # reference HRnet.py:23 (fuse/transition BNs use the default, a
 
 
 def _esz(dtype: int) -> int:
-    return 4 if (dtype & 0xff) == capi.F32 else 2
+    return capi.DTYPES[dtype & 0xff][0]
 
 
 def choose_tile(B: int, Ho: int, Wo: int, stride: int, ks: int, esz: int, bn_cols: int = 64,

@@ -10,7 +10,8 @@ MI355X-first: input and target run as ONE batch of 2B through the implicit-GEMM 
 fused into the patch kernel) so that it is a 1x1 conv with K = 32, and each slice's L1 is a
 two-level fp64 reduction.  Forward only, like the reference (its VGG is frozen and never
 back-propagated through in-tree).  The trunk's weight packing (``ready``) and launch plan (``Trunk``)
-serve the VGG19 losses of ``vgg19_style.py`` as well.
+serve the VGG19 losses of ``vgg19_style.py`` as well; ``pack_convs``, ``weight_table``, ``prep_weights``
+and ``list_conv`` under them are every conv trunk's, AdaIN's (``adain.py``) included.
 
 The reference takes the weights from ``torchvision.models.vgg16(pretrained=True)`` (a download);
 here they come from a state_dict with the reference module's own key names
@@ -45,32 +46,73 @@ def dtype_code(name: str) -> int:
     return capi.BF16 if name.lower() in ("bf16", "bfloat16") else capi.F32
 
 
-def add_conv(parent: nn.Module, idx: int, ci: int, co: int) -> nn.Module:
-    """Register a frozen 3x3 conv's ``weight`` and ``bias`` as ``parent.<idx>``; returns the leaf."""
+def add_conv(parent: nn.Module, idx: int, ci: int, co: int, ks: int = 3) -> nn.Module:
+    """Register a frozen ks x ks conv's ``weight`` and ``bias`` as ``parent.<idx>``; returns the leaf."""
     leaf = nn.Module()
-    leaf.register_parameter("weight", nn.Parameter(torch.zeros(co, ci, 3, 3), requires_grad=False))
+    leaf.register_parameter("weight", nn.Parameter(torch.zeros(co, ci, ks, ks), requires_grad=False))
     leaf.register_parameter("bias", nn.Parameter(torch.zeros(co), requires_grad=False))
     parent.add_module(str(idx), leaf)
     return leaf
 
 
+def pack_convs(convs, dev):
+    """[(weight, bias)] in launch order -> (``w_flat``, ``bias_flat``: fp32 on `dev`; ``bias_off``: each conv's first bias)."""
+    bias_off, off = [], 0
+    for _, b in convs:
+        bias_off.append(off)
+        off += b.numel()
+    w_flat = torch.cat([w.detach().reshape(-1).float() for w, _ in convs]).to(dev).contiguous()
+    return w_flat, torch.cat([b.detach().float() for _, b in convs]).to(dev).contiguous(), bias_off
+
+
 def ready(mod: nn.Module, dev) -> None:
-    """Move a VGG loss to `dev` and pack the convs of ``mod._convs`` there in layout order: ``w_flat`` and ``bias_flat``
-    (fp32), ``bias_off`` (each conv's first bias).  A repack drops ``mod._plans``: their launches point into the old buffers."""
+    """Move a VGG loss to `dev` and pack the convs of ``mod._convs`` there in layout order (``pack_convs``).  A repack drops
+    ``mod._plans``: their launches point into the old buffers."""
     if mod.mean.device != dev:
         mod.to(dev)
     if mod._flat_dev != dev:
-        ws, bs, mod.bias_off = [], [], []
-        off = 0
-        for leaf in mod._convs:
-            ws.append(leaf.weight.detach().reshape(-1).float())
-            bs.append(leaf.bias.detach().float())
-            mod.bias_off.append(off)
-            off += leaf.bias.numel()
-        mod.w_flat = torch.cat(ws).to(dev).contiguous()
-        mod.bias_flat = torch.cat(bs).to(dev).contiguous()
+        mod.w_flat, mod.bias_flat, mod.bias_off = pack_convs([(leaf.weight, leaf.bias) for leaf in mod._convs], dev)
         mod._flat_dev = dev
         mod._plans.clear()
+
+
+def weight_table(rows, grad: bool = False):
+    """The ``capi.WPrep`` table of the 3x3 convs ``rows`` = [(cin, cout)] packed by ``pack_convs`` -> (table, elements of the
+    kernel-layout buffer ``wk``, blocks of stl_weight_prep).  The first conv is a 1x1 conv on 32-wide 3x3 patches ([Co][32],
+    data gradient [32][Co]).  grad: ``wk`` also holds the data-gradient layouts [Ci][flipped tap][Co] (``bwd_off``): the
+    forward layouts' sizes, in the same order, behind them."""
+    tab = (capi.WPrep * len(rows))()
+    src = off = blk = 0
+    for i, (ci, co) in enumerate(rows):
+        patch = i == 0
+        cip, kk = (32, 1) if patch else (ci, 9)
+        e = tab[i]
+        e.src_off, e.fwd_off, e.bwd_off = src, off, -1
+        e.Co, e.Ci, e.ks, e.Cip, e.patch, e.blk0 = co, ci, 3, cip, int(patch), blk
+        src += co * ci * 9
+        off += co * kk * cip
+        blk += math.ceil(co * ci * 9 / 1024)
+    if grad:
+        for e in tab:
+            e.bwd_off = off + e.fwd_off
+        off *= 2
+    return tab, off, blk
+
+
+def prep_weights(dt: int, w_flat, wk, wtab_dev, n: int, blocks: int, stream: int) -> None:
+    """``w_flat`` -> the kernel layouts of the table's `n` convs in ``wk``."""
+    capi.call("stl_weight_prep", dt, w_flat.data_ptr(), wk.data_ptr(), wtab_dev.data_ptr(), n, blocks, stream)
+
+
+def list_conv(ops: LaunchList, dt: int, B, h, w, ci, co, ks, src, wptr, out, bias=0, out_relu=0, addend=0, mask_z=0) -> None:
+    """List a stride-1 'same' conv of the NHWC map at `src` onto `out` in `ops`."""
+    p = capi.Conv()
+    p.dtype, p.B, p.Hi, p.Wi, p.Ci, p.Ho, p.Wo, p.Co = dt, B, h, w, ci, h, w, co
+    p.ks, p.stride, p.shape = ks, 1, -1
+    p.src.x, p.src.mode = src, capi.SRC_PLAIN
+    p.w, p.out, p.bias, p.out_relu, p.addend, p.mask_z = wptr, out, bias, out_relu, addend, mask_z
+    capi.call("stl_conv_plan", C.byref(p))
+    ops.add("stl_conv_forward", p)
 
 
 class Trunk:
@@ -84,30 +126,13 @@ class Trunk:
     def __init__(self, mod: nn.Module, rows, nb: int, H: int, W: int, dev, hook, grad: bool = False):
         self.ops = LaunchList()
         self.keep, self.acts, self.dims = self.ops.keep, [], []   # acts, dims: per conv its output [nb, h, w, co], (h, w, co)
-        self.dt, self.esz = mod.dtype, (2 if mod.dtype == capi.BF16 else 4)
-        self.tdt = torch.bfloat16 if self.dt == capi.BF16 else torch.float32
+        self.dt = mod.dtype
+        self.esz, self.tdt = capi.DTYPES[self.dt]
         self.w_flat = mod.w_flat
         self.img = torch.zeros(nb, 3, H, W, device=dev)
-        # weights in kernel layout + table; conv1_1 is a 1x1 conv on 32-wide 3x3 patches ([Co][32], data gradient [32][Co])
-        self.nconv = len(rows)
-        self.tab = tab = (capi.WPrep * self.nconv)()
-        src = off = blk = 0
-        for i, (ci, co, _) in enumerate(rows):
-            patch = i == 0
-            cip, kk = (32, 1) if patch else (ci, 9)
-            e = tab[i]
-            e.src_off, e.fwd_off, e.bwd_off = src, off, -1
-            e.Co, e.Ci, e.ks, e.Cip, e.patch, e.blk0 = co, ci, 3, cip, int(patch), blk
-            src += co * ci * 9
-            off += co * kk * cip
-            blk += math.ceil(co * ci * 9 / 1024)
-        if grad:   # [Ci][flipped tap][Co]: the forward layouts' sizes, in the same order, behind them
-            for e in tab:
-                e.bwd_off = off + e.fwd_off
-            off *= 2
-        self.wk = torch.zeros(off, dtype=self.tdt, device=dev)
-        self.wtab = torch.frombuffer(bytearray(bytes(tab)), dtype=torch.uint8).clone().to(dev)
-        self.wblocks = blk
+        self.tab, wk_elems, self.wblocks = weight_table([row[:2] for row in rows], grad)
+        self.wk = torch.zeros(wk_elems, dtype=self.tdt, device=dev)
+        self.wtab = torch.frombuffer(bytearray(bytes(self.tab)), dtype=torch.uint8).clone().to(dev)
 
         def act(b, h, w, c):
             t = torch.empty(b * h * w * c * self.esz, dtype=torch.uint8, device=dev)
@@ -123,27 +148,16 @@ class Trunk:
                 self.ops.add("stl_maxpool2x2", self.dt, x.data_ptr(), y.data_ptr(), nb, h, w, c)
                 x, h, w = y, h // 2, w // 2
             y = act(nb, h, w, co)
-            self.conv(self.ops, nb, h, w, c, co, 1 if i == 0 else 3, x.data_ptr(), self.wk.data_ptr() + tab[i].fwd_off * self.esz,
+            list_conv(self.ops, self.dt, nb, h, w, c, co, 1 if i == 0 else 3, x.data_ptr(), self.wk.data_ptr() + self.tab[i].fwd_off * self.esz,
                       y.data_ptr(), bias=mod.bias_flat.data_ptr() + 4 * mod.bias_off[i], out_relu=1)
             x, c = y, co
             self.acts.append(y)
             self.dims.append((h, w, c))
             hook(self, i)
 
-    def conv(self, ops, B, h, w, ci, co, ks, src, wptr, out, bias=0, out_relu=0, addend=0, mask_z=0) -> None:
-        """List a stride-1 'same' conv of the NHWC map at `src` onto `out` in the LaunchList `ops` (needs ``self.dt`` only)."""
-        p = capi.Conv()
-        p.dtype, p.B, p.Hi, p.Wi, p.Ci, p.Ho, p.Wo, p.Co = self.dt, B, h, w, ci, h, w, co
-        p.ks, p.stride, p.shape = ks, 1, -1
-        p.src.x, p.src.mode = src, capi.SRC_PLAIN
-        p.w, p.out, p.bias, p.out_relu, p.addend, p.mask_z = wptr, out, bias, out_relu, addend, mask_z
-        capi.call("stl_conv_plan", C.byref(p))
-        ops.add("stl_conv_forward", p)
-
     def prep_weights(self, st) -> None:
         """``w_flat`` -> the kernel layouts in ``wk``."""
-        capi.call("stl_weight_prep", self.dt, self.w_flat.data_ptr(), self.wk.data_ptr(), self.wtab.data_ptr(), self.nconv,
-                  self.wblocks, st)
+        prep_weights(self.dt, self.w_flat, self.wk, self.wtab, len(self.tab), self.wblocks, st)
 
 
 class VGGPerceptualLoss(nn.Module):

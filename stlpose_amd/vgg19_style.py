@@ -31,7 +31,7 @@ import torch.nn as nn
 
 from . import capi
 from .launch import LaunchList
-from .vgg import Trunk, add_conv, dtype_code, ready
+from .vgg import Trunk, add_conv, dtype_code, list_conv, ready
 
 # (features index, cin, cout, 2x2 max-pool in front): torchvision VGG19 "E" up to conv5_1
 VGG19_LAYOUT = [(0, 3, 64, False), (2, 64, 64, False), (5, 64, 128, True), (7, 128, 128, False), (10, 128, 256, True),
@@ -135,22 +135,22 @@ class StylePlan:
                 self.gw[i] = wgt
                 out = other(h, w, g)
                 for b in range(B):
-                    t.conv(self.bwd_ops, 1, h, w, c, c, 1, f + b * pix, wgt[b].data_ptr(), out + b * pix,
-                           addend=(g + b * pix) if g is not None else 0, mask_z=f + b * pix)
+                    list_conv(self.bwd_ops, dt, 1, h, w, c, c, 1, f + b * pix, wgt[b].data_ptr(), out + b * pix,
+                              addend=(g + b * pix) if g is not None else 0, mask_z=f + b * pix)
                 g = out
             elif i == CONTENT_TAP:   # + wc * 2 (F_x - F_c) / n, then the ReLU mask, in place
                 self.bwd_ops.add("stl_l2_backward", dt, f, self.ctarget_ptr, g, B * h * w * c, self.cscale.data_ptr(), 1)
             _, ci, co, pool = VGG19_LAYOUT[i]
             out = other(h, w, g)
             if i == 0:   # conv1_1: 1x1 onto the 32-wide patches, then the patch adjoint (with 1 / std) to the NCHW image
-                t.conv(self.bwd_ops, B, h, w, co, 32, 1, g, t.wk.data_ptr() + t.tab[0].bwd_off * esz, out)
+                list_conv(self.bwd_ops, dt, B, h, w, co, 32, 1, g, t.wk.data_ptr() + t.tab[0].bwd_off * esz, out)
                 self.bwd_ops.add("stl_patch3x3_backward", dt, out, self.dimg.data_ptr(), B, self.H, self.W, 1, mod.std.data_ptr())
                 break
             hp, wp, cp = t.dims[i - 1]
             fp = t.acts[i - 1].data_ptr()
             masked = i - 1 not in STYLE_TAPS and i - 1 != CONTENT_TAP   # else the tap masks after adding its own term
-            t.conv(self.bwd_ops, B, h, w, co, ci, 3, g, t.wk.data_ptr() + t.tab[i].bwd_off * esz, out,
-                   mask_z=fp if masked and not pool else 0)
+            list_conv(self.bwd_ops, dt, B, h, w, co, ci, 3, g, t.wk.data_ptr() + t.tab[i].bwd_off * esz, out,
+                      mask_z=fp if masked and not pool else 0)
             if pool:
                 dst = other(hp, wp, None)
                 self.bwd_ops.add("stl_maxpool2x2_backward", dt, fp, out, dst, B, hp, wp, cp, int(masked))

@@ -91,7 +91,7 @@ def test_slices_selection_len_and_names(built_lib):
         sel.run(0, 1, 2)
 
 
-@pytest.mark.parametrize("model", ["vgg16", "vgg19", "adain", "d0.fp32", "d0.bf16"])
+@pytest.mark.parametrize("model", ["vgg16", "vgg19", "adain", "d0.fp32", "d0.bf16", "d0.f16"])
 def test_plans_are_the_recorded_ones(model, built_lib):
     """Every list holds the same ordered entry points with the same arguments (tests/launch_plans.py: scalars, descriptor fields,
     which pointers are null) as on the commit plans.json was recorded from, and the detector's counters are the same."""

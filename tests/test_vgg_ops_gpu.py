@@ -1,6 +1,6 @@
 """GPU: the small ops of the VGG path through the C ABI, each against plain torch in high precision: stl_maxpool2x2,
 stl_bilinear_nchw, stl_l1_partial / stl_l2_partial with stl_sum_partials, stl_patch3x3 (forward), stl_nchw_to_nhwc /
-stl_nhwc_to_nchw, and stl_conv_forward as Trunk.conv builds it (planned, plain source, bias + ReLU) up to 512 channels.
+stl_nhwc_to_nchw, and stl_conv_forward as vgg.list_conv builds it (planned, plain source, bias + ReLU) up to 512 channels.
 Every output is prefilled with NaN (every element must be written) and every op runs twice (bit-equal results).
 
 Bounds: tests/vgg_layers_ref.py.  Ops that only move or select values are held bit for bit; arithmetic in fp32 to
@@ -202,7 +202,7 @@ def test_layout_ops_are_permute(B, Cc, H, W, dt):
     assert torch.equal(to_nchw(y.cuda()).cpu(), y.float().permute(0, 3, 1, 2))
 
 
-# ------------------------------------------------------------------------------------------------ stl_conv_forward as Trunk.conv builds it
+# ------------------------------------------------------------------------------------------------ stl_conv_forward as vgg.list_conv builds it
 @pytest.mark.parametrize("dt", ["fp32", "bf16"])
 @pytest.mark.parametrize("B,H,W,Ci,Co", [(1, 20, 14, 512, 512), (2, 9, 7, 256, 512), (1, 33, 17, 64, 128), (2, 5, 4, 512, 512)])
 def test_conv_bias_relu_as_the_trunk_plans_it(B, H, W, Ci, Co, dt):
