@@ -301,6 +301,29 @@ int stl_sgd_step(float* p, const float* g, float* mom, int64_t n, const float* h
  * is NOT reproduced (exact float bilinear): parity for that rounding is unpinned (cv2 absent). */
 int stl_affine_crop(const uint8_t* src, const int64_t* src_off, const int32_t* src_hw, const float* minv, const int32_t* flip,
                     float* out, int B, int Ho, int Wo, const float* mean3, const float* std3, void* stream);
+/* The augmentation arithmetic of a training batch for COCO persons (17 joints; reference data/JointsDataset.py:164-200), one launch,
+ * one thread per person, no allocation and no host read (pose_batch.hip).  Person tables of N rows: joints_tab, vis_tab fp64
+ * [N, 17, 3]; center_tab, scale_tab fp32 [N, 2] (scale in units of 200 px); width_tab int32 [N]: the width of the person's source
+ * image.  index int64 [B]: the table row of each person of the batch (a row may repeat); draws fp64 [B, 6] = u_half, n_half,
+ * n_scale, u_rot, n_rot, u_flip (u: uniform in [0, 1), n: standard normal), made by the caller.  With train == 0 no draw is read:
+ * rot 0, no flip, centre and scale as stored.  With train != 0, in this order:
+ *   half body   iff sum(vis[:, 0]) > num_joints_half_body and u_half < prob_half_body: the visible joints 0 .. 10 iff n_half < 0.5
+ *               and more than two of them are visible, else the visible joints 11 .. 16; with two or more selected, centre = their
+ *               fp32 mean (running sum in joint order / count) and scale = their extent widened to Wo / Ho, / 200 * 1.5, all fp32;
+ *   scale       (double)scale * clip(n_scale * scale_factor + 1, 1 - scale_factor, 1 + scale_factor);
+ *   rot         clip(n_rot * rot_factor, -2 rot_factor, 2 rot_factor) iff u_rot <= 0.6, else 0 (degrees);
+ *   flip        iff flip_enabled and u_flip <= 0.5: centre x = width - x - 1 (fp64), joints mirrored the same way, left / right
+ *               pairs exchanged, joints multiplied by their visibility.
+ * Outputs: center, scale fp64 [B, 2]; rot fp64 [B]; flip int32 [B]; trans fp64 [B, 2, 3]: the map image -> (Wo, Ho) crop through
+ * the reference's three control points (rounded to fp32 as there; the fit itself is exact to the last digit of every entry); minv
+ * fp32 [B, 6]: its inverse, what stl_affine_crop takes together with flip; joints, joints_vis fp64 [B, 17, 3]: the visible joints
+ * through trans as (x * t00 + y * t01) + t02; joints_xy fp32 [B, 17, 2] and vis0 fp32 [B, 17]: what stl_gaussian_targets takes.
+ * An index outside [0, N) reads nothing: that person's fp64 results are NaN, its flip, minv, visibility and fp32 joints 0. */
+int stl_pose_augment(const double* joints_tab, const double* vis_tab, const float* center_tab, const float* scale_tab,
+                     const int32_t* width_tab, int64_t N, const int64_t* index, const double* draws, int B, int train,
+                     int flip_enabled, double scale_factor, double rot_factor, int num_joints_half_body, double prob_half_body,
+                     int Wo, int Ho, double* center, double* scale, double* rot, int32_t* flip, double* trans, float* minv,
+                     double* joints, double* joints_vis, float* joints_xy, float* vis0, void* stream);
 /* VGG perceptual path (reference lib/loss.py:17-58). */
 int stl_maxpool2x2(int dtype, const void* x, void* out, int B, int H, int W, int C, void* stream);
 int stl_l1_partial(int dtype, const void* a, const void* b, int64_t n, double* partial, int nblk,

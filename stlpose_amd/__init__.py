@@ -22,3 +22,4 @@ from .detection_eval import box_ap, CocoEvaluator, DetectorEvaluator  # noqa: F4
 from .keypoint_eval import keypoint_ap, keypoint_ap_tables, rescore_and_nms_device, KeypointGroundTruth, PoseResults  # noqa: F401,E402
 from .eval_tail import EvalTables  # noqa: F401,E402
 from .pose_parsing import pck_from_coords  # noqa: F401,E402
+from .pose_data import coco_person_db, epoch_indices, ResidentImages, StreamedImages, PoseBatchLoader, PersonDB  # noqa: F401,E402

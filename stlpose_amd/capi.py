@@ -212,6 +212,8 @@ SIGNATURES = {
     "stl_adam_step": [vp, vp, vp, vp, i64, vp, vp, vp, vp],
     "stl_sgd_step": [vp, vp, vp, i64, vp, vp, vp, vp],
     "stl_affine_crop": [vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp],
+    "stl_pose_augment": [vp, vp, vp, vp, vp, i64, vp, vp, i32, i32, i32, C.c_double, C.c_double, i32, C.c_double, i32, i32,
+                         vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
     "stl_maxpool2x2": [i32, vp, vp, i32, i32, i32, i32, vp],
     "stl_l1_partial": [i32, vp, vp, i64, vp, i32, vp],
     "stl_l2_partial": [i32, vp, vp, i64, vp, i32, vp],

@@ -207,6 +207,58 @@ _define("affine_crop(Tensor src, Tensor src_off, Tensor src_hw, Tensor minv, Ten
         _crop, lambda s, o, hw, m, f, ho, wo, mean, std: s.new_empty(hw.shape[0], 3, ho, wo, dtype=torch.float32))
 
 
+def _pose_augment(joints_tab, vis_tab, center_tab, scale_tab, width_tab, index, draws, train: bool, flip_enabled: bool, scale_factor: float,
+                  rot_factor: float, num_joints_half_body: int, prob_half_body: float, wo: int, ho: int):
+    """One launch of stl_pose_augment; every shape, dtype and device the kernel relies on is checked here, nothing is read back."""
+    op = "pose_augment"
+    j = capi.POSE_JOINTS
+    if joints_tab.dim() != 3 or tuple(joints_tab.shape[1:]) != (j, 3):
+        raise ValueError(f"stlpose {op}: joints must be [N, {j}, 3]; the kernel's flip pairs and upper-body ids are COCO's {j} joints, got "
+                         f"{tuple(joints_tab.shape)}")
+    n = _table(op, "joints", joints_tab, torch.float64, "N", tail=(j, 3))
+    if n < 1:
+        raise ValueError(f"stlpose {op}: an empty person table")
+    _table(op, "joints_vis", vis_tab, torch.float64, "N", n, tail=(j, 3))
+    _table(op, "center", center_tab, torch.float32, "N", n, tail=(2,))
+    _table(op, "scale", scale_tab, torch.float32, "N", n, tail=(2,))
+    _table(op, "width", width_tab, torch.int32, "N", n)
+    b = _table(op, "index", index, torch.int64, "B")
+    _table(op, "draws", draws, torch.float64, "B", b, tail=(6,))
+    if not joints_tab.is_cuda:
+        raise RuntimeError(f"stlpose {op}: the person tables must be on the GPU")
+    dev = joints_tab.device
+    tabs = (("joints_vis", vis_tab), ("center", center_tab), ("scale", scale_tab), ("width", width_tab), ("index", index), ("draws", draws))
+    _same_device(tabs, dev)
+    for name, t in (("joints", joints_tab),) + tabs:
+        if not t.is_contiguous():
+            raise ValueError(f"stlpose {op}: {name} must be contiguous")
+    if wo < 1 or ho < 1 or scale_factor < 0 or rot_factor < 0:
+        raise ValueError(f"stlpose {op}: crop {wo} x {ho}, scale_factor {scale_factor}, rot_factor {rot_factor}")
+    f64 = dict(dtype=torch.float64, device=dev)
+    out = (torch.empty(b, 2, **f64), torch.empty(b, 2, **f64), torch.empty(b, **f64), torch.empty(b, dtype=torch.int32, device=dev),
+           torch.empty(b, 2, 3, **f64), torch.empty(b, 6, dtype=torch.float32, device=dev), torch.empty(b, j, 3, **f64),
+           torch.empty(b, j, 3, **f64), torch.empty(b, j, 2, dtype=torch.float32, device=dev),
+           torch.empty(b, j, dtype=torch.float32, device=dev))
+    capi.call("stl_pose_augment", joints_tab.data_ptr(), vis_tab.data_ptr(), center_tab.data_ptr(), scale_tab.data_ptr(),
+              width_tab.data_ptr(), n, index.data_ptr(), draws.data_ptr(), b, int(bool(train)), int(bool(flip_enabled)),
+              float(scale_factor), float(rot_factor), int(num_joints_half_body), float(prob_half_body), int(wo), int(ho),
+              *(t.data_ptr() for t in out), _st())
+    return out
+
+
+def _pose_augment_fake(jt, vt, ct, st, wt, index, draws, train, flip_enabled, sf, rf, nh, ph, wo, ho):
+    b, j = index.shape[0], jt.shape[1]
+    return (jt.new_empty(b, 2), jt.new_empty(b, 2), jt.new_empty(b), jt.new_empty(b, dtype=torch.int32), jt.new_empty(b, 2, 3),
+            jt.new_empty(b, 6, dtype=torch.float32), jt.new_empty(b, j, 3), jt.new_empty(b, j, 3),
+            jt.new_empty(b, j, 2, dtype=torch.float32), jt.new_empty(b, j, dtype=torch.float32))
+
+
+# center, scale, rot, flip, trans, minv, joints, joints_vis, joints_xy (fp32), vis0 (fp32): stl_pose_augment in include/stlpose_hip.h
+_define("pose_augment(Tensor joints, Tensor joints_vis, Tensor center, Tensor scale, Tensor width, Tensor index, Tensor draws, bool train, "
+        "bool flip_enabled, float scale_factor, float rot_factor, int num_joints_half_body, float prob_half_body, int wo, int ho) "
+        "-> (Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)", _pose_augment, _pose_augment_fake)
+
+
 # ------------------------------------------------------------------ whole network (models/HRnet.py:433-468 + its autograd backward)
 def register_engine(eng) -> int:
     h = id(eng)
@@ -803,4 +855,4 @@ _define("oks_ap_match(Tensor kpts, Tensor scores, Tensor? area, Tensor det_offse
 OPS = ["person_mse", "heatmap_argmax", "final_preds", "flip_merge", "flip_merge_backward", "gaussian_targets", "affine_crop",
        "hrnet_forward", "hrnet_backward", "hrnet_backward_input", "pose_vectors", "pose_distances", "pose_topk", "pose_rank", "pose_rank_any",
        "box_select", "heatmap_resize_argmax", "det_decode", "det_nms", "det_loss", "box_ap_match", "box_ap_accumulate",
-       "pose_rescore_nms", "oks_ap_match", "eval_tail", "eval_affine"]
+       "pose_rescore_nms", "oks_ap_match", "eval_tail", "eval_affine", "pose_augment"]

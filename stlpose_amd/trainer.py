@@ -16,8 +16,9 @@ What is kept from the reference so that its experiment directories stay intercha
     ``02_train.py:166`` / ``model_setup.py:200-205``), ``optimizer_state_dict`` in
     ``torch.optim`` layout (per-parameter ``step`` / ``exp_avg`` / ``exp_avg_sq`` or
     ``momentum_buffer``) and ``scheduler_state_dict``.
-Data loading, augmentation and TensorBoard stay the caller's: the
-loaders are any iterables of ``(imgs, target, target_weight, metadata)`` like the reference's.
+TensorBoard stays the caller's.  The loaders are any iterables of
+``(imgs, target, target_weight, metadata)`` like the reference's; ``pose_data.PoseBatchLoader`` builds such
+batches on the device from COCO person annotations.
 """
 from __future__ import annotations
 
