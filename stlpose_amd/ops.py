@@ -352,7 +352,7 @@ def _ptr(t):
 
 
 def _pose_vectors(joints: torch.Tensor, approach: str, normalize: bool) -> torch.Tensor:
-    if joints.dim() != 3 or joints.shape[1] != 17 or joints.shape[2] < 2:
+    if joints.dim() != 3 or joints.shape[1] != capi.POSE_JOINTS or joints.shape[2] < 2:
         raise RuntimeError(f"stlpose pose_vectors: joints must be [N, 17, C >= 2], got {tuple(joints.shape)}")
     j = joints.contiguous().float()
     n = j.shape[0]
