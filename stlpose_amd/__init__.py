@@ -19,6 +19,7 @@ from .topdown import detect_poses  # noqa: F401,E402
 from .adain import AdaINStylizer  # noqa: F401,E402
 from .styled_coco import create_styled_dataset  # noqa: F401,E402
 from .detection_eval import box_ap, CocoEvaluator, DetectorEvaluator  # noqa: F401,E402
+from .detections import Detections, DetectionStore  # noqa: F401,E402
 from .keypoint_eval import keypoint_ap, keypoint_ap_tables, rescore_and_nms_device, KeypointGroundTruth, PoseResults  # noqa: F401,E402
 from .eval_tail import EvalTables  # noqa: F401,E402
 from .pose_parsing import pck_from_coords  # noqa: F401,E402

@@ -45,6 +45,8 @@ INT64_FUNCS = tuple(n for n, r in RESTYPES.items() if r is C.c_int64)     # int6
 STRING_FUNCS = tuple(n for n, r in RESTYPES.items() if r is C.c_char_p)   # const char* f(void)
 # include/stlpose_hip_debug.h: exported by the stamped diagnostic build only (STLPOSE_HIP_LIB=.../libstlpose_hip_stamps.so)
 DEBUG_SIGNATURES = Header(os.path.join(INCLUDE, "stlpose_hip_debug.h")).signatures
+# include/stlpose_hip_detections.h: the detector's device tail (csrc/detections.hip), part of the product library
+DETECTIONS = Header(os.path.join(INCLUDE, "stlpose_hip_detections.h"))
 
 DTYPES = {F32: (4, torch.float32), BF16: (2, torch.bfloat16), F16: (2, torch.float16)}   # code -> (bytes per element, torch dtype)
 
@@ -83,6 +85,9 @@ def lib() -> C.CDLL:
         for name, args in SIGNATURES.items():
             fn = getattr(l, name)  # AttributeError if the library lacks a symbol of the header
             fn.argtypes, fn.restype = args, RESTYPES[name]
+        for name, args in DETECTIONS.signatures.items():
+            fn = getattr(l, name)
+            fn.argtypes, fn.restype = args, DETECTIONS.restypes[name]
         for name, args in DEBUG_SIGNATURES.items():
             if hasattr(l, name):
                 getattr(l, name).argtypes, getattr(l, name).restype = args, C.c_int

@@ -22,6 +22,7 @@ import numpy as np
 import torch
 
 from . import capi
+from .detections import Detections, DetectionStore
 from .coco_tables import REC_THRS, device_of, match_and_accumulate, mean_valid as mean, offsets_of, segment_rows, take_images
 
 IOU_THRS = np.linspace(.5, 0.95, 10)
@@ -140,7 +141,7 @@ class CocoEvaluator:
     pycocotools ``COCO``); it is uploaded once, here.  The categories are the dataset's ``categories`` where it has them, else every
     category the annotations or the predictions name."""
 
-    def __init__(self, coco_gt, iou_types=("bbox",), device=None):
+    def __init__(self, coco_gt, iou_types=("bbox",), device=None, store_capacity: int = 1 << 20):
         iou_types = [iou_types] if isinstance(iou_types, str) else list(iou_types)
         for t in iou_types:
             if t != "bbox":
@@ -154,12 +155,25 @@ class CocoEvaluator:
         self.img_ids: List[int] = []
         self._chunks: list = []    # per update: (image ids, rows per image, boxes xywh f64, scores f32, labels i64) on the device
         self._tables = None
+        self.store_capacity = int(store_capacity)   # rows of the DetectionStore that update(image_ids, Detections) fills
+        self._store: Optional[DetectionStore] = None
 
     # -- collecting
-    def update(self, predictions: Dict[int, Dict[str, torch.Tensor]]) -> None:
+    def update(self, predictions, detections: Optional[Detections] = None) -> None:
         """predictions: {image_id: {"boxes" [n, 4] xyxy, "labels" [n], "scores" [n]}}, CPU or device tensors.  The boxes become xywh
         as the reference's convert_to_xywh makes them (the subtraction in the tensor's own dtype) and stay on the device; nothing
-        here waits for the device."""
+        here waits for the device.  ``update(image_ids, detections)`` takes a batch as ``Detections`` (forward(output="device"))
+        with one id per image: one launch into a ``DetectionStore`` of ``store_capacity`` rows."""
+        if detections is not None or isinstance(predictions, Detections):
+            if not isinstance(detections, Detections):
+                raise TypeError("CocoEvaluator.update: (image_ids, Detections) or {image_id: prediction}")
+            if self._store is None:
+                self._store = DetectionStore(self.store_capacity, self.device)
+            ids = [int(i) for i in predictions]
+            self._store.append(ids, detections)
+            self.img_ids.extend(sorted(set(ids)))
+            self._tables = None
+            return
         ids, cnt, bs, ss, ls = [], [], [], [], []
         for image_id, p in predictions.items():
             b = torch.as_tensor(p["boxes"]).reshape(-1, 4)
@@ -184,10 +198,13 @@ class CocoEvaluator:
     def synchronize_between_processes(self, process_group=None) -> None:
         """Builds the evaluation tables: the updates concatenated (with a process group: all-gathered first, ranks in order),
         each image id once -- its first occurrence, as ``np.unique`` picks it in the reference's merge -- and ascending."""
-        if self._chunks:
-            ids = np.concatenate([c[0] for c in self._chunks])
-            cnt = np.concatenate([c[1] for c in self._chunks])
-            boxes, scores, labels = (torch.cat([c[i] for c in self._chunks]) for i in (2, 3, 4))
+        chunks = list(self._chunks)   # the dict updates in order, then the store's batches in order
+        if self._store is not None and self._store.num_slots:
+            chunks.append(self._store.finish())
+        if chunks:
+            ids = np.concatenate([c[0] for c in chunks])
+            cnt = np.concatenate([c[1] for c in chunks])
+            boxes, scores, labels = (torch.cat([c[i] for c in chunks]) if len(chunks) > 1 else chunks[0][i] for i in (2, 3, 4))
         else:
             ids, cnt = np.zeros(0, np.int64), np.zeros(0, np.int64)
             boxes = torch.zeros(0, 4, dtype=torch.float64, device=self.device)
@@ -249,8 +266,12 @@ class DetectorEvaluator:
     of batches, a map-style dataset of batches: ``__len__`` and ``__getitem__``) is indexed directly, so a rank never loads the
     batches of the others; a plain iterable can only be skipped through, which loads them all."""
 
-    def __init__(self, model, process_group=None, device=None):
-        self.model, self.pg, self.device = model, process_group, device_of(device)
+    def __init__(self, model, process_group=None, device=None, output="host"):
+        """output="device": the model's detections stay on the device (``forward(output="device")``) and are collected with one
+        launch per batch; the scores are the same."""
+        if output not in ("host", "device"):
+            raise ValueError(f"DetectorEvaluator: output {output!r} (one of 'host', 'device')")
+        self.model, self.pg, self.device, self.output = model, process_group, device_of(device), output
         self.rank, self.world = 0, 1
         if process_group is not None:
             import torch.distributed as dist
@@ -279,6 +300,9 @@ class DetectorEvaluator:
         for imgs, metas in self._my_batches(loader, limit):
             if isinstance(imgs, (list, tuple)):
                 imgs = torch.stack(list(imgs))
+            if self.output == "device":
+                ev.update([int(meta["image_id"]) for meta in metas], self.model(imgs.to(self.device).float() / 255, output="device"))
+                continue
             outputs = self.model(imgs.to(self.device).float() / 255)
             ev.update({int(meta["image_id"]): out for meta, out in zip(metas, outputs)})
         ev.synchronize_between_processes(self.pg)

@@ -726,6 +726,7 @@ class EfficientDetBackbone(nn.Module):
             p.run(ops._st())
             self._range_guard(p)
         p._inflight = keep   # the sources and the record table live until the next call
+        p._records = (metas, keep[0])   # output="device" divides by these records' ratios
         return p, metas
 
     def detection_loss(self, inputs, targets, alpha=0.25, gamma=2.0, box_weight=50.0) -> Dict[str, torch.Tensor]:
@@ -747,8 +748,11 @@ class EfficientDetBackbone(nn.Module):
             raise FloatingPointError("EfficientDet: non-finite head outputs in compute_dtype='f16': activations left f16's range "
                                      "(largest finite value 65504); build the detector with compute_dtype='bf16'")
 
-    def forward(self, inputs, preprocess=True, postprocess=True, threshold=None, iou_threshold=None):
+    def forward(self, inputs, preprocess=True, postprocess=True, threshold=None, iou_threshold=None, output="host"):
+        """output="host": the reference's list of per-image dicts of CPU tensors.  output="device": a ``detections.Detections``,
+        the same detections as device tables from one launch, with no wait for the device (``.to_list()`` gives the list)."""
         self._check_mode()
+        _check_output(output)
         if threshold is not None:
             self.threshold = threshold
         if iou_threshold is not None:
@@ -769,10 +773,13 @@ class EfficientDetBackbone(nn.Module):
         if not postprocess:
             feats = tuple(f.permute(0, 3, 1, 2).to(torch.float32, copy=True) for f, _ in p.feats)
             return feats, p.reg.clone(), p.cls.clone(), self._anchor_dev[None].clone()
-        return self.detect(p, metas, self.threshold, self.iou_threshold)
+        return self.detect(p, metas, self.threshold, self.iou_threshold, output)
 
-    def detect(self, p: _Plan, metas, threshold, iou_threshold) -> List[Dict[str, torch.Tensor]]:
-        """postprocess + invert_affine + the reference's dict format from a plan's head outputs."""
+    def detect(self, p: _Plan, metas, threshold, iou_threshold, output="host"):
+        """postprocess + invert_affine + the reference's dict format from a plan's head outputs; output="device": the same as a
+        ``Detections`` (one launch, nothing copied)."""
+        if _check_output(output) == "device":
+            return detect_on_device(p.reg, p.cls, self._anchor_dev, threshold, iou_threshold, self._record_table(p, metas))
         dets = detect_from_heads(p.reg, p.cls, self._anchor_dev, threshold, iou_threshold)
         out = []
         for i, (boxes, cls, scores) in enumerate(dets):
@@ -785,8 +792,35 @@ class EfficientDetBackbone(nn.Module):
                         "scores": torch.from_numpy(scores)})
         return out
 
+    def _record_table(self, p: _Plan, metas) -> Optional[torch.Tensor]:
+        """The device table of StlDetImage records that belongs to `metas`: the one run_raw uploaded, or a new upload."""
+        if metas is None:
+            return None
+        held = getattr(p, "_records", None)
+        if held is not None and held[0] is metas:
+            return held[1]
+        recs = (capi.DetImage * len(metas))()
+        for i, (new_w, new_h, old_w, old_h, *_) in enumerate(metas):
+            recs[i] = capi.DetImage(None, 1, old_h, old_w, new_h, new_w, 0, 1.0 / (new_h / old_h), 1.0 / (new_w / old_w))
+        return torch.frombuffer(bytearray(bytes(recs)), dtype=torch.uint8).to(p.reg.device, non_blocking=True)
+
 
 EfficientDet = EfficientDetBackbone
+
+
+def _check_output(output):
+    if output not in ("host", "device"):
+        raise ValueError(f"EfficientDet: output {output!r} (one of 'host', 'device')")
+    return output
+
+
+def detect_on_device(reg: torch.Tensor, cls: torch.Tensor, anchors_dev: torch.Tensor, threshold: float, iou_threshold: float,
+                     records: Optional[torch.Tensor] = None):
+    """detect_from_heads without the host: one launch of stlpose::det_postprocess; with `records` (the device table of
+    StlDetImage records) the boxes are on the source images' scale, as invert_affine puts them.  Returns a ``Detections``."""
+    from .detections import Detections
+    return Detections(*torch.ops.stlpose.det_postprocess(reg, cls, anchors_dev, records, float(threshold), float(MAX_SIZE - 1),
+                                                         float(MAX_SIZE - 1), float(iou_threshold)))
 
 
 def detect_from_heads(reg: torch.Tensor, cls: torch.Tensor, anchors_dev: torch.Tensor, threshold: float, iou_threshold: float):

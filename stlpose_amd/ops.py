@@ -852,7 +852,128 @@ _define("oks_ap_match(Tensor kpts, Tensor scores, Tensor? area, Tensor det_offse
         "-> (Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)", _oks_ap_match,
         lambda k, s, a, do, gk, ga, gb, gc, gn, go, thrs, rng, sg: _match_fake(k, s, do, 1, capi.OKS_AP_AREAS))
 
+# ------------------------------------------------------------------ the detector's device tail (csrc/detections.hip)
+def _det_postprocess(reg, cls, anchors, images, threshold: float, xmax: float, ymax: float, iou_thr: float):
+    op = "det_postprocess"
+    if reg.dim() != 3 or reg.shape[2] != 4 or reg.dtype != torch.float32:
+        raise ValueError(f"stlpose {op}: regression must be float32 [B, A, 4], got {reg.dtype} {tuple(reg.shape)}")
+    b, a = reg.shape[:2]
+    if cls.dim() != 3 or tuple(cls.shape[:2]) != (b, a) or cls.shape[2] < 1 or cls.dtype != torch.float32:
+        raise ValueError(f"stlpose {op}: classification must be float32 [B={b}, A={a}, nc], got {cls.dtype} {tuple(cls.shape)}")
+    if tuple(anchors.shape[-2:]) != (a, 4) or anchors.numel() != a * 4 or anchors.dtype != torch.float32:
+        raise ValueError(f"stlpose {op}: anchors must be float32 [A={a}, 4], got {anchors.dtype} {tuple(anchors.shape)}")
+    rec = capi.C.sizeof(capi.DetImage)
+    if images is not None and (images.dtype != torch.uint8 or images.dim() != 1 or images.shape[0] != b * rec or not images.is_contiguous()):
+        raise ValueError(f"stlpose {op}: images must be the uint8 [B={b} * {rec}] table of StlDetImage records, got {images.dtype} "
+                         f"{tuple(images.shape)}")
+    if not reg.is_cuda:
+        raise RuntimeError(f"stlpose {op}: regression must be on the GPU")
+    _same_device((("classification", cls), ("anchors", anchors), ("images", images)), reg.device)
+    r, c, an = reg.contiguous(), cls.contiguous(), anchors.contiguous()
+    k = capi.BOX_MAX
+    boxes = torch.empty(b, k, 4, device=reg.device)
+    scores = torch.empty(b, k, device=reg.device)
+    labels = torch.empty(b, k, dtype=torch.int32, device=reg.device)
+    count = torch.empty(b, dtype=torch.int32, device=reg.device)
+    capi.call("stl_det_postprocess", r.data_ptr(), c.data_ptr(), an.data_ptr(), _ptr(images), b, a, c.shape[2], float(threshold),
+              float(xmax), float(ymax), float(iou_thr), boxes.data_ptr(), scores.data_ptr(), labels.data_ptr(), count.data_ptr(), _st())
+    return boxes, scores, labels, count
+
+
+def _det_tables_fake(r):
+    k = capi.BOX_MAX
+    return (r.new_empty(r.shape[0], k, 4), r.new_empty(r.shape[0], k), r.new_empty(r.shape[0], k, dtype=torch.int32),
+            r.new_empty(r.shape[0], dtype=torch.int32))
+
+
+_define("det_postprocess(Tensor regression, Tensor classification, Tensor anchors, Tensor? images, float threshold, float xmax, "
+        "float ymax, float iou_thr) -> (Tensor, Tensor, Tensor, Tensor)", _det_postprocess,
+        lambda r, c, a, im, t, xm, ym, it: _det_tables_fake(r))
+
+
+def _det_tables(op: str, boxes, scores, labels, count) -> int:
+    """The [B, STL_BOX_MAX] tables of det_postprocess, contiguous; B."""
+    k = capi.BOX_MAX
+    b = _table(op, "count", count, torch.int32, "B")
+    for name, t, dtype, tail in (("boxes", boxes, torch.float32, (k, 4)), ("scores", scores, torch.float32, (k,)),
+                                 ("labels", labels, torch.int32, (k,))):
+        _table(op, name, t, dtype, "B", b, tail)
+        if not t.is_contiguous():
+            raise ValueError(f"stlpose {op}: {name} must be contiguous")
+    return b
+
+
+def _det_append(boxes, scores, labels, count, image_ids, st_boxes, st_scores, st_labels, slots, slot0: int, cursor, parity: int,
+                overflow) -> None:
+    """One launch, no allocation and no sync: the batch's rows go behind cursor[parity], its slots to slots[slot0 ..]."""
+    op = "det_append"
+    b = _det_tables(op, boxes, scores, labels, count)
+    if b > 1024:
+        raise ValueError(f"stlpose {op}: {b} images in one batch (at most 1024)")
+    _table(op, "image_ids", image_ids, torch.int64, "B", b)
+    cap = _table(op, "st_boxes", st_boxes, torch.float64, "cap", None, (4,))
+    _table(op, "st_scores", st_scores, torch.float32, "cap", cap)
+    _table(op, "st_labels", st_labels, torch.int64, "cap", cap)
+    ns = _table(op, "slots", slots, torch.int64, "slots", None, (3,))
+    if slot0 < 0 or slot0 + b > ns:
+        raise ValueError(f"stlpose {op}: slots {slot0} .. {slot0 + b - 1} of a table of {ns}")
+    _table(op, "cursor", cursor, torch.int64, "2", 2)
+    _table(op, "overflow", overflow, torch.int64, "1", 1)
+    if parity not in (0, 1):
+        raise ValueError(f"stlpose {op}: parity {parity} (0 or 1)")
+    for name, t in (("count", count), ("image_ids", image_ids), ("st_boxes", st_boxes), ("st_scores", st_scores), ("st_labels", st_labels),
+                    ("slots", slots), ("cursor", cursor), ("overflow", overflow)):
+        if not t.is_contiguous():
+            raise ValueError(f"stlpose {op}: {name} must be contiguous")
+    if not boxes.is_cuda:
+        raise RuntimeError(f"stlpose {op}: boxes must be on the GPU")
+    _same_device((("scores", scores), ("labels", labels), ("count", count), ("image_ids", image_ids), ("st_boxes", st_boxes),
+                  ("st_scores", st_scores), ("st_labels", st_labels), ("slots", slots), ("cursor", cursor), ("overflow", overflow)),
+                 boxes.device)
+    capi.call("stl_det_append", boxes.data_ptr(), scores.data_ptr(), labels.data_ptr(), count.data_ptr(), image_ids.data_ptr(), b,
+              st_boxes.data_ptr(), st_scores.data_ptr(), st_labels.data_ptr(), cap, slots.data_ptr(), int(slot0), cursor.data_ptr(),
+              int(parity), overflow.data_ptr(), _st())
+
+
+_define("det_append(Tensor boxes, Tensor scores, Tensor labels, Tensor count, Tensor image_ids, Tensor(a!) st_boxes, Tensor(b!) st_scores, "
+        "Tensor(c!) st_labels, Tensor(d!) slots, int slot0, Tensor(e!) cursor, int parity, Tensor(f!) overflow) -> ()", _det_append,
+        lambda *a: None)
+
+def _person_boxes(boxes, scores, labels, count, label: int, score_thr: float, iou_thr: float, aspect: float, crop_w: int, crop_h: int):
+    """iou_thr < 0: the label / score filter alone (1 launch); otherwise NMS on the passing rows as well (3 launches)."""
+    op = "person_boxes"
+    b = _det_tables(op, boxes, scores, labels, count)
+    if b > 1024:
+        raise ValueError(f"stlpose {op}: {b} images in one batch (at most 1024)")
+    if crop_w < 1 or crop_h < 1 or not aspect > 0:
+        raise ValueError(f"stlpose {op}: crop {crop_w} x {crop_h}, aspect {aspect}")
+    if not count.is_contiguous():
+        raise ValueError(f"stlpose {op}: count must be contiguous")
+    if not boxes.is_cuda:
+        raise RuntimeError(f"stlpose {op}: boxes must be on the GPU")
+    _same_device((("scores", scores), ("labels", labels), ("count", count)), boxes.device)
+    n, dev = b * capi.BOX_MAX, boxes.device
+    img = torch.empty(n, dtype=torch.int32, device=dev)
+    out = [torch.empty(n, w, device=dev) if w else torch.empty(n, device=dev) for w in (4, 0, 2, 2, 6)]
+    total = torch.empty(1, dtype=torch.int32, device=dev)
+    nms = iou_thr >= 0
+    work = torch.empty(max(1, int(capi.lib().stl_person_boxes_workspace(b, int(nms)))), dtype=torch.uint8, device=dev)
+    capi.call("stl_person_boxes", boxes.data_ptr(), scores.data_ptr(), labels.data_ptr(), count.data_ptr(), b, int(label), float(score_thr),
+              float(iou_thr), float(aspect), int(crop_w), int(crop_h), work.data_ptr(), img.data_ptr(), *[t.data_ptr() for t in out],
+              total.data_ptr(), _st())
+    return (img, *out, total)
+
+
+def _person_boxes_fake(boxes, scores, labels, count, label, score_thr, iou_thr, aspect, crop_w, crop_h):
+    n = boxes.shape[0] * capi.BOX_MAX
+    return (boxes.new_empty(n, dtype=torch.int32), boxes.new_empty(n, 4), boxes.new_empty(n), boxes.new_empty(n, 2), boxes.new_empty(n, 2),
+            boxes.new_empty(n, 6), boxes.new_empty(1, dtype=torch.int32))
+
+
+_define("person_boxes(Tensor boxes, Tensor scores, Tensor labels, Tensor count, int label, float score_thr, float iou_thr, float aspect, "
+        "int crop_w, int crop_h) -> (Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)", _person_boxes, _person_boxes_fake)
+
 OPS = ["person_mse", "heatmap_argmax", "final_preds", "flip_merge", "flip_merge_backward", "gaussian_targets", "affine_crop",
        "hrnet_forward", "hrnet_backward", "hrnet_backward_input", "pose_vectors", "pose_distances", "pose_topk", "pose_rank", "pose_rank_any",
        "box_select", "heatmap_resize_argmax", "det_decode", "det_nms", "det_loss", "box_ap_match", "box_ap_accumulate",
-       "pose_rescore_nms", "oks_ap_match", "eval_tail", "eval_affine", "pose_augment"]
+       "pose_rescore_nms", "oks_ap_match", "eval_tail", "eval_affine", "pose_augment", "det_postprocess", "det_append", "person_boxes"]

@@ -15,7 +15,7 @@ import numpy as np
 import torch
 
 from . import capi, ops  # noqa: F401  (ops registers the stlpose:: custom ops)
-from .augment import affine_matrices, crop_batch
+from .augment import IMAGENET_MEAN, IMAGENET_STD, affine_matrices, crop_batch
 from .bounding_box import select_boxes
 from .inference import forward_pass
 from .pose_parsing import create_pose_entries
@@ -155,6 +155,64 @@ class PoseExtractor:
             a += n
         return res
 
+    # -- from device tables
+    def person_rows(self, detections, label=1, det_thr=0.7, nms_thr=None):
+        """The person rows of a ``Detections`` on the device (``stlpose::person_boxes``): bbox_filtering's label / score test, the
+        optional NMS, coords2cs and the crop matrices.  Returns (n, img int32 [n], boxes [n, 4], scores [n], center [n, 2], scale
+        [n, 2], minv [n, 6]) with the tensors on the device; reading n, the person count, is the one wait."""
+        t = self.transform
+        img, boxes, scores, center, scale, minv, total = torch.ops.stlpose.person_boxes(
+            detections.boxes, detections.scores, detections.labels, detections.count, int(label), float(np.float32(det_thr)),
+            -1.0 if nms_thr is None else float(nms_thr), float(np.float32(t.aspect_ratio)), t.det_width, t.det_height)
+        n = int(total.item())
+        if n < 0:
+            raise ValueError(f"PoseExtractor: image {-n - 1} of the batch has more candidates than the device path holds "
+                             f"({capi.BOX_MAX}, STL_BOX_MAX); raise the detector's threshold or use the host pipeline")
+        return n, img[:n], boxes[:n], scores[:n], center[:n], scale[:n], minv[:n]
+
+    def from_detections(self, images, detections, label=1, det_thr=0.7, nms_thr=None) -> List[Dict]:
+        """``__call__`` for a detector's device tables (``forward(output="device")``): the boxes never visit the host.  The person
+        count is read once, to size the chunk loop; then affine_crop, the network, final_preds and heatmap_resize_argmax run on
+        device tensors and one copy brings boxes, scores, centers, scales and poses back.  The same dicts as ``__call__``."""
+        if len(images) != len(detections):
+            raise ValueError(f"{len(images)} images but detections of {len(detections)}")
+        dev = detections.device
+        n, img, boxes, scores, center, scale, minv = self.person_rows(detections, label, det_thr, nms_thr)
+        j = 17
+        host = np.zeros((0, 10 + 6 * j), np.float32)
+        if n:
+            src = [_image(im, dev) for im in images]
+            sizes = [s.numel() for s in src]
+            offs = torch.tensor(np.concatenate([[0], np.cumsum(sizes)[:-1]]).astype(np.int64)).to(dev, non_blocking=True)
+            hw = torch.tensor([[s.shape[0], s.shape[1]] for s in src], dtype=torch.int32).to(dev, non_blocking=True)
+            which = img.long()
+            mean, std = torch.tensor(IMAGENET_MEAN, device=dev), torch.tensor(IMAGENET_STD, device=dev)
+            crops = torch.ops.stlpose.affine_crop(torch.cat([s.reshape(-1) for s in src]), offs[which], hw[which], minv,
+                                                  torch.zeros(n, dtype=torch.int32, device=dev), self.transform.det_height,
+                                                  self.transform.det_width, mean, std)
+            hm = self.heatmaps(crops)
+            preds, mx = torch.ops.stlpose.final_preds(hm, center, scale)
+            _, cmx, cpreds = torch.ops.stlpose.heatmap_resize_argmax(hm.float(), self.transform.det_height, self.transform.det_width)
+            j = preds.shape[1]
+            host = torch.cat([img.float()[:, None], boxes, scores[:, None], center, scale, torch.cat([preds, mx], 2).reshape(n, -1),
+                              torch.cat([cpreds, cmx[..., None]], 2).reshape(n, -1)], 1).cpu().numpy()
+        counts = np.bincount(host[:, 0].astype(np.int64), minlength=len(images))
+        res, a = [], 0
+        for c in counts.tolist():
+            rows = host[a:a + c]
+            r = dict(boxes=rows[:, 1:5].copy(), scores=rows[:, 5].copy(), center=rows[:, 6:8].copy(), scale=rows[:, 8:10].copy())
+            if c:
+                r["keypoints"] = rows[:, 10:10 + 3 * j].reshape(c, j, 3).copy()
+                r["crop_keypoints"] = rows[:, 10 + 3 * j:].reshape(c, j, 3).copy()
+                entries, all_kp = create_pose_entries(r["keypoints"][..., :2], r["keypoints"][..., 2:], thr=self.keypoint_thr)
+                r["pose_entries"], r["all_keypoints"] = entries, all_kp[:, [1, 0, 2, 3]]
+            else:
+                r["keypoints"] = r["crop_keypoints"] = np.zeros((0, j, 3), np.float32)
+                r["pose_entries"], r["all_keypoints"] = [], np.zeros((0, 4))
+            res.append(r)
+            a += c
+        return res
+
 
 def extract_retrieval_db(model, loader, flip=True, keypoint_thr=0.1, device=None) -> Dict[str, Dict]:
     """05_create_archdata_retrieval_db.py:114-171 (extract_retrieval_dataset): for every loader batch (imgs, _, _, metadata) with
@@ -177,15 +235,22 @@ def extract_retrieval_db(model, loader, flip=True, keypoint_thr=0.1, device=None
     return db
 
 
-def detect_poses(detector, extractor: PoseExtractor, images, detector_thr=0.7, nms_thr=None) -> List[Dict]:
+def detect_poses(detector, extractor: PoseExtractor, images, detector_thr=0.7, nms_thr=None, pipeline="host") -> List[Dict]:
     """04_evaluate_vases_qualitatively.py:184-250 from raw images: uint8 HWC RGB images (tensors or arrays) -> the EfficientDet
     detector (preprocessed on the device from the same device images) -> bbox_filtering's person boxes (label 1, score >
-    detector_thr) -> ``extractor``.  Returns the extractor's dicts; only the detector's kept boxes and the poses reach the host."""
+    detector_thr) -> ``extractor``.  Returns the extractor's dicts; only the detector's kept boxes and the poses reach the host.
+    pipeline="device": the detections stay device tables from the heads to the crops (``PoseExtractor.from_detections``); the
+    host reads the person count and, at the end, the results."""
+    if pipeline not in ("host", "device"):
+        raise ValueError(f"detect_poses: pipeline {pipeline!r} (one of 'host', 'device')")
     dev = torch.device("cuda", torch.cuda.current_device())
     src = [_image(im, dev) for im in images]
     if not src:
         return []
     p, metas = detector.run_raw(src, 0, dev)
+    if pipeline == "device":
+        dets = detector.detect(p, metas, detector.threshold, detector.iou_threshold, output="device")
+        return extractor.from_detections(src, dets, label=1, det_thr=detector_thr, nms_thr=nms_thr)
     dets = detector.detect(p, metas, detector.threshold, detector.iou_threshold)
     return extractor(src, [d["boxes"].reshape(-1, 4) for d in dets], [d["scores"] for d in dets], [d["labels"].long() for d in dets],
                      label=1, det_thr=detector_thr, nms_thr=nms_thr)
