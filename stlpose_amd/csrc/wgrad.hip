@@ -26,6 +26,7 @@ struct WgK {
     int tiles_c, npt, HR, HC, HP, PI, pad, taps;
     int psg, psh;  // LDS bytes per pixel (32 channels + 16 B pad)
     int off_cg, off_ch, off_g, off_h;
+    int ntl, img;  // wide 1x1 kernel: tiles per round, and LDS bytes from one tile image (g at off_g, h at off_h) to the next
     float r_TW, r_HC, r_tc, r_vp, r_PI;  // reciprocals for fdiv
     unsigned long long m_tc, m_vp, m_PI;  // ceil(2^32 / d): exact n / d = (n * m) >> 32 on the scalar unit for n * d < 2^32
     int xmap, units, gy, gz;   // XCD-aware block order (see wg_block): units = ng * nsplit pixel ranges, gy x gz channel chunks
@@ -504,13 +505,26 @@ int launch(const WgK& k, dim3 grid, size_t lds, hipStream_t st) {
 // MFMAs per barrier pair, and there is no cross-wave reduction: every wave writes its own quadrant
 // of the slab straight from the accumulators.  LDS pixel stride 160 B (128 B data + 32 B pad: the
 // four rows of a transposed 16-lane read fall into disjoint bank groups).
-template <typename T, int KS, int NVH, bool GQ, int TPX, typename TY = T>
+// With one wave per SIMD and 16 MFMAs per wave and tile (one tap), a tile costs what its STAGING costs in vector instructions and
+// LDS waits, not a memory round trip (the phase stamps): the staging below is kept short -- one pixel walk for g and h,
+// straight-line offsets, channel constants in registers.
+// NTL: pixel tiles per ROUND (1, or 2 with STL_WGRAD64_TILES=2).  A block walks its tiles t = bsplit, bsplit + nsplit, ... NTL at
+// a time: it waits for the round's staged loads, transforms and writes NTL LDS images (k.img bytes apart), passes ONE barrier,
+// requests the NTL tiles of the next round, multiplies the NTL images one after the other in walk order and passes one more
+// barrier.  Every accumulator receives the same addends in the same order whatever NTL is: the slabs are bitwise equal.  Rounds
+// of two are 3-5 % faster alone on the layer1 launches and give nothing in the step (80 KB of LDS and 254 registers per block
+// leave less of the CU to the data-gradient chain); rounds of three were slower alone as well.  One tile per round is the default.
+template <typename T, int KS, int NVH, bool GQ, int TPX, typename TY = T, int NTL = 1>
 __global__ __launch_bounds__(256) void wgrad64_kernel(const WgK k) {
     static_assert(sizeof(T) == 2, "bf16 only");
+    static_assert(NTL >= 1 && NTL <= 2, "tiles per round");
+    static_assert(KS == 1 && NVH >= TPX * 8 / 256, "1x1 stride-1 layers only: the staging below walks one pixel set for g and h");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int KV = 8, TAPS = KS * KS, KSTEP = 32, NR = 2;
     constexpr int VPX = 8;                  // 16-byte vectors per pixel (64 channels)
     constexpr int NVG = TPX * VPX / 256;    // g staging vectors per thread
+    // h staging vectors per thread: NVG too -- a stride-1 1x1 tile has no halo, its h pixels are its g pixels (at most
+    // 128 * 8 / 256 = 4 vectors).  NVH only names the instantiation: the bucket the dispatch rules state for this family.
     constexpr int NKS = TPX / KSTEP;        // K steps per tile, all done by every wave
     const stl_wgrad& p = k.p;
     const WgBlock wb = wg_block(k);   // grouped launch, see wgrad_kernel
@@ -530,29 +544,26 @@ __global__ __launch_bounds__(256) void wgrad64_kernel(const WgK k) {
     const int vpitch = p.Ho + 1;
     const int nks = (tilepx + KSTEP - 1) / KSTEP;
 
-    // ---- loop-invariant staging descriptors
-    int g_yx[NVG];
+    // ---- loop-invariant staging descriptors.  A stride-1 1x1 tile has no halo: slot i of a thread is the SAME tile pixel in g
+    // and in h (the host admits nothing else here), so one pixel walk serves both tensors.
+    int s_yx[NVG];    // (ty << 16) | tx of the tile pixel of slot i, -1 = beyond the tile (zero row in g, no row in h)
+    int g_lo[NVG], h_lo[NVG];   // element offsets of the slot from the tile's first pixel, the thread's channels included
     const int g_part = tid % VPX;
+    const bool g_chok = (co0 + g_part * KV) < p.Co, h_chok = (ci0 + g_part * KV) < p.Ci;
+    uint32_t slot_ok = 0;   // bit i: slot i inside the tile and its g channels inside Co; bit NVG + i: ... its h channels inside Ci
 #pragma unroll
     for (int i = 0; i < NVG; ++i) {
         const int m = (tid + i * 256) / VPX;
-        g_yx[i] = -1;
+        s_yx[i] = -1, g_lo[i] = 0, h_lo[i] = 0;
         if (m < tilepx) {
-            const int ty = fdiv(m, k.r_TW);
-            g_yx[i] = (ty << 16) | (m - ty * p.TW);
+            const int ty = fdiv(m, k.r_TW), tx = m - ty * p.TW;
+            s_yx[i] = (ty << 16) | tx;
+            g_lo[i] = (ty * p.Wo + tx) * p.Co + co0 + g_part * KV;
+            h_lo[i] = (ty * p.Wi + tx) * p.Ci + ci0 + g_part * KV;
+            slot_ok |= (g_chok ? 1u << i : 0u) | (h_chok ? 1u << (NVG + i) : 0u);
         }
     }
-    int h_rc[NVH];
-#pragma unroll
-    for (int i = 0; i < NVH; ++i) {
-        const int v = tid + i * 256;
-        h_rc[i] = -1;
-        if (v < k.HP * VPX) {
-            const int hp = v / VPX, hr = fdiv(hp, k.r_HC);
-            h_rc[i] = (hr << 16) | (hp - hr * k.HC);
-        }
-    }
-    const bool g_chok = (co0 + g_part * KV) < p.Co, h_chok = (ci0 + g_part * KV) < p.Ci;
+    const int g_row = p.Wo * p.Co, h_row = p.Wi * p.Ci;   // elements per image row
 
     // ---- MFMA-side offsets: pixel m = 32 s + 8 g + 4 i + ((lane & 15) >> 2) of K step s
     int rg0[NR], rh[NKS][NR];
@@ -568,71 +579,67 @@ __global__ __launch_bounds__(256) void wgrad64_kernel(const WgK k) {
             rh[s][i] = ((ty * p.stride) * k.HC + tx * p.stride) * k.psh;
         }
 
-    V16 rgv[NVG], rgq[GQ ? NVG : 1], rhv[NVH];
-    int g_go[NVG], h_go[NVH];
+    // ---- NTL register sets of staged loads (one per tile of a round), each with the validity bits of its slots
+    V16 rgv[NTL][NVG], rgq[NTL][GQ ? NVG : 1], rhv[NTL][NVG];
+    uint32_t okm[NTL];   // bit i = g slot i, bit NVG + i = h slot i: inside the tensors (all zero for a tile the round does not have)
 
-    auto setup = [&](int t) {
-        const int tr = fdiv(t, k.r_tc), tc = t - tr * k.tiles_c;
+    // request tile t into set J.  Unconditional loads with clamped addresses: a slot outside the tensors (or every slot,
+    // !en: the round has no such tile) loads element 0 and is zeroed when written to LDS.
+    // Element offset of a slot = (tile term: uniform) + (slot term: computed once) - (images the slot lies beyond the tile's
+    // first row) * (one image row): straight-line, a handful of vector instructions per slot.  (Until the rounds were measured
+    // every tile recomputed batch, row and column of all eight slots with nested conditionals: 1.1 us of the 3.1 us a tile took.)
+    auto fetch = [&](auto J, int t, bool en) __attribute__((always_inline)) {
+        constexpr int j = decltype(J)::value;
+        const int tt = en ? t : 0;
+        const int tr = fdiv(tt, k.r_tc), tc = tt - tr * k.tiles_c;
         const int vr0 = tr * p.TH, c0 = tc * p.TW;
         const int gb0 = fdiv(vr0, k.r_vp), gy0 = vr0 - gb0 * vpitch;
+        const int pix0 = (vr0 - gb0) * p.Wo + c0;   // the tile's first pixel (image rows only: the separator rows are virtual)
+        const int g_t = pix0 * p.Co, h_t = pix0 * p.Ci;
+        const uint32_t live = en ? slot_ok : 0u;
+        uint32_t ok = 0;
 #pragma unroll
         for (int i = 0; i < NVG; ++i) {
-            g_go[i] = -1;
-            if (g_yx[i] >= 0 && g_chok) {
-                int oy = gy0 + (g_yx[i] >> 16), b = gb0;
-                const int c = c0 + (g_yx[i] & 0xffff);
-                { const int wr_ = fdiv(oy, k.r_vp); oy -= wr_ * vpitch, b += wr_; }
-                if (b < p.B && oy < p.Ho && c < p.Wo) g_go[i] = ((b * p.Ho + oy) * p.Wo + c) * p.Co + co0 + g_part * KV;
-            }
+            const int oy0 = gy0 + (s_yx[i] >> 16), c = c0 + (s_yx[i] & 0xffff);
+            const int wr_ = fdiv(oy0 < 0 ? 0 : oy0, k.r_vp);   // images between the tile's first row and this slot's
+            const int oy = oy0 - wr_ * vpitch;
+            const bool in = (gb0 + wr_ < p.B) & (oy < p.Ho) & (c < p.Wo);
+            const bool gin = in & (((live >> i) & 1u) != 0), hin = in & (((live >> (NVG + i)) & 1u) != 0);
+            const size_t go = gin ? (size_t)(g_t + g_lo[i] - wr_ * g_row) : 0;
+            const size_t ho = hin ? (size_t)(h_t + h_lo[i] - wr_ * h_row) : 0;
+            rgv[j][i] = ldg16((const char*)io.g.x + go * sizeof(T));
+            if (GQ) rgq[j][i] = ldg16((const char*)io.g.y + go * sizeof(T));
+            rhv[j][i] = ldg16((const char*)io.h.x + ho * sizeof(T));
+            ok |= (gin ? 1u << i : 0u) | (hin ? 1u << (NVG + i) : 0u);
         }
-        const int vrs = vr0 * p.stride, cb = c0 * p.stride - k.pad;
-        const int hb0 = fdiv(vrs, k.r_PI), hy0 = vrs - hb0 * k.PI - k.pad;
-#pragma unroll
-        for (int i = 0; i < NVH; ++i) {
-            h_go[i] = -1;
-            if (h_rc[i] >= 0 && h_chok) {
-                int iy = hy0 + (h_rc[i] >> 16), b = hb0;
-                const int ix = cb + (h_rc[i] & 0xffff);
-                if (iy >= 0 && ix >= 0 && ix < p.Wi) {
-                    { const int wr_ = fdiv(iy, k.r_PI); iy -= wr_ * k.PI, b += wr_; }
-                    if (b < p.B && iy < p.Hi) h_go[i] = ((b * p.Hi + iy) * p.Wi + ix) * p.Ci + ci0 + g_part * KV;
-                }
-            }
-        }
-    };
-    auto issue = [&](bool en) {  // unconditional loads, clamped addresses
-#pragma unroll
-        for (int i = 0; i < NVG; ++i) {
-            const size_t off = (en && g_go[i] >= 0) ? (size_t)g_go[i] : 0;
-            rgv[i] = ldg16((const char*)io.g.x + off * sizeof(T));
-            if (GQ) rgq[i] = ldg16((const char*)io.g.y + off * sizeof(T));
-        }
-#pragma unroll
-        for (int i = 0; i < NVH; ++i) {
-            const size_t off = (en && h_go[i] >= 0) ? (size_t)h_go[i] : 0;
-            rhv[i] = ldg16((const char*)io.h.x + off * sizeof(T));
-        }
+        okm[j] = ok;
     };
     const float relu_lo = io.h.relu ? 0.f : -INFINITY;
-    auto write_lds = [&]() {
-        const int cl = g_part * KV;
+    // set J -> LDS image J.  Every staged register is read unconditionally (only an h store beyond the tile is predicated), so
+    // that no load stays pending on some path; a tile the round does not have writes a zero image that nothing multiplies.
+    // kg / kh: this thread's channel constants in registers (every slot of a thread covers the same 8 channels): read from LDS
+    // per staging vector, each read with a full LDS wait behind it, they were most of the 1.6 us a tile's transform took.
+    alignas(16) float kg[3][KV], kh[2][KV];
+    auto write_lds = [&](auto J) __attribute__((always_inline)) {
+        constexpr int j = decltype(J)::value;
+        char* sGj = sG + j * k.img;
+        char* sHj = sH + j * k.img;
 #pragma unroll
         for (int i = 0; i < NVG; ++i) {
-            V16 val = rgv[i];
-            if (GQ) val = xform_bnbwd<T, TY>(val, rgq[i], cgc + cl, cgc + 64 + cl, cgc + 128 + cl);
-            mask16(val, g_go[i] >= 0);
+            V16 val = rgv[j][i];
+            if (GQ) val = xform_bnbwd<T, TY>(val, rgq[j][i], kg[0], kg[1], kg[2]);
+            mask16(val, (okm[j] >> i) & 1u);
             const int v = tid + i * 256;
-            *reinterpret_cast<V16*>(sG + (v / VPX) * k.psg + g_part * 16) = val;
+            *reinterpret_cast<V16*>(sGj + (v / VPX) * k.psg + g_part * 16) = val;
         }
 #pragma unroll
-        for (int i = 0; i < NVH; ++i) {
-            if (h_rc[i] < 0) continue;
-            V16 val = rhv[i];
-            if (io.h.mode == STL_SRC_BN) val = xform_bn<T, TY>(val, chc + cl, chc + 64 + cl, relu_lo);
+        for (int i = 0; i < NVG; ++i) {
+            V16 val = rhv[j][i];
+            if (io.h.mode == STL_SRC_BN) val = xform_bn<T, TY>(val, kh[0], kh[1], relu_lo);
             else val = xform_cvt<T, TY>(val);
-            mask16(val, h_go[i] >= 0);
+            mask16(val, (okm[j] >> (NVG + i)) & 1u);
             const int v = tid + i * 256;
-            *reinterpret_cast<V16*>(sH + (v / VPX) * k.psh + g_part * 16) = val;
+            if (s_yx[i] >= 0) *reinterpret_cast<V16*>(sHj + (v / VPX) * k.psh + g_part * 16) = val;
         }
     };
 
@@ -644,11 +651,16 @@ __global__ __launch_bounds__(256) void wgrad64_kernel(const WgK k) {
 #pragma unroll
             for (int t = 0; t < TAPS; ++t) acc[a][b][t] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-    int t = bsplit;
-    bool have = t < k.npt;
+    // f(J) for every tile slot J of a round, in walk order
+    auto each_tile = [&](auto f) __attribute__((always_inline)) {
+        f(std::integral_constant<int, 0>{});
+        if constexpr (NTL > 1) f(std::integral_constant<int, 1>{});
+    };
+    const int step = p.nsplit;
+    int t = bsplit;   // first tile of the round; slot J holds tile t + J * step
     WSTAMP(1);
     // BatchNorm constants (wave 3: the 64 channels of g, wave 2: those of h): statistics loads go out
-    // ahead of the first tile's loads, the arithmetic runs while those are in flight
+    // ahead of the first round's loads, the arithmetic runs while those are in flight
     SrcRaw raw;
     const bool cw = wave >= 2, cg = wave == 3;
     const bool cok = cw && (cg ? co0 + lane < p.Co : ci0 + lane < p.Ci);
@@ -656,8 +668,10 @@ __global__ __launch_bounds__(256) void wgrad64_kernel(const WgK k) {
         if (cg) src_raw_load(io.g, co0 + lane, p.Co, raw);
         else src_raw_load(io.h, ci0 + lane, p.Ci, raw);
     }
-    if (have) setup(t);
-    issue(have);
+    each_tile([&](auto J) __attribute__((always_inline)) {
+        const int tj = t + decltype(J)::value * step;
+        fetch(J, tj, tj < k.npt);
+    });
     WSTAMP(2);
     if (cw) {
         float a = 0.f, b = 0.f, cc = 0.f;
@@ -669,18 +683,21 @@ __global__ __launch_bounds__(256) void wgrad64_kernel(const WgK k) {
         else chc[lane] = a, chc[64 + lane] = b;
     }
     __syncthreads();  // constants visible
+#pragma unroll
+    for (int c = 0; c < KV; ++c) {
+        const int ch = g_part * KV + c;
+        kg[0][c] = cgc[ch], kg[1][c] = cgc[64 + ch], kg[2][c] = cgc[128 + ch];
+        kh[0][c] = chc[ch], kh[1][c] = chc[64 + ch];
+    }
     WSTAMP(3);
     bool first = true;
+    [[maybe_unused]] int dbg_i = 0;
 
     const int acol = (wm * 32) * (int)sizeof(T), bcol = (wn * 32) * (int)sizeof(T);
-    while (have) {
-        write_lds();
-        __syncthreads();
-        if (first) WSTAMP(4);
-        const int tn = t + p.nsplit;
-        const bool have_n = tn < k.npt;
-        if (have_n) setup(tn);
-        issue(have_n);  // next tile's loads fly during the MFMAs
+    // all pixels of LDS image J x this wave's quadrant (today's K-step order inside the tile)
+    auto multiply = [&](auto J) __attribute__((always_inline)) {
+        const char* sGj = sG + decltype(J)::value * k.img;
+        const char* sHj = sH + decltype(J)::value * k.img;
 #pragma unroll
         for (int s = 0; s < NKS; ++s) {
             if (s < nks) {
@@ -689,23 +706,43 @@ __global__ __launch_bounds__(256) void wgrad64_kernel(const WgK k) {
                 for (int i = 0; i < NR; ++i) rg[i] = rg0[i] + s * KSTEP * k.psg;
                 V16 a[2];
 #pragma unroll
-                for (int mt = 0; mt < 2; ++mt) a[mt] = frag_tr<T>(sG, rg, acol + mt * 16 * (int)sizeof(T), lane);
+                for (int mt = 0; mt < 2; ++mt) a[mt] = frag_tr<T>(sGj, rg, acol + mt * 16 * (int)sizeof(T), lane);
 #pragma unroll
                 for (int tap = 0; tap < TAPS; ++tap) {
                     const int toff = ((tap / KS) * k.HC + (tap % KS)) * k.psh;
 #pragma unroll
                     for (int nt = 0; nt < 2; ++nt) {
-                        const V16 b = frag_tr<T>(sH + toff, rh[s], bcol + nt * 16 * (int)sizeof(T), lane);
+                        const V16 b = frag_tr<T>(sHj + toff, rh[s], bcol + nt * 16 * (int)sizeof(T), lane);
 #pragma unroll
                         for (int mt = 0; mt < 2; ++mt) mma16<T>(acc[mt][nt][tap], a[mt], b);
                     }
                 }
             }
         }
+    };
+    while (t < k.npt) {   // one round: tiles t, t + step, ... (NTL of them, fewer in the last round)
+        WSTAMP2(4 * dbg_i);
+        each_tile(write_lds);
         __syncthreads();
+        WSTAMP2(4 * dbg_i + 1);
+        if (first) WSTAMP(4);
+        const int tn = t + NTL * step;
+        each_tile([&](auto J) __attribute__((always_inline)) {   // the next round's loads fly during the MFMAs
+            const int tj = tn + decltype(J)::value * step;
+            fetch(J, tj, tj < k.npt);
+        });
+        WSTAMP2(4 * dbg_i + 2);
+        each_tile([&](auto J) __attribute__((always_inline)) {
+            if (t + decltype(J)::value * step < k.npt) multiply(J);   // block-uniform: a tile the round does not have is skipped
+        });
+        __syncthreads();
+        WSTAMP2(4 * dbg_i + 3);
+#ifdef STL_STAMPS
+        ++dbg_i;
+#endif
         if (first) WSTAMP(5);
         first = false;
-        t = tn, have = have_n;
+        t = tn;
     }
     WSTAMP(6);
     // ---- every wave writes its quadrant: acc[mt][nt][tap][r] = dw[co = 4g + r][ci = lane & 15]
@@ -728,28 +765,41 @@ __global__ __launch_bounds__(256) void wgrad64_kernel(const WgK k) {
     WSTAMP(8);
 }
 
-template <typename T, typename TY, int KS, int NVH, bool GQ, int TPX>
+template <typename T, typename TY, int KS, int NVH, bool GQ, int TPX, int NTL>
 int launch64(const WgK& k, dim3 grid, size_t lds, hipStream_t st) {
     static bool attr_done = false;
     if (!attr_done) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad64_kernel<T, KS, NVH, GQ, TPX, TY>),
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad64_kernel<T, KS, NVH, GQ, TPX, TY, NTL>),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         attr_done = true;
     }
-    STL_LAUNCH((wgrad64_kernel<T, KS, NVH, GQ, TPX, TY>), grid, dim3(256), lds, st, k);
+    STL_LAUNCH((wgrad64_kernel<T, KS, NVH, GQ, TPX, TY, NTL>), grid, dim3(256), lds, st, k);
     static char nbuf[160];
-    static const char* nm = stl_kname<T>(nbuf, "wgrad64_kernel", {KS, NVH, GQ, TPX, stl_code<TY>()});
+    static const char* nm = stl_kname<T>(nbuf, "wgrad64_kernel", {KS, NVH, GQ, TPX, stl_code<TY>(), NTL});
     stl_note_kernel(nm, true);
     STL_LAUNCH_CHECK("conv_wgrad64");
     return 0;
 }
 
 #if STL_DT != 0
+// tiles per round of the wide 1x1 kernel: 1 (default), STL_WGRAD64_TILES=2: rounds of two tiles -- A/B, bit-identical slabs.
+// Read per call: the tests compare the arms.
+static int wgrad64_tiles() {
+    const char* e = getenv("STL_WGRAD64_TILES");
+    return e && atoi(e) == 2 ? 2 : 1;
+}
+
+template <typename TY, bool GQ>
+int dispatch64_tiles(const WgK& k, dim3 grid, size_t lds, hipStream_t st) {
+    if (k.ntl == 2) return launch64<__bf16, TY, 1, 6, GQ, 128, 2>(k, grid, lds, st);
+    return launch64<__bf16, TY, 1, 6, GQ, 128, 1>(k, grid, lds, st);
+}
 template <typename TY>
-int dispatch64(const WgK& k, dim3 grid, size_t lds, hipStream_t st) {   // 1x1 layers, 128-pixel tiles
+int dispatch64(const WgK& k, dim3 grid, size_t lds, hipStream_t st) {   // 1x1 stride-1 layers, 128-pixel tiles: the halo is the tile
     const int nvh = ceil_div(k.HP * 8, 256);
     const bool gq = k.p.g.mode == STL_SRC_BNBWD;
-    if (k.p.TH * k.p.TW <= 128 && nvh <= 6) return gq ? launch64<__bf16, TY, 1, 6, true, 128>(k, grid, lds, st) : launch64<__bf16, TY, 1, 6, false, 128>(k, grid, lds, st);
+    STL_CHECK(k.p.ks == 1 && k.p.stride == 1 && k.ntl >= 1 && k.ntl <= 2, "wgrad64: 1x1 stride-1 layers, 1 or 2 tiles per round");
+    if (k.p.TH * k.p.TW <= 128 && nvh <= 4) return gq ? dispatch64_tiles<TY, true>(k, grid, lds, st) : dispatch64_tiles<TY, false>(k, grid, lds, st);
     return stl_set_error("wgrad64: halo of %d pixels is too large for a %d-pixel tile", k.HP, k.p.TH * k.p.TW);
 }
 #endif
@@ -899,6 +949,7 @@ static int wgrad_run(const stl_wgrad* const* ps, int ng, void* stream) {
     k.ng = ng;
     for (int i = 0; i < ng; ++i) k.io[i].h = ps[i]->h, k.io[i].g = ps[i]->g, k.io[i].partial = ps[i]->partial;
     k.dbg = getenv("STL_CONV_STAMPS") ? 1 : 0;
+    k.ntl = 1, k.img = 0;
     k.taps = p.ks * p.ks;
     k.pad = pad;
     k.PI = p.stride * (p.Ho + 1);
@@ -926,7 +977,9 @@ static int wgrad_run(const stl_wgrad* const* ps, int ng, void* stream) {
         k.psg = k.psh = 160;
         k.off_cg = 0, k.off_ch = 3 * 64 * 4, k.off_g = 2048;  // consts: g [3][64] at 0, h [2][64] at 768
         k.off_h = k.off_g + 128 * k.psg;
-        const size_t lds64 = (size_t)k.off_h + (size_t)k.HP * k.psh;
+        k.ntl = wgrad64_tiles();
+        k.img = 128 * k.psg + k.HP * k.psh;   // one tile image: 128 g pixels, then the h pixels (40 KB for a 128-pixel tile)
+        const size_t lds64 = (size_t)k.off_g + (size_t)k.ntl * k.img;
         STL_CHECK(lds64 <= 160 * 1024, "wgrad64: tile needs %zu B of LDS (>160 KiB)", lds64);
         STL_CHECK(p.nsplit <= k.npt || p.nsplit == 1, "wgrad: nsplit %d > tiles %d", p.nsplit, k.npt);
         dim3 grid64 = wg_grid(k, p.nsplit * ng, ceil_div(p.Co, 64), ceil_div(p.Ci, 64));

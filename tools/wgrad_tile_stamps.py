@@ -1,16 +1,18 @@
-"""Per-tile phase stamps of the 3x3 weight-gradient kernel: block 0 / thread 0 of one launch (stamped build:
-python -m stlpose_amd.build --stamps).  usage: python tools/wgrad_tile_stamps.py [B,H,W,Ci,Co,nsplit ...]"""
+"""Per-tile phase stamps of the weight-gradient kernels: block 0 / thread 0 of one launch (stamped build:
+python -m stlpose_amd.build --stamps).  usage: python tools/wgrad_tile_stamps.py [B,H,W,Ci,Co,nsplit[,ks] ...]
+ks defaults to 3; ks 1 with Ci, Co >= 64 is the wide 1x1 kernel, whose rows are per ROUND (STL_WGRAD64_TILES tiles each)."""
 import os, sys, ctypes as C
 os.environ["STL_CONV_STAMPS"] = "1"
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import tools.wgrad_probe as w   # selects the stamped library
 import torch
 from stlpose_amd import capi
-cases = [(32, 96, 72, 32, 32, 128), (32, 96, 72, 32, 32, 512), (32, 48, 36, 64, 64, 32), (32, 48, 36, 64, 64, 128), (32, 24, 18, 128, 128, 32)]
+cases = [(32, 96, 72, 32, 32, 128), (32, 96, 72, 32, 32, 512), (32, 48, 36, 64, 64, 32), (32, 48, 36, 64, 64, 128), (32, 24, 18, 128, 128, 32),
+         (32, 96, 72, 64, 256, 63, 1), (32, 96, 72, 256, 64, 63, 1)]
 if len(sys.argv) > 1:
     cases = [tuple(int(v) for v in a.split(",")) for a in sys.argv[1:]]
-for B, H, W, Ci, Co, ns in cases:
-    w.run(B, H, W, Ci, Co, 3, 128, [ns])
+for B, H, W, Ci, Co, ns, *ks in cases:
+    w.run(B, H, W, Ci, Co, ks[0] if ks else 3, 128, [ns])
     torch.cuda.synchronize()
     b = (C.c_longlong * 64)()
     capi.call("stl_debug_wgrad_stamps2", C.cast(b, C.c_void_p))
