@@ -24,3 +24,5 @@ from .keypoint_eval import keypoint_ap, keypoint_ap_tables, rescore_and_nms_devi
 from .eval_tail import EvalTables  # noqa: F401,E402
 from .pose_parsing import pck_from_coords  # noqa: F401,E402
 from .pose_data import coco_person_db, epoch_indices, ResidentImages, StreamedImages, PoseBatchLoader, PersonDB  # noqa: F401,E402
+from .det_data import coco_detection_db, DetectionDB, DetBatch, DetBatchLoader  # noqa: F401,E402
+from .detector_trainer import DetectorTrainer  # noqa: F401,E402

@@ -22,7 +22,7 @@ UNITS = [("capi.hip", "capi", []), ("conv_core.hip", "conv_core_bf16", ["-DSTL_D
          ("topdown.hip", "topdown", []), ("detector.hip", "detector", []), ("detector_train.hip", "detector_train", []),
          ("adain.hip", "adain", []), ("box_ap.hip", "box_ap", []), ("keypoint_eval.hip", "keypoint_eval", []),
          ("eval_tail.hip", "eval_tail", []), ("pose_batch.hip", "pose_batch", ["-ffp-contract=off"]),
-         ("detections.hip", "detections", ["-ffp-contract=off"])]
+         ("detections.hip", "detections", ["-ffp-contract=off"]), ("det_batch.hip", "det_batch", ["-ffp-contract=off"])]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wno-unused-result", "-Wno-unused-value"]
 

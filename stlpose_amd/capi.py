@@ -47,6 +47,9 @@ STRING_FUNCS = tuple(n for n, r in RESTYPES.items() if r is C.c_char_p)   # cons
 DEBUG_SIGNATURES = Header(os.path.join(INCLUDE, "stlpose_hip_debug.h")).signatures
 # include/stlpose_hip_detections.h: the detector's device tail (csrc/detections.hip), part of the product library
 DETECTIONS = Header(os.path.join(INCLUDE, "stlpose_hip_detections.h"))
+# include/stlpose_hip_det_batch.h: detector batches built on the device (csrc/det_batch.hip), part of the product library
+DET_BATCH = Header(os.path.join(INCLUDE, "stlpose_hip_det_batch.h"))
+globals().update({name[len("STL_"):]: value for name, value in DET_BATCH.constants.items()})   # DET_BATCH_MAX, DET_BATCH_SIDE
 
 DTYPES = {F32: (4, torch.float32), BF16: (2, torch.bfloat16), F16: (2, torch.float16)}   # code -> (bytes per element, torch dtype)
 
@@ -85,9 +88,10 @@ def lib() -> C.CDLL:
         for name, args in SIGNATURES.items():
             fn = getattr(l, name)  # AttributeError if the library lacks a symbol of the header
             fn.argtypes, fn.restype = args, RESTYPES[name]
-        for name, args in DETECTIONS.signatures.items():
-            fn = getattr(l, name)
-            fn.argtypes, fn.restype = args, DETECTIONS.restypes[name]
+        for header in (DETECTIONS, DET_BATCH):
+            for name, args in header.signatures.items():
+                fn = getattr(l, name)
+                fn.argtypes, fn.restype = args, header.restypes[name]
         for name, args in DEBUG_SIGNATURES.items():
             if hasattr(l, name):
                 getattr(l, name).argtypes, getattr(l, name).restype = args, C.c_int

@@ -258,10 +258,16 @@ class CocoEvaluator:
         return {"bbox": ev.stats}
 
 
+def _is_det_batch(imgs) -> bool:
+    from .det_data import DetBatch
+    return isinstance(imgs, DetBatch)
+
+
 class DetectorEvaluator:
     """The evaluation loop of ``03_evaluate_faster_rcnn.py:133-167`` (and, with ``fraction=0.2``, the validation epoch of
     ``02_train_faster_rcnn.py:241-280``, which scores the first fifth of the loader).  The loader yields ``(imgs, metas)``: images
-    with values in 0 .. 255 (a stacked tensor or a list of CHW tensors) and one dict per image with ``image_id``.  With a
+    with values in 0 .. 255 (a stacked tensor or a list of CHW tensors), or a ``det_data.DetBatch`` (``DetBatchLoader``), which goes to
+    the model as it is, and one dict per image with ``image_id``.  With a
     process group, rank r runs batches r, r + world, ... and every rank scores the gathered set.  An indexable loader (a list
     of batches, a map-style dataset of batches: ``__len__`` and ``__getitem__``) is indexed directly, so a rank never loads the
     batches of the others; a plain iterable can only be skipped through, which loads them all."""
@@ -298,6 +304,13 @@ class DetectorEvaluator:
         ev = self.coco_evaluator = CocoEvaluator(coco_gt, ("bbox",), device=self.device)
         limit = None if fraction == 1.0 else int(np.floor(len(loader) * fraction + 1e-9))
         for imgs, metas in self._my_batches(loader, limit):
+            if _is_det_batch(imgs):   # det_data.DetBatchLoader: the batch is the network's input already, on the device
+                out = self.model(imgs, output=self.output)
+                if self.output == "device":
+                    ev.update([int(meta["image_id"]) for meta in metas], out)
+                else:
+                    ev.update({int(meta["image_id"]): o for meta, o in zip(metas, out)})
+                continue
             if isinstance(imgs, (list, tuple)):
                 imgs = torch.stack(list(imgs))
             if self.output == "device":

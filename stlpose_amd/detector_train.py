@@ -30,7 +30,7 @@ import numpy as np
 import torch
 
 from . import capi, ops
-from .efficientdet import MAX_SIZE, list_dwconv, list_pointwise, resize_meta
+from .efficientdet import MAX_SIZE, _device, _is_det_batch, list_dwconv, list_pointwise, resize_meta
 from .launch import LaunchList
 
 HEADS = ("regressor", "classifier")
@@ -243,24 +243,32 @@ def detection_loss(m, inputs, targets, alpha: float = 0.25, gamma: float = 2.0, 
     if m.compute_dtype not in ("fp32", "f16"):
         raise NotImplementedError(f"EfficientDet.detection_loss: compute_dtype {m.compute_dtype!r}; the heads train in \"fp32\" or "
                                   "\"f16\" (f16 forward, bf16 gradients)")
-    dev = torch.device("cuda", torch.cuda.current_device())
-    srcs = m._float_sources(inputs, dev)
-    gt, offsets = pack_targets(targets, [(int(s.shape[1]), int(s.shape[2])) for s in srcs], m.num_classes)
     st = ops._st()
+    if _is_det_batch(inputs):   # det_data.DetBatch: the canvas and the ground-truth table are on the device already
+        if targets is not None:
+            raise ValueError("EfficientDet.detection_loss: a DetBatch carries its targets (gt, offsets); pass no targets with it")
+        dev = _device(inputs.canvas.device)
+        p, canvas, keep = m.plan(len(inputs), dev), inputs.canvas, inputs
+        gt_dev, offsets_dev = inputs.gt, inputs.offsets
+    else:
+        dev = torch.device("cuda", torch.cuda.current_device())
+        srcs = m._float_sources(inputs, dev)
+        gt, offsets = pack_targets(targets, [(int(s.shape[1]), int(s.shape[2])) for s in srcs], m.num_classes)
+        with torch.no_grad():
+            p, _, keep = m._preprocess(srcs, 1, dev)
+        canvas, gt_dev, offsets_dev = None, torch.from_numpy(gt).to(dev), torch.from_numpy(offsets).to(dev)
     with torch.no_grad():
-        p, _, keep = m._preprocess(srcs, 1, dev)
         if p.train is None:
             p.train = HeadTrain(m, p)
         tr = p.train
-        p.run(st, upto=p.head_start)
+        p.run(st, upto=p.head_start, canvas=canvas)
         tr.forward(st)
         p._inflight = keep
         if tr.h16 and not bool((torch.isfinite(tr.reg).all() & torch.isfinite(tr.cls).all()).item()):
             raise FloatingPointError("EfficientDet.detection_loss: non-finite head outputs in compute_dtype='f16': activations left "
                                      "f16's range (largest finite value 65504); fine-tune the detector with compute_dtype=\"fp32\"")
-        losses, dreg, dlogit, npos = torch.ops.stlpose.det_loss(tr.reg, tr.cls, m._anchor_dev, torch.from_numpy(gt).to(dev),
-                                                                torch.from_numpy(offsets).to(dev), float(alpha), float(gamma),
-                                                                float(box_weight))
+        losses, dreg, dlogit, npos = torch.ops.stlpose.det_loss(tr.reg, tr.cls, m._anchor_dev, gt_dev, offsets_dev, float(alpha),
+                                                                float(gamma), float(box_weight))
         tr.set_grads(dreg, dlogit)
         tr.npos = npos
     named = head_parameters(m)

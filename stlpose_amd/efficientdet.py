@@ -25,6 +25,7 @@ backbone and the BiFPN are frozen, every BN stays on its running statistics, and
 """
 from __future__ import annotations
 
+import ctypes
 import math
 from typing import Dict, List, Optional
 
@@ -529,8 +530,22 @@ class _Plan:
         p7_out = node("conv7_down", "p7_w2", [(p7_in, 0), (p6_out, 2)], hs[4])
         return [(p, p.shape[1]) for p in (p3_out, p4_out, p5_out, p6_out, p7_out)]
 
-    def run(self, stream: int, upto: Optional[int] = None) -> None:
-        self.calls.run(stream, 0, upto)
+    def run(self, stream: int, upto: Optional[int] = None, canvas: Optional[torch.Tensor] = None) -> None:
+        """canvas: another fp32 [B, S, S, 3] input than the plan's own (a ``DetBatch``'s): the stem, the first launch and the canvas's
+        only reader, reads it where it lies -- nothing is copied."""
+        if canvas is None or canvas.data_ptr() == self.canvas.data_ptr():
+            return self.calls.run(stream, 0, upto)
+        if tuple(canvas.shape) != tuple(self.canvas.shape) or canvas.dtype != torch.float32 or canvas.device != self.canvas.device \
+                or not canvas.is_contiguous():
+            raise ValueError(f"EfficientDet: the batch's canvas must be contiguous float32 {tuple(self.canvas.shape)} on {self.canvas.device}, "
+                             f"got {canvas.dtype} {tuple(canvas.shape)} on {canvas.device}")
+        fn, name, args = self.calls.calls[0]
+        own = self.canvas.data_ptr()
+        mine = [isinstance(a, ctypes.c_void_p) and a.value == own for a in args]
+        assert name in ("stl_det_stem", "stl_det_stem16") and sum(mine) == 1, "EfficientDet: the plan's first launch is not the stem"
+        args = tuple(ctypes.c_void_p(canvas.data_ptr()) if m else a for a, m in zip(args, mine))
+        capi.check(fn(*args, ctypes.c_void_p(stream)), name)
+        self.calls.run(stream, 1, upto)
 
 
 # ------------------------------------------------------------------------------------------------ the model
@@ -575,6 +590,7 @@ class EfficientDetBackbone(nn.Module):
         self.num_anchors_total = self.anchors_np.shape[0]
         self._version, self._plans, self._wbuf, self._wbuf16, self._anchor_dev = None, {}, None, None, None
         self._wbufT16, self._layoutT = None, None   # the heads' bf16 transposed packs (_ensure_transposed: models that train only)
+        self._batch_tables: dict = {}               # _batch_records: the constant record table of a DetBatch geometry
         self.eval()
 
     # ---------------------------------------------------------------- state
@@ -729,7 +745,29 @@ class EfficientDetBackbone(nn.Module):
         p._records = (metas, keep[0])   # output="device" divides by these records' ratios
         return p, metas
 
-    def detection_loss(self, inputs, targets, alpha=0.25, gamma=2.0, box_weight=50.0) -> Dict[str, torch.Tensor]:
+    def _batch_records(self, batch, dev):
+        """(metas, device record table) of a ``DetBatch``: B times its constant ``resize_meta(S1, S1)``, built and uploaded once per
+        (batch size, S1) and held: a batch builds no host table."""
+        key = (len(batch), tuple(batch.meta), str(dev))
+        held = self._batch_tables.get(key)
+        if held is None:
+            metas = [tuple(batch.meta)] * len(batch)
+            held = self._batch_tables[key] = (metas, self._record_table(None, metas, dev))
+        return held
+
+    def run_batch(self, batch, dev):
+        """run_raw for a ``det_data.DetBatch``: the network reads the batch's canvas where it lies; returns (plan, metas)."""
+        self._check_mode()
+        p = self.plan(len(batch), dev)
+        with torch.no_grad():
+            p.run(ops._st(), canvas=batch.canvas)
+            self._range_guard(p)
+        metas, table = self._batch_records(batch, dev)
+        p._inflight = batch   # the canvas lives until the next call
+        p._records = (metas, table)
+        return p, metas
+
+    def detection_loss(self, inputs, targets=None, alpha=0.25, gamma=2.0, box_weight=50.0) -> Dict[str, torch.Tensor]:
         """The fine-tuning counterpart of ``loss_dict = model(imgs / 255, targets)`` (02_train_faster_rcnn.py:212): the focal
         classification and smooth-L1 box regression losses of RetinaNet / EfficientDet over IoU-assigned anchors.  inputs as
         forward takes them; targets one dict per image with ``boxes`` [n, 4] (x1, y1, x2, y2 in original pixels) and ``labels``
@@ -738,7 +776,10 @@ class EfficientDetBackbone(nn.Module):
         on its running statistics, whatever ``.training`` is.  compute_dtype "fp32", or "f16" (f16 forward tensors, bf16 gradients in
         flight, fp32 sums and fp32 ``.grad``; non-finite head outputs raise FloatingPointError); "bf16" raises
         NotImplementedError.  One activation set per batch size: backward before the
-        next detection_loss of that batch size (a stale-forward error otherwise).  See stlpose_amd/detector_train.py."""
+        next detection_loss of that batch size (a stale-forward error otherwise).  See stlpose_amd/detector_train.py.
+
+        ``detection_loss(batch)`` with a ``det_data.DetBatch`` (``DetBatchLoader``) and no targets: the network reads the batch's
+        canvas and stl_det_loss its ``gt`` / ``offsets`` tables; nothing is copied and no host table is built."""
         from . import detector_train
         return detector_train.detection_loss(self, inputs, targets, alpha, gamma, box_weight)
 
@@ -750,7 +791,9 @@ class EfficientDetBackbone(nn.Module):
 
     def forward(self, inputs, preprocess=True, postprocess=True, threshold=None, iou_threshold=None, output="host"):
         """output="host": the reference's list of per-image dicts of CPU tensors.  output="device": a ``detections.Detections``,
-        the same detections as device tables from one launch, with no wait for the device (``.to_list()`` gives the list)."""
+        the same detections as device tables from one launch, with no wait for the device (``.to_list()`` gives the list).
+        inputs may be a ``det_data.DetBatch``: its canvas is the network's input as it lies, and the boxes come back on the scale of
+        its S1 x S1 images."""
         self._check_mode()
         _check_output(output)
         if threshold is not None:
@@ -758,7 +801,9 @@ class EfficientDetBackbone(nn.Module):
         if iou_threshold is not None:
             self.iou_threshold = iou_threshold
         dev = torch.device("cuda", torch.cuda.current_device())
-        if preprocess:
+        if _is_det_batch(inputs):   # a det_data.DetBatch is preprocessed already, whatever `preprocess` says
+            p, metas = self.run_batch(inputs, _device(inputs.canvas.device))
+        elif preprocess:
             p, metas = self.run_raw(self._float_sources(inputs, dev), 1, dev)
         else:
             x = inputs.detach().to(dev, torch.float32)
@@ -792,7 +837,7 @@ class EfficientDetBackbone(nn.Module):
                         "scores": torch.from_numpy(scores)})
         return out
 
-    def _record_table(self, p: _Plan, metas) -> Optional[torch.Tensor]:
+    def _record_table(self, p: Optional[_Plan], metas, dev=None) -> Optional[torch.Tensor]:
         """The device table of StlDetImage records that belongs to `metas`: the one run_raw uploaded, or a new upload."""
         if metas is None:
             return None
@@ -802,10 +847,15 @@ class EfficientDetBackbone(nn.Module):
         recs = (capi.DetImage * len(metas))()
         for i, (new_w, new_h, old_w, old_h, *_) in enumerate(metas):
             recs[i] = capi.DetImage(None, 1, old_h, old_w, new_h, new_w, 0, 1.0 / (new_h / old_h), 1.0 / (new_w / old_w))
-        return torch.frombuffer(bytearray(bytes(recs)), dtype=torch.uint8).to(p.reg.device, non_blocking=True)
+        return torch.frombuffer(bytearray(bytes(recs)), dtype=torch.uint8).to(p.reg.device if dev is None else dev, non_blocking=True)
 
 
 EfficientDet = EfficientDetBackbone
+
+
+def _is_det_batch(inputs) -> bool:
+    from .det_data import DetBatch   # det_data imports this module
+    return isinstance(inputs, DetBatch)
 
 
 def _check_output(output):

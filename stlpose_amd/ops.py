@@ -973,7 +973,62 @@ def _person_boxes_fake(boxes, scores, labels, count, label, score_thr, iou_thr, 
 _define("person_boxes(Tensor boxes, Tensor scores, Tensor labels, Tensor count, int label, float score_thr, float iou_thr, float aspect, "
         "int crop_w, int crop_h) -> (Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)", _person_boxes, _person_boxes_fake)
 
+# ------------------------------------------------------------------ detector batches (csrc/det_batch.hip)
+def _det_batch(canvas, src, src_off, src_hw, index, box_start, box_count, boxes, labels, draws, flip_enabled: bool, s1: int, gt_rows: int,
+               want_stage1: bool):
+    """One launch of stl_det_batch (include/stlpose_hip_det_batch.h) into canvas, fp32 [B, S, S, 3] (a plan's, or a new tensor); every
+    shape, dtype and device the kernel relies on is checked here, nothing is read back."""
+    op = "det_batch"
+    if src.dim() != 1 or src.dtype != torch.uint8:
+        raise ValueError(f"stlpose {op}: src must be the uint8 [bytes] image buffer, got {src.dtype} {tuple(src.shape)}")
+    if not src.is_cuda:
+        raise RuntimeError(f"stlpose {op}: the image buffer must be on the GPU")
+    b = _table(op, "index", index, torch.int64, "B")
+    if not 1 <= b <= capi.DET_BATCH_MAX:
+        raise ValueError(f"stlpose {op}: {b} images in one batch (1 .. {capi.DET_BATCH_MAX})")
+    _table(op, "src_off", src_off, torch.int64, "B", b)
+    _table(op, "src_hw", src_hw, torch.int32, "B", b, (2,))
+    n = _table(op, "box_start", box_start, torch.int64, "N")
+    _table(op, "box_count", box_count, torch.int32, "N", n)
+    m = _table(op, "boxes", boxes, torch.float32, "M", None, (4,))
+    _table(op, "labels", labels, torch.int64, "M", m)
+    tabs = [("src_off", src_off), ("src_hw", src_hw), ("index", index), ("box_start", box_start), ("box_count", box_count),
+            ("boxes", boxes), ("labels", labels)]
+    if draws is not None:
+        _table(op, "draws", draws, torch.float64, "B", b)
+        tabs.append(("draws", draws))
+    if canvas.dim() != 4 or canvas.shape[1] != canvas.shape[2]:
+        raise ValueError(f"stlpose {op}: canvas must be float32 [B={b}, S, S, 3], got {canvas.dtype} {tuple(canvas.shape)}")
+    s = canvas.shape[1]
+    _table(op, "canvas", canvas, torch.float32, "B", b, (s, s, 3))
+    tabs.append(("canvas", canvas))
+    if not (1 <= s1 <= capi.DET_BATCH_SIDE and 1 <= s <= capi.DET_BATCH_SIDE) or gt_rows < 0:
+        raise ValueError(f"stlpose {op}: S1 {s1}, canvas {s} (1 .. {capi.DET_BATCH_SIDE}), gt_rows {gt_rows}")
+    dev = src.device
+    _same_device(tabs, dev)
+    for name, t in [("src", src)] + tabs:
+        if not t.is_contiguous():
+            raise ValueError(f"stlpose {op}: {name} must be contiguous")
+    stage1 = torch.empty(b if want_stage1 else 0, s1, s1, 3, dtype=torch.uint8, device=dev)
+    gt = torch.empty(gt_rows, 5, dtype=torch.float32, device=dev)
+    offsets = torch.empty(b + 1, dtype=torch.int32, device=dev)
+    capi.call("stl_det_batch", src.data_ptr(), src.numel(), src_off.data_ptr(), src_hw.data_ptr(), index.data_ptr(), _ptr(box_start),
+              _ptr(box_count), n, _ptr(boxes), _ptr(labels), m, _ptr(draws), int(bool(flip_enabled)), b, int(s1), int(s), canvas.data_ptr(),
+              stage1.data_ptr() if want_stage1 else None, gt.data_ptr() if gt_rows else None, int(gt_rows), offsets.data_ptr(), _st())
+    return stage1, gt, offsets
+
+
+def _det_batch_fake(canvas, src, src_off, src_hw, index, box_start, box_count, boxes, labels, draws, flip_enabled, s1, gt_rows, want_stage1):
+    b = index.shape[0]
+    return (src.new_empty(b if want_stage1 else 0, s1, s1, 3), boxes.new_empty(gt_rows, 5), index.new_empty(b + 1, dtype=torch.int32))
+
+
+# fills canvas; returns stage1 uint8 [B, s1, s1, 3] ([0, s1, s1, 3] unless asked for), gt fp32 [gt_rows, 5], offsets int32 [B + 1]
+_define("det_batch(Tensor(a!) canvas, Tensor src, Tensor src_off, Tensor src_hw, Tensor index, Tensor box_start, Tensor box_count, "
+        "Tensor boxes, Tensor labels, Tensor? draws, bool flip_enabled, int s1, int gt_rows, bool want_stage1) "
+        "-> (Tensor, Tensor, Tensor)", _det_batch, _det_batch_fake)
+
 OPS = ["person_mse", "heatmap_argmax", "final_preds", "flip_merge", "flip_merge_backward", "gaussian_targets", "affine_crop",
        "hrnet_forward", "hrnet_backward", "hrnet_backward_input", "pose_vectors", "pose_distances", "pose_topk", "pose_rank", "pose_rank_any",
        "box_select", "heatmap_resize_argmax", "det_decode", "det_nms", "det_loss", "box_ap_match", "box_ap_accumulate",
-       "pose_rescore_nms", "oks_ap_match", "eval_tail", "eval_affine", "pose_augment", "det_postprocess", "det_append", "person_boxes"]
+       "pose_rescore_nms", "oks_ap_match", "eval_tail", "eval_affine", "pose_augment", "det_postprocess", "det_append", "person_boxes", "det_batch"]
