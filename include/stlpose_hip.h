@@ -93,8 +93,10 @@ typedef struct stl_conv {
                               produces the last contribution to dz (HRnet.py:58-59,99-100). */
     void* src_out;         /* BNADD source: [B,Hi,Wi,Ci] dtype -- the transformed source (the block-end sum) is stored here, every
                               pixel by the one block whose tile owns it; NULL = not stored */
-    int32_t ydtype, pad_;       /* data gradient (BNBWD source) of the mixed mode: element type of the FORWARD tensors it reads -- src.y,
-                              mask_y, mask_z -- when it differs from dtype (STL_F16 with dtype STL_BF16); 0 = same as dtype */
+    int32_t ydtype, math;       /* ydtype -- data gradient (BNBWD source) of the mixed mode: element type of the FORWARD tensors it reads
+                              -- src.y, mask_y, mask_z -- when it differs from dtype (STL_F16 with dtype STL_BF16); 0 = same as dtype.
+                              math -- STL_MATH_* (stlpose_hip_math.h): how the operands are multiplied; 0 (every zero-filled
+                              descriptor) = natively, STL_MATH_BF16X3 = fp32 tensors on the bf16 matrix cores (forward launches) */
 } stl_conv;
 int stl_conv_forward(const stl_conv* p, void* stream);
 /* Fill p->shape / p->TH / p->TW once (host-side tile search) so that launches are cheap. */

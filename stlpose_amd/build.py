@@ -13,10 +13,10 @@ CSRC = os.path.join(HERE, "csrc")
 INCLUDE = os.path.join(HERE, "..", "include")
 LIB = os.path.join(HERE, "libstlpose_hip.so")
 # (source, object tag, extra flags): conv_core and wgrad are compiled once per dtype (-DSTL_DT = number of the TRANSLATION UNIT:
-# 0 fp32, 1 bf16 + C ABI, 3 f16 -- not an element-type code, STL_F16 is 2) so that their kernel
+# 0 fp32, 1 bf16 + C ABI, 3 f16, 4 fp32 multiplied as split bf16 -- not an element-type code, STL_F16 is 2) so that their kernel
 # instantiations build in parallel
 UNITS = [("capi.hip", "capi", []), ("conv_core.hip", "conv_core_bf16", ["-DSTL_DT=1"]), ("conv_core.hip", "conv_core_f32", ["-DSTL_DT=0"]),
-         ("conv_core.hip", "conv_core_f16", ["-DSTL_DT=3"]),
+         ("conv_core.hip", "conv_core_f16", ["-DSTL_DT=3"]), ("conv_core.hip", "conv_core_f32s", ["-DSTL_DT=4"]),
          ("wgrad.hip", "wgrad_bf16", ["-DSTL_DT=1"]), ("wgrad.hip", "wgrad_f32", ["-DSTL_DT=0"]), ("elementwise.hip", "elementwise", []),
          ("program.hip", "program", []), ("retrieval.hip", "retrieval", []),
          ("topdown.hip", "topdown", []), ("detector.hip", "detector", []), ("detector_train.hip", "detector_train", []),

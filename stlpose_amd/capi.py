@@ -50,6 +50,9 @@ DETECTIONS = Header(os.path.join(INCLUDE, "stlpose_hip_detections.h"))
 # include/stlpose_hip_det_batch.h: detector batches built on the device (csrc/det_batch.hip), part of the product library
 DET_BATCH = Header(os.path.join(INCLUDE, "stlpose_hip_det_batch.h"))
 globals().update({name[len("STL_"):]: value for name, value in DET_BATCH.constants.items()})   # DET_BATCH_MAX, DET_BATCH_SIDE
+# include/stlpose_hip_math.h: the values of stl_conv.math
+MATH = Header(os.path.join(INCLUDE, "stlpose_hip_math.h"))
+globals().update({name[len("STL_"):]: value for name, value in MATH.constants.items()})   # MATH_NATIVE, MATH_BF16X3
 
 DTYPES = {F32: (4, torch.float32), BF16: (2, torch.bfloat16), F16: (2, torch.float16)}   # code -> (bytes per element, torch dtype)
 
@@ -60,6 +63,17 @@ def dt2(grad_dtype: int, fwd_dtype: int) -> int:
 
 
 MIXED = dt2(BF16, F16)   # the mixed 16-bit mode: forward tensors f16, gradients bf16
+# A compute mode of the Python layer may carry an stl_conv.math value above the two element types (bits 16-23): "fp32x3" is fp32
+# tensors whose conv launches multiply split bf16 operands on the 16-bit matrix cores.  Inference only (X3_NO_GRADIENTS).
+F32X3 = F32 | (MATH_BF16X3 << 16)
+X3_NO_GRADIENTS = ("compute_dtype='fp32x3' is inference only: gradients need the third bf16 piece of each operand (the two-piece "
+                   "split is 16-30x fp32's gradient error); train and differentiate with compute_dtype=\"fp32\".")
+
+
+def math_of(code: int) -> int:
+    """The STL_MATH_* value of a compute-mode code (0 for every mode but F32X3)."""
+    return (code >> 16) & 0xff
+
 # pose retrieval
 POSE_APPROACH = {"all_kpts": POSE_ALL_KPTS, "full_body": POSE_FULL_BODY, "upper_body": POSE_UPPER_BODY}
 POSE_DIM = {"all_kpts": 34, "full_body": 26, "upper_body": 18}

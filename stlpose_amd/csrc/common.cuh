@@ -8,11 +8,13 @@
 #include <type_traits>
 #include <utility>
 #include "../../include/stlpose_hip.h"
+#include "../../include/stlpose_hip_math.h"
 
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
 typedef __attribute__((ext_vector_type(4))) short s16x4;
+struct f32s { float v; };   // fp32 as stored (STL_F32), multiplied as two bf16 pieces on the bf16 matrix cores: mma16<f32s> below
 typedef _Float16 f16;   // STL_F16: forward activations of the mixed 16-bit mode (10 mantissa bits; gradients stay bf16 for range)
 
 struct alignas(16) V16 {
@@ -45,6 +47,8 @@ struct ET<float> {
     static constexpr int CK = 16;  // channels per 64-byte K chunk
 };
 template <>
+struct ET<f32s> : ET<float> {};
+template <>
 struct ET<__bf16> {
     static constexpr int KV = 8;
     static constexpr int CK = 32;
@@ -54,6 +58,9 @@ struct ET<f16> {
     static constexpr int KV = 8;
     static constexpr int CK = 32;
 };
+// element types that exist in forward launches only (no data-gradient or weight-gradient instantiations)
+template <typename T>
+constexpr bool stl_fwd_only = std::is_same<T, f16>::value || std::is_same<T, f32s>::value;
 // dtype code (STL_F32 / STL_BF16 / STL_F16) of an element type
 template <typename T>
 constexpr int stl_code() { return sizeof(T) == 4 ? STL_F32 : (std::is_same<T, __bf16>::value ? STL_BF16 : STL_F16); }
@@ -98,6 +105,8 @@ __device__ __forceinline__ void unpack<float>(const V16& v, float* f) {
     for (int i = 0; i < 4; ++i) f[i] = __uint_as_float(v.w[i]);
 }
 template <>
+__device__ __forceinline__ void unpack<f32s>(const V16& v, float* f) { unpack<float>(v, f); }
+template <>
 __device__ __forceinline__ void unpack<__bf16>(const V16& v, float* f) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) unpack2<__bf16>(v.w[i], f[2 * i], f[2 * i + 1]);
@@ -116,6 +125,8 @@ __device__ __forceinline__ V16 pack<float>(const float* f) {
     for (int i = 0; i < 4; ++i) v.w[i] = __float_as_uint(f[i]);
     return v;
 }
+template <>
+__device__ __forceinline__ V16 pack<f32s>(const float* f) { return pack<float>(f); }
 template <>
 __device__ __forceinline__ V16 pack<__bf16>(const float* f) {
     V16 v;
@@ -136,9 +147,22 @@ __device__ __forceinline__ float round_to(float f);
 template <>
 __device__ __forceinline__ float round_to<float>(float f) { return f; }
 template <>
+__device__ __forceinline__ float round_to<f32s>(float f) { return f; }
+template <>
 __device__ __forceinline__ float round_to<__bf16>(float f) { return bf16_to_f32(f32_to_bf16(f)); }
 template <>
 __device__ __forceinline__ float round_to<f16>(float f) { return (float)(_Float16)f; }
+
+// max(v, lo) of a value headed for a tensor of T: the ReLU of every kernel (lo = 0) and its absence (lo = -inf).  On fp32 tensors --
+// the parity path, native or split -- a NaN stays a NaN, as under torch's relu (v_maximum3_f32): with fmaxf, which returns its
+// other operand, an Inf in the input (Inf * w = +-Inf, summed into NaN by the next conv) was zeroed by the ReLU behind it and
+// ended as FINITE heat maps that Evaluator's finiteness check cannot see.  Equal to fmaxf for every other operand (-0 < +0 in
+// both).  The 16-bit kernels keep fmaxf: their range guard rides on the BatchNorm sums.
+template <typename T>
+__device__ __forceinline__ float max_lo(float v, float lo) {
+    if constexpr (sizeof(T) == 4) return __builtin_elementwise_maximum(v, lo);
+    else return fmaxf(v, lo);
+}
 
 __device__ __forceinline__ V16 zero16() {
     V16 v;
@@ -166,6 +190,46 @@ __device__ __forceinline__ void mma16<float>(f32x4& acc, const V16& a, const V16
 #pragma unroll
     for (int s = 0; s < 4; ++s)
         acc = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a.w[s]), __uint_as_float(b.w[s]), acc, 0, 0, 0);
+}
+
+// fp32 operands on the bf16 matrix cores: x = hi + lo + O(2^-16 |x|) with hi = bf16_rne(x), lo = bf16_rne(x - hi), and
+// a * b ~ hi*hi + hi*lo + lo*hi (the lo*lo term, <= 2^-16 |a b|, is dropped: DESIGN.md 2a).  A 16-byte fp32 fragment is the
+// K = 16 operand of v_mfma_f32_16x16x16_bf16 as it stands: lane (lane & 15, g) holds K elements 4g .. 4g+3.
+// A pure function of the fragment, so a fragment that several MFMA steps share is split once.
+// x is clamped to bf16's finite range before hi is rounded (one v_med3_f32; the identity for every x that rounds to a finite
+// bf16): an Inf then splits into (bf16 max, Inf) and multiplies like an Inf -- with hi = Inf, lo = Inf - Inf would be NaN, which
+// poisons every output the operand reaches where the native launch gives +-Inf to those whose weight has the sign.  NaN gives lo = NaN.
+// Zero splits into (0, 0), so padded lanes stay exactly zero.
+struct BfSplit {
+    s16x4 hi, lo;
+};
+__device__ __forceinline__ BfSplit split_bf16(const V16& v) {
+    float x[4], r[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) x[i] = __uint_as_float(v.w[i]);
+    uint32_t h[2], l[2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        constexpr float BF16_MAX = 3.3895313892515355e38f;   // 0x7F7F0000
+        h[i] = pack2<__bf16>(__builtin_amdgcn_fmed3f(x[2 * i], -BF16_MAX, BF16_MAX), __builtin_amdgcn_fmed3f(x[2 * i + 1], -BF16_MAX, BF16_MAX));
+        float h0, h1;
+        unpack2<__bf16>(h[i], h0, h1);
+        r[2 * i] = x[2 * i] - h0, r[2 * i + 1] = x[2 * i + 1] - h1;   // exact for finite x: hi shares x's leading bits
+        l[i] = pack2<__bf16>(r[2 * i], r[2 * i + 1]);
+    }
+    typedef __attribute__((ext_vector_type(2))) uint32_t u2;
+    BfSplit s;
+    s.hi = __builtin_bit_cast(s16x4, (u2{h[0], h[1]}));
+    s.lo = __builtin_bit_cast(s16x4, (u2{l[0], l[1]}));
+    return s;
+}
+// smallest term first, all three on the one accumulator
+template <>
+__device__ __forceinline__ void mma16<f32s>(f32x4& acc, const V16& a, const V16& b) {
+    const BfSplit sa = split_bf16(a), sb = split_bf16(b);
+    acc = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(sa.lo, sb.hi, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(sa.hi, sb.lo, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(sa.hi, sb.hi, acc, 0, 0, 0);
 }
 
 // 1/sqrt(x) in fp32: hardware estimate + one Newton step (full fp32 accuracy, ~6 instructions; the
@@ -390,7 +454,7 @@ static inline void stl_launch(void (*kernel)(KArgs...), dim3 grid, dim3 block, s
 // "base<bf16,a0,a1,...>" for stl_note_kernel (built once per instantiation: function-local static in the launcher)
 template <typename T>
 static inline const char* stl_kname(char (&buf)[160], const char* base, std::initializer_list<int> args) {
-    int n = snprintf(buf, sizeof(buf), "%s<%s", base, sizeof(T) == 4 ? "f32" : (std::is_same<T, __bf16>::value ? "bf16" : "f16"));
+    int n = snprintf(buf, sizeof(buf), "%s<%s", base, std::is_same<T, f32s>::value ? "f32s" : sizeof(T) == 4 ? "f32" : (std::is_same<T, __bf16>::value ? "bf16" : "f16"));
     for (int a : args) n += snprintf(buf + n, sizeof(buf) - n, ",%d", a);
     snprintf(buf + n, sizeof(buf) - n, ">");
     return buf;

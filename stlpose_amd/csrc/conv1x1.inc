@@ -281,7 +281,7 @@ int run_1x1(const stl_conv& p, hipStream_t st) {
     const char* noeo = getenv("STL_CONV_NO_EO");
     const int eo = (noeo && (atoi(noeo) & 2)) ? -1 : epi_code(p);   // compile-time epilogue operand set where the planner's forms match
     if (q) {
-        if constexpr (!std::is_same<T, f16>::value) {
+        if constexpr (!stl_fwd_only<T>) {
             // (the mask_y forms, EO 1 / 7, spill 35 - 50 registers at this kernel's 128-register budget: 14.21 vs 14.06 ms per step)
             if (eo == 2) return launch_1x1<T, TY, 2, true, 4, 2>(k, grid, lds, st);
             return launch_1x1<T, TY, 2, true, 4>(k, grid, lds, st);

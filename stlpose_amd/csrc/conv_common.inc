@@ -49,7 +49,7 @@ __device__ __forceinline__ V16 xform_bn(const V16& x, const float* ca, const flo
 #pragma unroll
     for (int i = 0; i < NP; ++i) {
         const f2v t = fma2(a2[i], v[i], b2[i]);
-        u[i][0] = fmaxf(t[0], lo), u[i][1] = fmaxf(t[1], lo);
+        u[i][0] = max_lo<T>(t[0], lo), u[i][1] = max_lo<T>(t[1], lo);
     }
     return pack_pairs<T>(u);
 }
@@ -77,7 +77,7 @@ __device__ __forceinline__ V16 xform_bnadd(const V16& x, const V16& y, const flo
 #pragma unroll
     for (int i = 0; i < NP; ++i) {
         const f2v t = fma2(a2[i], v[i], b2[i]) + q[i];   // same association as the stand-alone sum kernel: BN term first, then the skip
-        u[i][0] = fmaxf(t[0], lo), u[i][1] = fmaxf(t[1], lo);
+        u[i][0] = max_lo<T>(t[0], lo), u[i][1] = max_lo<T>(t[1], lo);
     }
     return pack_pairs<T>(u);
 }
@@ -108,7 +108,7 @@ __device__ __forceinline__ V16 xform_bn_r(const V16& x, const f2v* a2, const f2v
 #pragma unroll
     for (int i = 0; i < NP; ++i) {
         const f2v t = fma2(a2[i], v[i], b2[i]);
-        u[i][0] = fmaxf(t[0], lo), u[i][1] = fmaxf(t[1], lo);
+        u[i][0] = max_lo<T>(t[0], lo), u[i][1] = max_lo<T>(t[1], lo);
     }
     return pack_pairs<T>(u);
 }
@@ -339,7 +339,7 @@ __device__ __forceinline__ void epilogue_apply(const stl_conv& p, f32x4* acc, co
         }
         if (O::orelu(p)) {
 #pragma unroll
-            for (int h = 0; h < 2; ++h) f[h][0] = fmaxf(f[h][0], 0.f), f[h][1] = fmaxf(f[h][1], 0.f);
+            for (int h = 0; h < 2; ++h) f[h][0] = max_lo<T>(f[h][0], 0.f), f[h][1] = max_lo<T>(f[h][1], 0.f);
         }
         // round to the storage type once; statistics are those of the stored values
         if constexpr (sizeof(T) == 2) {

@@ -21,8 +21,9 @@
 #include <type_traits>
 #include "common.cuh"
 
-// The file is compiled three times by stlpose_amd/build.py -- -DSTL_DT=1: the bf16 kernels + the C ABI entry points, -DSTL_DT=0: the
-// fp32 kernels, -DSTL_DT=3: the f16 forward kernels -- so that its kernel instantiations build in parallel; STL_DT=2 (default) =
+// The file is compiled four times by stlpose_amd/build.py -- -DSTL_DT=1: the bf16 kernels + the C ABI entry points, -DSTL_DT=0: the
+// fp32 kernels, -DSTL_DT=3: the f16 forward kernels, -DSTL_DT=4: the forward kernels of fp32 tensors multiplied as split bf16
+// (math = STL_MATH_BF16X3) -- so that its kernel instantiations build in parallel; STL_DT=2 (default) =
 // one unit with everything.  NOTE: STL_DT numbers TRANSLATION UNITS, not element types (the element type STL_F16 is 2, the f16
 // unit is 3): only the STL_HAS_* macros below may look at it.
 #ifndef STL_DT
@@ -31,6 +32,7 @@
 #define STL_HAS_F32 (STL_DT == 0 || STL_DT == 2)
 #define STL_HAS_BF16 (STL_DT == 1 || STL_DT == 2)   // + the C ABI entry points
 #define STL_HAS_F16 (STL_DT == 3 || STL_DT == 2)    // forward kernels of the mixed 16-bit mode (STL_F16)
+#define STL_HAS_F32S (STL_DT == 4 || STL_DT == 2)   // forward kernels of fp32 tensors on the bf16 matrix cores (f32s)
 
 struct ConvK {
     stl_conv p;
@@ -53,6 +55,7 @@ struct ConvK {
 int stl_conv_backend_bf16(int path, const stl_conv& p, const ConvK& k, int shape, int nva, dim3 grid, size_t lds, hipStream_t st);
 int stl_conv_backend_f32(int path, const stl_conv& p, const ConvK& k, int shape, int nva, dim3 grid, size_t lds, hipStream_t st);
 int stl_conv_backend_f16(int path, const stl_conv& p, const ConvK& k, int shape, int nva, dim3 grid, size_t lds, hipStream_t st);
+int stl_conv_backend_f32s(int path, const stl_conv& p, const ConvK& k, int shape, int nva, dim3 grid, size_t lds, hipStream_t st);
 
 namespace {
 
@@ -710,6 +713,10 @@ template <typename T, typename TY, int KS, bool Q, bool PE, int EO = -1>
 int dispatch(int shape, int nva, const ConvK& k, dim3 grid, size_t lds, hipStream_t st) {
     constexpr int EOC = (KS == 3 && (Q || EO == 48)) ? EO : -1;   // conv_core: data gradients and the bias + ReLU forward form (its other forward convs have the plain epilogue)
     constexpr int EOW = (KS == 3 && EO != 48) ? EO : -1;   // wave-specialised kernel: forward with statistics (EO 8) and data gradients
+    // waves per SIMD of the C <= 32 blocks with filters staged per chunk: four, three for data gradients -- and for the split-bf16
+    // 3x3 form with epilogue operands, which needs 12 - 60 bytes of scratch at the 128-register budget (the split pieces of the
+    // fragments live beside the operands)
+    constexpr int OCC4 = (Q || (std::is_same<T, f32s>::value && KS == 3 && !PE)) ? 3 : 4;
     switch (shape) {
         case 0:
             if (nva <= 3) return launch<T, TY, KS, 4, 1, 2, 4, 3, Q, PE>(k, grid, lds, st);
@@ -729,11 +736,11 @@ int dispatch(int shape, int nva, const ConvK& k, dim3 grid, size_t lds, hipStrea
             break;
         case 8:   // three (data gradient) resp. four waves per SIMD, no spills
             if (nva <= 3 && k.wres) return launch<T, TY, KS, 8, 1, 2, 2, 3, Q, PE, 4, 1, false, false, EOC>(k, grid, lds, st);
-            if (nva <= 3) return launch<T, TY, KS, 8, 1, 2, 2, 3, Q, PE, (Q ? 3 : 4)>(k, grid, lds, st);
+            if (nva <= 3) return launch<T, TY, KS, 8, 1, 2, 2, 3, Q, PE, OCC4>(k, grid, lds, st);
             break;
         case 4:
             if (nva <= 3 && k.wres) return launch<T, TY, KS, 4, 1, 2, 2, 3, Q, PE, 4, 1>(k, grid, lds, st);  // 113-123 VGPRs, no spills
-            if (nva <= 3) return launch<T, TY, KS, 4, 1, 2, 2, 3, Q, PE, (Q ? 3 : 4)>(k, grid, lds, st);
+            if (nva <= 3) return launch<T, TY, KS, 4, 1, 2, 2, 3, Q, PE, OCC4>(k, grid, lds, st);
             if (nva <= 6) return launch<T, TY, KS, 4, 1, 2, 2, 6, Q, PE, 3>(k, grid, lds, st);
             break;
         case 7:
@@ -772,7 +779,10 @@ int conv_backend(int path, const stl_conv& p, const ConvK& k, int shape, int nva
     if constexpr (std::is_same<T, f16>::value) {   // f16 tensors exist in the forward pass only
         if (q) return stl_set_error("conv: STL_F16 is a forward-tensor type; gradients are bf16 (dtype STL_BF16 + ydtype STL_F16)");
     }
-    constexpr bool FWD = std::is_same<T, TY>::value, BWD = !std::is_same<T, f16>::value;
+    if constexpr (std::is_same<T, f32s>::value) {   // checked by stl_conv_forward; here so that no gradient form is instantiated
+        if (q) return stl_set_error("conv: math = STL_MATH_BF16X3 has no data-gradient (BNBWD source) kernels");
+    }
+    constexpr bool FWD = std::is_same<T, TY>::value, BWD = !stl_fwd_only<T>;
     if (path == 0) return run_1x1<T, TY>(p, st);
     if (path == 3) {
         if constexpr (sizeof(T) == 2) return dispatch_r2<T, TY>(p, k, shape == 5 ? 0 : (shape == 6 ? 1 : 2), grid, lds, st);
@@ -941,6 +951,19 @@ Plan choose_plan(const stl_conv& p, int ck) {
 }  // namespace
 
 #if STL_HAS_BF16
+// stl_conv.math: STL_MATH_BF16X3 goes with fp32 tensors in forward launches only (the block shapes, tiles and LDS layouts are
+// the fp32 ones: the plan does not look at the field beyond this check)
+static bool math_ok(const stl_conv& p) {
+    return p.math == STL_MATH_NATIVE || (p.math == STL_MATH_BF16X3 && p.dtype == STL_F32 && p.src.mode != STL_SRC_BNBWD && !p.stuff);
+}
+static const char* math_error(const stl_conv& p, const char* who) {
+    static thread_local char buf[200];
+    if (p.math != STL_MATH_BF16X3) snprintf(buf, sizeof(buf), "%s: math %d (STL_MATH_NATIVE or STL_MATH_BF16X3)", who, p.math);
+    else if (p.dtype != STL_F32) snprintf(buf, sizeof(buf), "%s: math = STL_MATH_BF16X3 needs dtype STL_F32 (got dtype %d)", who, p.dtype);
+    else if (p.stuff) snprintf(buf, sizeof(buf), "%s: math = STL_MATH_BF16X3 does not go with stuff = 1 (a data gradient)", who);
+    else snprintf(buf, sizeof(buf), "%s: math = STL_MATH_BF16X3 does not go with a BNBWD source (src.mode, a data gradient)", who);
+    return buf;
+}
 static int ydtype_of(const stl_conv& p) { return (p.dtype == STL_BF16 && p.ydtype == STL_F16) ? STL_F16 : p.dtype; }   // 0 = same as dtype
 int stl_conv_backend_bf16(int path, const stl_conv& p, const ConvK& k, int shape, int nva, dim3 grid, size_t lds, hipStream_t st) {
     if (ydtype_of(p) == STL_F16) return conv_backend<__bf16, f16>(path, p, k, shape, nva, grid, lds, st);   // mixed-mode data gradient
@@ -955,6 +978,11 @@ int stl_conv_backend_f32(int path, const stl_conv& p, const ConvK& k, int shape,
 #if STL_HAS_F16
 int stl_conv_backend_f16(int path, const stl_conv& p, const ConvK& k, int shape, int nva, dim3 grid, size_t lds, hipStream_t st) {
     return conv_backend<f16, f16>(path, p, k, shape, nva, grid, lds, st);
+}
+#endif
+#if STL_HAS_F32S
+int stl_conv_backend_f32s(int path, const stl_conv& p, const ConvK& k, int shape, int nva, dim3 grid, size_t lds, hipStream_t st) {
+    return conv_backend<f32s, f32s>(path, p, k, shape, nva, grid, lds, st);
 }
 #endif
 
@@ -972,6 +1000,7 @@ extern "C" int stl_conv_plan(stl_conv* pp) {
     stl_conv& p = *pp;
     STL_CHECK(p.dtype == STL_F32 || p.dtype == STL_BF16 || p.dtype == STL_F16, "conv_plan: bad dtype");
     STL_CHECK((p.ks == 1 || p.ks == 3) && (p.stride == 1 || p.stride == 2) && p.Ci > 0 && p.Co > 0, "conv_plan: bad geometry");
+    STL_CHECK(math_ok(p), "%s", math_error(p, "conv_plan"));
     const int ck = p.dtype == STL_F32 ? 16 : 32;
     Plan plan = choose_plan(p, ck);
     STL_CHECK(plan.shape >= 0, "conv_plan: no tile fits LDS for %dx%d ks %d stride %d Ci %d", p.Ho, p.Wo, p.ks, p.stride, p.Ci);
@@ -992,6 +1021,7 @@ extern "C" int stl_conv_forward(const stl_conv* pp, void* stream) {
     const stl_conv& p = *pp;
     STL_CHECK(p.dtype == STL_F32 || p.dtype == STL_BF16 || p.dtype == STL_F16, "conv: bad dtype %d", p.dtype);
     STL_CHECK(p.ydtype == 0 || p.ydtype == p.dtype || (p.dtype == STL_BF16 && p.ydtype == STL_F16), "conv: ydtype %d does not go with dtype %d", p.ydtype, p.dtype);
+    STL_CHECK(math_ok(p), "%s", math_error(p, "conv"));
     STL_CHECK(p.ks == 1 || p.ks == 3, "conv: ks must be 1 or 3 (got %d)", p.ks);
     STL_CHECK(p.stride == 1 || p.stride == 2, "conv: stride must be 1 or 2");
     STL_CHECK(!(p.stuff && p.stride != 1), "conv: stuff requires stride 1");
@@ -1024,7 +1054,8 @@ extern "C" int stl_conv_forward(const stl_conv* pp, void* stream) {
     STL_CHECK(!p.red || p.mask_y, "conv: red needs mask_y");
     STL_CHECK(!p.mask_y || (p.mask_bn.gamma && p.mask_bn.beta && (p.mask_bn.stats || (p.mask_bn.rmean && p.mask_bn.rvar))), "conv: mask BN incomplete");
 
-    const auto backend = p.dtype == STL_BF16 ? stl_conv_backend_bf16 : (p.dtype == STL_F16 ? stl_conv_backend_f16 : stl_conv_backend_f32);
+    const auto backend = p.dtype == STL_BF16 ? stl_conv_backend_bf16
+                         : (p.dtype == STL_F16 ? stl_conv_backend_f16 : (p.math == STL_MATH_BF16X3 ? stl_conv_backend_f32s : stl_conv_backend_f32));
     if (use_1x1(p))  // wide 1x1 convolutions: streaming GEMM kernel (conv1x1.inc)
         return backend(0, p, ConvK{}, 0, 0, dim3(1), 0, (hipStream_t)stream);
 

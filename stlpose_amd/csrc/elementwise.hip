@@ -86,7 +86,7 @@ __global__ __launch_bounds__(256) void fuse_fwd_kernel(const stl_fuse p) {
                 for (int j = 0; j < 8; ++j) {
                     float u = fmaf(cs[(t * 2) * C + c0 + j], f[j], cs[(t * 2 + 1) * C + c0 + j]);   // one rounding, as conv_common.inc's fma2
                     // BN terms are rounded to the storage type like a materialised BN output would be
-                    f[j] = tm.src.relu ? fmaxf(u, 0.f) : u;
+                    f[j] = tm.src.relu ? max_lo<T>(u, 0.f) : u;
                 }
             }
 #pragma unroll
@@ -94,7 +94,7 @@ __global__ __launch_bounds__(256) void fuse_fwd_kernel(const stl_fuse p) {
         }
         if (p.relu) {
 #pragma unroll
-            for (int j = 0; j < 8; ++j) s[j] = fmaxf(s[j], 0.f);
+            for (int j = 0; j < 8; ++j) s[j] = max_lo<T>(s[j], 0.f);
         }
         store8<T>(p.out, (size_t)v * 8, s);
     }
@@ -144,7 +144,7 @@ __global__ __launch_bounds__(256) void fuse_flat_big_kernel(const stl_fuse p) {
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
                 const float u = fmaf(a[j], f[j], b[j]);
-                f[j] = relu ? fmaxf(u, 0.f) : u;
+                f[j] = relu ? max_lo<T>(u, 0.f) : u;
             }
         }
     };
@@ -169,7 +169,7 @@ __global__ __launch_bounds__(256) void fuse_flat_big_kernel(const stl_fuse p) {
         }
         if (p.relu) {
 #pragma unroll
-            for (int j = 0; j < 8; ++j) s[j] = fmaxf(s[j], 0.f);
+            for (int j = 0; j < 8; ++j) s[j] = max_lo<T>(s[j], 0.f);
         }
         store8<T>(p.out, (size_t)v * 8, s);
         if (hw) {
@@ -183,7 +183,7 @@ __global__ __launch_bounds__(256) void fuse_flat_big_kernel(const stl_fuse p) {
             }
             if (p.relu) {
 #pragma unroll
-                for (int j = 0; j < 8; ++j) s[j] = fmaxf(s[j], 0.f);
+                for (int j = 0; j < 8; ++j) s[j] = max_lo<T>(s[j], 0.f);
             }
             store8<T>(p.out, (size_t)w * 8, s);
         }

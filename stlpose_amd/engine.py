@@ -229,6 +229,9 @@ class Engine:
         # weights): f16 in the mixed mode -- BatchNorm bounds their range, and 10 mantissa bits instead of 7 cut the distance
         # from the fp32 reference; gradients have no such bound and stay bf16.
         self.dtype_code = dtype
+        self.math = capi.math_of(dtype)   # stl_conv.math of every forward conv launch (capi.F32X3: the fp32 plan, split-bf16 products)
+        if self.math and (training or input_grad):
+            raise NotImplementedError("stlpose_amd.Engine: " + capi.X3_NO_GRADIENTS)
         self.dtype, self.fdtype = dtype & 0xff, ((dtype >> 8) & 0xff) or (dtype & 0xff)
         self.ydtype = self.fdtype if self.fdtype != self.dtype else 0   # what the backward descriptors carry (0 = same)
         self.training = training
@@ -393,6 +396,7 @@ class Engine:
         p.dtype = self.fdtype
         p.B, p.Hi, p.Wi, p.Ci, p.Ho, p.Wo, p.Co = x.B, x.H, x.W, x.C, Ho, Wo, cout
         p.ks, p.stride, p.stuff = kks, kstride, 0
+        p.math = self.math
         p.TH, p.TW, p.shape = 0, 0, -1
         capi.call("stl_conv_plan", C.byref(p))  # block shape + pixel tile, searched once
         reads, writes = [x.ptr], [y.ptr]

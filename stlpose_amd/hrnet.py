@@ -22,6 +22,10 @@ against a pose loss):
 Everything between input and output runs in the hand-written HIP kernels of
 ``libstlpose_hip.so`` through the static plans of ``engine.py``; there is no torch.nn compute and
 no CPU fallback (a CPU tensor raises).
+
+``compute_dtype`` (or ``STLPOSE_DTYPE``): "mixed" (default), "bf16", "fp32", or "fp32x3" -- the fp32 plan with every conv launch
+multiplying split bf16 operands on the 16-bit matrix cores (``stl_conv.math = STL_MATH_BF16X3``): heat maps within the fp32
+parity bar, eval-mode forward only (training mode and ``img.requires_grad`` raise ``NotImplementedError``).
 """
 from __future__ import annotations
 
@@ -56,9 +60,11 @@ def _dtype_code(name: str) -> int:
         return capi.BF16
     if name in ("fp32", "f32", "float32"):
         return capi.F32
+    if name in ("fp32x3", "f32x3"):   # fp32 tensors, convs multiplied as split bf16 (capi.F32X3): inference only
+        return capi.F32X3
     if name in ("mixed", "f16bf16", "fp16bf16"):   # forward tensors f16, gradients bf16 (capi.MIXED)
         return capi.MIXED
-    raise ValueError(f"compute_dtype must be 'mixed', 'bf16' or 'fp32', got {name!r}")
+    raise ValueError(f"compute_dtype must be 'mixed', 'bf16', 'fp32' or 'fp32x3', got {name!r}")
 
 
 def norm_device(device) -> torch.device:
@@ -264,6 +270,8 @@ class PoseHighResolutionNet(nn.Module):
             self._pack(x.device)
         B, _, H, W = x.shape
         want_dimg = torch.is_grad_enabled() and x.requires_grad
+        if capi.math_of(self.compute_dtype) and (self.training or want_dimg):
+            raise NotImplementedError("stlpose_amd.PoseHighResolutionNet: " + capi.X3_NO_GRADIENTS)
         if self.training and torch.is_grad_enabled():
             return _Fn.apply(x, self._anchor, self, self.engine(B, H, W, True, want_dimg))
         if want_dimg:

@@ -27,6 +27,8 @@ class TrainStep:
                  momentum: float = 0.9, nesterov: bool = False, process_group=None, bucket_mb: float = 32.0,
                  use_graph: bool = True, device=None, bf16_buckets: Optional[bool] = None):
         self.model = model
+        if capi.math_of(model.compute_dtype):
+            raise NotImplementedError("stlpose_amd.TrainStep: " + capi.X3_NO_GRADIENTS)
         from .hrnet import norm_device
         dev = norm_device(device or "cuda")
         if not model._packed(dev):

@@ -30,7 +30,8 @@ from typing import Iterable, Optional
 import numpy as np
 import torch
 
-from .hrnet import PoseHighResolutionNet, norm_device
+from . import capi
+from .hrnet import PoseHighResolutionNet, _dtype_code, norm_device
 from .inference import forward_pass
 from .loss import PersonMSELoss, perceptual_affine
 from .pose_parsing import accuracy
@@ -75,6 +76,8 @@ class Trainer:
         self.train_loader, self.valid_loader = train_loader, valid_loader
         self.batch_size = int(batch_size)
         self.arch, self.compute_dtype = arch, compute_dtype
+        if capi.math_of(_dtype_code(compute_dtype)):
+            raise NotImplementedError("stlpose_amd.Trainer: " + capi.X3_NO_GRADIENTS)
         self.checkpoint, self.resume_training = checkpoint, resume_training
         self.pg, self.device = process_group, norm_device(device)
         self.rank, self.world = 0, 1

@@ -42,8 +42,17 @@ VGG16_LAYOUT = [
 SLICE_END = {1: 0, 3: 1, 6: 2, 9: 3}  # conv position (0-based) -> slice that ends after it
 
 
-def dtype_code(name: str) -> int:
+def dtype_code(name: str, x3: bool = False) -> int:
+    """Element type the activations are stored in.  "fp32x3" (fp32 storage, conv launches with ``math_code``'s value) is for the
+    modules that say so with `x3`; the others multiply fp32 natively and refuse the name."""
+    if name.lower() in ("fp32x3", "f32x3") and not x3:
+        raise ValueError(f"compute_dtype {name!r} is VGGPerceptualLoss's and the pose network's; this module takes 'fp32' or 'bf16'")
     return capi.BF16 if name.lower() in ("bf16", "bfloat16") else capi.F32
+
+
+def math_code(name: str) -> int:
+    """``stl_conv.math`` of a compute mode: split-bf16 products for "fp32x3", the element type's own for every other."""
+    return capi.MATH_BF16X3 if name.lower() in ("fp32x3", "f32x3") else capi.MATH_NATIVE
 
 
 def add_conv(parent: nn.Module, idx: int, ci: int, co: int, ks: int = 3) -> nn.Module:
@@ -104,9 +113,10 @@ def prep_weights(dt: int, w_flat, wk, wtab_dev, n: int, blocks: int, stream: int
     capi.call("stl_weight_prep", dt, w_flat.data_ptr(), wk.data_ptr(), wtab_dev.data_ptr(), n, blocks, stream)
 
 
-def list_conv(ops: LaunchList, dt: int, B, h, w, ci, co, ks, src, wptr, out, bias=0, out_relu=0, addend=0, mask_z=0) -> None:
+def list_conv(ops: LaunchList, dt: int, B, h, w, ci, co, ks, src, wptr, out, bias=0, out_relu=0, addend=0, mask_z=0, math=0) -> None:
     """List a stride-1 'same' conv of the NHWC map at `src` onto `out` in `ops`."""
     p = capi.Conv()
+    p.math = math
     p.dtype, p.B, p.Hi, p.Wi, p.Ci, p.Ho, p.Wo, p.Co = dt, B, h, w, ci, h, w, co
     p.ks, p.stride, p.shape = ks, 1, -1
     p.src.x, p.src.mode = src, capi.SRC_PLAIN
@@ -127,6 +137,7 @@ class Trunk:
         self.ops = LaunchList()
         self.keep, self.acts, self.dims = self.ops.keep, [], []   # acts, dims: per conv its output [nb, h, w, co], (h, w, co)
         self.dt = mod.dtype
+        self.math = getattr(mod, "math", capi.MATH_NATIVE)   # VGGPerceptualLoss(compute_dtype="fp32x3"): on every conv launch
         self.esz, self.tdt = capi.DTYPES[self.dt]
         self.w_flat = mod.w_flat
         self.img = torch.zeros(nb, 3, H, W, device=dev)
@@ -149,7 +160,7 @@ class Trunk:
                 x, h, w = y, h // 2, w // 2
             y = act(nb, h, w, co)
             list_conv(self.ops, self.dt, nb, h, w, c, co, 1 if i == 0 else 3, x.data_ptr(), self.wk.data_ptr() + self.tab[i].fwd_off * self.esz,
-                      y.data_ptr(), bias=mod.bias_flat.data_ptr() + 4 * mod.bias_off[i], out_relu=1)
+                      y.data_ptr(), bias=mod.bias_flat.data_ptr() + 4 * mod.bias_off[i], out_relu=1, math=self.math)
             x, c = y, co
             self.acts.append(y)
             self.dims.append((h, w, c))
@@ -165,7 +176,7 @@ class VGGPerceptualLoss(nn.Module):
                  compute_dtype: str = "fp32"):
         super().__init__()
         self.resize = resize
-        self.dtype = dtype_code(compute_dtype)
+        self.dtype, self.math = dtype_code(compute_dtype, x3=True), math_code(compute_dtype)
         self.blocks = nn.ModuleList([nn.Module() for _ in range(4)])  # reference: self.blocks[s][features idx]
         self._convs = [add_conv(self.blocks[s], idx, ci, co) for s, idx, ci, co, _ in VGG16_LAYOUT]
         self.mean = nn.Parameter(torch.tensor([0.485, 0.456, 0.406]).view(1, 3, 1, 1))   # loss.py:37

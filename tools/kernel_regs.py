@@ -17,8 +17,8 @@ def demangle(n):
     if not rest.startswith("I"):
         return base
     args = []
-    for a in re.findall(r"DF16b|Lin\d+E|Li\d+E|Lb[01]E|f", rest[1:rest.index("EEv") + 1] if "EEv" in rest else rest[1:]):
-        args.append("bf16" if a == "DF16b" else "f32" if a == "f" else ("-" + a[3:-1]) if a.startswith("Lin") else a[2:-1])
+    for a in re.findall(r"DF16b|4f32s|S1_|Lin\d+E|Li\d+E|Lb[01]E|f", rest[1:rest.index("EEv") + 1] if "EEv" in rest else rest[1:]):
+        args.append("bf16" if a == "DF16b" else "f32s" if a in ("4f32s", "S1_") else "f32" if a == "f" else ("-" + a[3:-1]) if a.startswith("Lin") else a[2:-1])
     return base + "<" + ",".join(args) + ">"
 names = [demangle(r[0]) for r in rows]
 print("vgpr agpr sgpr scratch occ spill  kernel")
