@@ -50,6 +50,10 @@ DETECTIONS = Header(os.path.join(INCLUDE, "stlpose_hip_detections.h"))
 # include/stlpose_hip_det_batch.h: detector batches built on the device (csrc/det_batch.hip), part of the product library
 DET_BATCH = Header(os.path.join(INCLUDE, "stlpose_hip_det_batch.h"))
 globals().update({name[len("STL_"):]: value for name, value in DET_BATCH.constants.items()})   # DET_BATCH_MAX, DET_BATCH_SIDE
+# include/stlpose_hip_det_bifpn.h: the BiFPN node's backward (csrc/detector_bifpn.hip), part of the product library; it takes
+# StlDetFuse from stlpose_hip.h
+DET_BIFPN = Header(os.path.join(INCLUDE, "stlpose_hip_det_bifpn.h"), {"StlDetFuseBwd": "DetFuseBwd"}, base=HEADER)
+DetFuseBwd = DET_BIFPN.structs["StlDetFuseBwd"]
 # include/stlpose_hip_math.h: the values of stl_conv.math
 MATH = Header(os.path.join(INCLUDE, "stlpose_hip_math.h"))
 globals().update({name[len("STL_"):]: value for name, value in MATH.constants.items()})   # MATH_NATIVE, MATH_BF16X3
@@ -102,7 +106,7 @@ def lib() -> C.CDLL:
         for name, args in SIGNATURES.items():
             fn = getattr(l, name)  # AttributeError if the library lacks a symbol of the header
             fn.argtypes, fn.restype = args, RESTYPES[name]
-        for header in (DETECTIONS, DET_BATCH):
+        for header in (DETECTIONS, DET_BATCH, DET_BIFPN):
             for name, args in header.signatures.items():
                 fn = getattr(l, name)
                 fn.argtypes, fn.restype = args, header.restypes[name]

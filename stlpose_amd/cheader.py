@@ -2,6 +2,7 @@
 become Python ints, ``ctypes.Structure`` classes and argtypes / restypes.  No compiler and no preprocessor run: whatever is outside
 that subset raises ``SyntaxError`` with its line, so a header edit the reader does not understand cannot drop a symbol quietly."""
 import ctypes as C
+import os
 import re
 
 SCALARS = {"int": C.c_int32, "int32_t": C.c_int32, "int64_t": C.c_int64, "float": C.c_float, "double": C.c_double,
@@ -19,12 +20,17 @@ _MORE = re.compile(r"(\w+)\s*(?:\[(\w+)\])?")   # the later declarators of one m
 
 
 class Header:
-    def __init__(self, path, class_names=None, device_records=()):
+    def __init__(self, path, class_names=None, device_records=(), base=None):
         """``class_names``: C struct name -> Python class name (default: the C name).  ``device_records``: the structs that live in
-        device tables, so that a pointer to one is a raw address (``c_void_p``) and not ``POINTER(Class)``."""
+        device tables, so that a pointer to one is a raw address (``c_void_p``) and not ``POINTER(Class)``.  ``base``: the Header of
+        the one file this header may ``#include "..."``: its structs (the same classes) and constants are known here, and
+        ``structs`` / ``constants`` then hold them too."""
         self.path, self.class_names, self.device_records = path, class_names or {}, tuple(device_records)
-        self.constants = {}                        # "STL_NAME" -> int
-        self.structs = {}                          # C name -> ctypes.Structure subclass, in header order
+        self.base = base
+        self.constants = dict(base.constants) if base else {}   # "STL_NAME" -> int
+        self.structs = dict(base.structs) if base else {}       # C name -> ctypes.Structure subclass, in header order
+        if base:
+            self.device_records += tuple(base.device_records)
         self.signatures, self.restypes = {}, {}    # function name -> argtypes list / restype
         with open(path) as f:   # comments go, their line breaks stay: errors name the header's own line
             text = re.sub(r"/\*.*?\*/", lambda m: " " + "\n" * m.group().count("\n"), f.read(), flags=re.S)
@@ -51,7 +57,7 @@ class Header:
             if not re.fullmatch(r"[\d\s()<+*|-]+", m.group(3)):
                 self._fail(n, "not an integer expression")
             self.constants[m.group(1)] = int(eval(m.group(3), {"__builtins__": {}}))
-        elif not m and not _GUARD.fullmatch(s):
+        elif not m and not _GUARD.fullmatch(s) and not (self.base and s == f'#include "{os.path.basename(self.base.path)}"'):
             self._fail(n)
         return s == "#ifdef __cplusplus"
 

@@ -15,6 +15,17 @@ level) from the header down through csrc/detector_train.hip and produces gradien
 ops, and the weights shared by the five levels sum their five contributions.  The first depthwise layer of a (head, level) reads
 a frozen feature map: no data gradient is computed for it.
 
+``model.set_train_bifpn(k)`` (1 <= k <= cells - 1) trains the last k BiFPN cells with the heads, fp32 only.  The forward is not
+touched: the inference plan keeps every map (``_Plan.cells``), and the backward recomputes each node's pre-activation from them.
+Then the first depthwise layer of every (head, level) also computes its data gradient (stl_det_dwconv_bwd_data without z), the two
+heads' gradients of a level are added regressor first, each times the gradient of its own loss (stl_det_grad_add reads the two
+scalars on the device), and the cells run in reverse, the nodes of a cell in the reverse of the forward order.  Every consumer of a
+map comes later in the forward order, so a map's gradient is complete when its node is reached; the first contribution writes, the
+later ones accumulate, in that fixed order.  Per node: the pointwise layer's weight and data gradient (x = d), the depthwise
+layer's weight gradient (x = f) and data gradient, then stl_det_fuse_bwd (csrc/detector_bifpn.hip), whose destinations are null for
+the frozen inputs of the first trainable cell.  ``cell_raw_grads`` carries the folded gradients to the raw parameters: ``fold_chain``
+for the pointwise layer and its BN, ``fusion_weight_grads`` for ``p*_w1`` / ``p*_w2``.
+
 A model with ``compute_dtype="f16"`` trains in 16 bit, by the recipe of the pose network's mixed mode: the trunk runs as the 16-bit
 inference plan's launches, the heads' forward tensors (every depthwise output d, pre-activation z and swish output t) are f16, the
 gradients in flight are bf16, every sum is fp32, and the folded gradients come out in the same fp32 ``grads`` tensors, so
@@ -30,7 +41,7 @@ import numpy as np
 import torch
 
 from . import capi, ops
-from .efficientdet import MAX_SIZE, _device, _is_det_batch, list_dwconv, list_pointwise, resize_meta
+from .efficientdet import MAX_SIZE, _BiFPN, _device, _is_det_batch, list_dwconv, list_pointwise, resize_meta
 from .launch import LaunchList
 
 HEADS = ("regressor", "classifier")
@@ -115,6 +126,13 @@ class HeadTrain:
         self.pw_part = torch.empty(getattr(lib, self._name("stl_det_pointwise_bwd_slabs"))(m0) * (c * kmax + kmax), device=dev)
         self.dw_part = torch.empty(getattr(lib, self._name("stl_det_dwconv_bwd_parts"))(m0) * 9 * c, device=dev)
         self.grads: Dict[str, Dict[str, torch.Tensor]] = {}
+        self.ncells = ncells = m.train_bifpn   # the trailing BiFPN cells that train with the heads
+        if ncells:
+            assert not self.h16, "the BiFPN cells train in fp32 only"
+            # the gradient of every node output of the trainable cells, by the address of the plan's map
+            self.gmap = {y.data_ptr(): torch.empty_like(y) for kept in plan.cells[len(plan.cells) - ncells:] for _, _, y, _, _ in kept.values()}
+            self.hc = [torch.empty_like(f) for f, _ in plan.feats]   # the classifier's gradient of each level (the regressor's goes to gmap)
+            self.scale = torch.ones(2, device=dev)                   # the gradients of (regression, classification): _DetLossFn.backward
         for name, out, k, act in (("regressor", self.reg, 4, 0), ("classifier", self.cls, nc, 2)):
             lay, n = L[name], self.nlayers
             g = dict(pw_w=torch.empty(5, n, c, c, device=dev), pw_b=torch.empty(5, n, c, device=dev),
@@ -141,8 +159,42 @@ class HeadTrain:
                 self._dw_bwd(t[n], self.ga, plan._w(lay["hdw"]), g["hdw"][lv], z[n - 1], self.gb, hh)
                 for i in range(n - 1, -1, -1):
                     self._pw_bwd(plan, d[i], self.gb, self.ga, M, hh * hh, c, c, lay["pw"][lv][i], g["pw_w"][lv, i], g["pw_b"][lv, i])
-                    self._dw_bwd(t[i], self.ga, plan._w(lay["dw"][i]), g["dw"][lv, i], z[i - 1] if i else None, self.gb if i else None, hh)
+                    dx0 = None if not ncells else (self.gmap[f.data_ptr()] if name == "regressor" else self.hc[lv])
+                    self._dw_bwd(t[i], self.ga, plan._w(lay["dw"][i]), g["dw"][lv, i], z[i - 1] if i else None, self.gb if i else dx0, hh)
                 aoff += hh * hh * 9
+        if ncells:
+            self._cells_bwd(plan, L)
+
+    def _cells_bwd(self, plan, L) -> None:
+        """The backward launches of the trainable cells, behind the heads'."""
+        B, c, dev = self.B, self.c, self.dev
+        written = set()   # the maps whose gradient has its first contribution
+        for lv, (f, _) in enumerate(plan.feats):
+            g = self.gmap[f.data_ptr()]
+            self.bwd.add("stl_det_grad_add", g, self.hc[lv], self.scale, self.scale[1:], g, g.numel())
+            written.add(f.data_ptr())
+        self.fuse_ws = torch.empty(capi.lib().stl_det_fuse_bwd_workspace(self.ga.numel()), device=dev)
+        first = len(plan.cells) - self.ncells
+        self.cgrads = {}
+        for j in range(len(plan.cells) - 1, first - 1, -1):
+            lay, kept = L["bifpn"][j], plan.cells[j]
+            for name in reversed(_BiFPN.NODES):   # the forward runs them in this tuple's order
+                f, d, y, desc, terms = kept[name]
+                assert y.data_ptr() in written, (j, name)
+                h = y.shape[1]
+                g = dict(pw_w=torch.empty(c, c, device=dev), pw_b=torch.empty(c, device=dev), dw=torch.empty(3, 3, c, device=dev),
+                         what=torch.zeros(3, device=dev))
+                self.cgrads[j, name] = g
+                self._pw_bwd(plan, d, self.gmap[y.data_ptr()], self.ga, B * h * h, h * h, c, c, lay[name][1], g["pw_w"], g["pw_b"])
+                self._dw_bwd(f, self.ga, plan._w(lay[name][0]), g["dw"], None, self.gb, h)
+                fb = capi.DetFuseBwd()
+                for i, t in enumerate(terms):   # a term outside gmap is an input of the first trainable cell: frozen
+                    dst = self.gmap.get(t.data_ptr())
+                    if dst is not None:
+                        fb.dx[i], fb.accumulate[i] = dst.data_ptr(), int(t.data_ptr() in written)
+                        written.add(t.data_ptr())
+                self.bwd.keep_alive(f, d, y, *terms)   # the descriptors hold their addresses
+                self.bwd.add("stl_det_fuse_bwd", desc, self.gb, fb, self.fuse_ws, g["what"])
 
     def _name(self, name: str) -> str:
         return NAME16[name] if self.h16 else name
@@ -188,6 +240,40 @@ def head_parameters(m) -> List[Tuple[str, torch.nn.Parameter]]:
     return [(f"{h}.{n}", p) for h in HEADS for n, p in getattr(m, h).named_parameters()]
 
 
+def trainable_parameters(m) -> List[Tuple[str, torch.nn.Parameter]]:
+    """What detection_loss differentiates: the parameters of the last ``m.train_bifpn`` BiFPN cells in state_dict order, then
+    head_parameters(m)."""
+    k = getattr(m, "train_bifpn", 0)
+    n = len(m.bifpn) if k else 0
+    cells = [(f"bifpn.{j}.{name}", p) for j in range(n - k, n) for name, p in m.bifpn[j].named_parameters()]
+    return cells + head_parameters(m)
+
+
+def fusion_weight_grads(p: torch.Tensor, dwhat: torch.Tensor, eps: float = 1e-4) -> torch.Tensor:
+    """The gradient of a node's raw fusion weights p [n] from that of the normalised w^_i = relu(p_i) / (sum_j relu(p_j) + eps):
+    dL/dp_j = dw^_j / S - sum_i dw^_i relu(p_i) / S^2 with S = sum relu(p) + eps where p_j > 0, and 0 where p_j <= 0."""
+    r = torch.relu(p)
+    S = r.sum() + eps
+    return torch.where(p > 0, dwhat / S - (dwhat * r).sum() / (S * S), torch.zeros_like(p))
+
+
+def cell_raw_grads(m, tr: HeadTrain) -> Dict[str, torch.Tensor]:
+    """{parameter name: gradient} of every parameter of the trainable BiFPN cells from the folded per-node gradients of tr."""
+    out = {}
+    for (j, node), g in tr.cgrads.items():
+        sep, pre = getattr(m.bifpn[j], node), f"bifpn.{j}.{node}."
+        out[pre + "depthwise_conv.conv.weight"] = g["dw"].permute(2, 0, 1)[:, None]
+        pw, bn = sep.pointwise_conv.conv, sep.bn
+        W, b = pw.weight.detach().reshape(pw.out_channels, pw.in_channels), pw.bias.detach()
+        dW, db, dgam, dbeta = fold_chain(W, b, bn.weight.detach(), bn.running_mean, bn.running_var, bn.eps, g["pw_w"].t(), g["pw_b"])
+        out[pre + "pointwise_conv.conv.weight"], out[pre + "pointwise_conv.conv.bias"] = dW[:, :, None, None], db
+        out[pre + "bn.weight"], out[pre + "bn.bias"] = dgam, dbeta.clone()
+        wname = dict(zip(_BiFPN.NODES, _BiFPN.WEIGHTS))[node][0]
+        p = getattr(m.bifpn[j], wname).detach()
+        out[f"bifpn.{j}.{wname}"] = fusion_weight_grads(p, g["what"][:p.numel()])
+    return out
+
+
 def raw_grads(m, tr: HeadTrain) -> Dict[str, torch.Tensor]:
     """{parameter name: gradient} of every regressor.* / classifier.* parameter from the folded per-level gradients of tr."""
     out = {}
@@ -213,8 +299,8 @@ def raw_grads(m, tr: HeadTrain) -> Dict[str, torch.Tensor]:
 
 
 class _DetLossFn(torch.autograd.Function):
-    """(classification, regression) as functions of the head parameters: forward hands out the losses stl_det_loss computed,
-    backward runs the heads' backward launches and the folded-to-raw chain."""
+    """(classification, regression) as functions of trainable_parameters: forward hands out the losses stl_det_loss computed,
+    backward runs the backward launches (the heads', then the trainable cells') and the folded-to-raw chain."""
 
     @staticmethod
     def forward(ctx, m, tr, names, losses, *params):
@@ -231,10 +317,15 @@ class _DetLossFn(torch.autograd.Function):
                 "were overwritten (the reference's autograd keeps one set per call; this engine keeps one per plan).  Call "
                 "backward before the next detection_loss of the same batch size.")
         with torch.no_grad():
+            if tr.ncells:   # the cells' gradients are linear in both: stl_det_grad_add scales the heads' two contributions
+                tr.scale.copy_(torch.stack([gr, gc]))
             tr.backward(ops._st())
             grads = raw_grads(ctx.m, tr)
             scale = {"regressor": gr, "classifier": gc}   # dreg / dlogit are the gradients of the regression / classification loss
-            out = [grads[n].contiguous() * scale[n.split(".", 1)[0]] for n in ctx.names]
+            out = [grads[n].contiguous() * scale[n.split(".", 1)[0]] for n in ctx.names if not n.startswith("bifpn.")]
+            if tr.ncells:
+                cells = cell_raw_grads(ctx.m, tr)
+                out = [cells[n].contiguous() for n in ctx.names if n.startswith("bifpn.")] + out
         return (None, None, None, None, *out)
 
 
@@ -243,6 +334,9 @@ def detection_loss(m, inputs, targets, alpha: float = 0.25, gamma: float = 2.0, 
     if m.compute_dtype not in ("fp32", "f16"):
         raise NotImplementedError(f"EfficientDet.detection_loss: compute_dtype {m.compute_dtype!r}; the heads train in \"fp32\" or "
                                   "\"f16\" (f16 forward, bf16 gradients)")
+    if m.train_bifpn and m.compute_dtype != "fp32":
+        raise NotImplementedError(f"EfficientDet.detection_loss: compute_dtype {m.compute_dtype!r} with train_bifpn = {m.train_bifpn}; "
+                                  "the BiFPN cells train in \"fp32\" only (16-bit models train their heads: set_train_bifpn(0))")
     st = ops._st()
     if _is_det_batch(inputs):   # det_data.DetBatch: the canvas and the ground-truth table are on the device already
         if targets is not None:
@@ -258,7 +352,7 @@ def detection_loss(m, inputs, targets, alpha: float = 0.25, gamma: float = 2.0, 
             p, _, keep = m._preprocess(srcs, 1, dev)
         canvas, gt_dev, offsets_dev = None, torch.from_numpy(gt).to(dev), torch.from_numpy(offsets).to(dev)
     with torch.no_grad():
-        if p.train is None:
+        if p.train is None or p.train.ncells != m.train_bifpn:
             p.train = HeadTrain(m, p)
         tr = p.train
         p.run(st, upto=p.head_start, canvas=canvas)
@@ -271,6 +365,6 @@ def detection_loss(m, inputs, targets, alpha: float = 0.25, gamma: float = 2.0, 
                                                                 float(gamma), float(box_weight))
         tr.set_grads(dreg, dlogit)
         tr.npos = npos
-    named = head_parameters(m)
+    named = trainable_parameters(m)
     c, r = _DetLossFn.apply(m, tr, [n for n, _ in named], losses, *[q for _, q in named])
     return {"classification": c, "regression": r}

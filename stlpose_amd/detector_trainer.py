@@ -9,8 +9,10 @@
     with the batch's ``perceptual_loss``, the skip of a zero or non-finite loss, ``zero_grad / backward / step``.  The skip reads the
     loss scalar: ONE host wait per step, as the reference has it (``loss.item()``, ``:220``); everything else of the step is enqueued
     without waiting;
-  * ``setup_optimizer`` (``lib/model_setup.py:109-159``) over ``detector_train.head_parameters(model)`` -- the parameters
-    ``detection_loss`` trains; the backbone and the BiFPN are frozen: Adam, or SGD with momentum, nesterov and weight decay 0.0005;
+  * ``setup_optimizer`` (``lib/model_setup.py:109-159``) over ``detector_train.trainable_parameters(model)`` -- the parameters
+    ``detection_loss`` trains: the heads, and with ``exp_data["training"]["train_bifpn"] = k`` (default 0, applied to the model by
+    ``set_train_bifpn``) the last k BiFPN cells; everything before them is frozen: Adam, or SGD with momentum, nesterov and weight
+    decay 0.0005;
     ``ReduceLROnPlateau(mode="max", min_lr=1e-8)``, ``StepLR`` or no scheduler;
   * ``detector_logs.json`` as ``create_ / load_ / update_detector_logs`` write it (``lib/utils.py:244-301``);
   * checkpoints ``<exp>/models/detector/checkpoint_epoch_{k|final}.pth`` with the four keys of ``save_checkpoint``
@@ -34,7 +36,7 @@ import numpy as np
 import torch
 
 from .detection_eval import DetectorEvaluator, GroundTruth
-from .detector_train import head_parameters
+from .detector_train import trainable_parameters
 from .loss import apply_perceptual_loss
 
 LOGS_FILE = "detector_logs.json"
@@ -106,7 +108,10 @@ class DetectorTrainer:
         self.cur_epoch, self.skipped = 0, 0
         self.train_loss, self.valid_ap, self.valid_stats = float("nan"), -1.0, None
         self.model.to(self.device).eval()
-        self.optimizer, self.scheduler = setup_optimizer(exp_data, [p for _, p in head_parameters(model)])
+        k = int(tr.get("train_bifpn", 0))
+        if k != getattr(self.model, "train_bifpn", 0):   # (a model without that stage takes 0 only)
+            self.model.set_train_bifpn(k)
+        self.optimizer, self.scheduler = setup_optimizer(exp_data, [p for _, p in trainable_parameters(model)])
         self.evaluator = DetectorEvaluator(model, device=self.device, output=output)
         self.gt = coco_gt if isinstance(coco_gt, GroundTruth) else self._ground_truth(coco_gt)
         os.makedirs(self.save_dir, exist_ok=True)

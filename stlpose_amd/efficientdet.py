@@ -6,8 +6,8 @@
 inference only (``detection_loss`` fine-tunes the heads, see below) and runs every layer through csrc/detector.hip (NHWC): the preprocess kernel, the stem, depthwise and
 squeeze-excitation kernels, the pointwise GEMM on MFMA with BN folded into its weights, the BiFPN node kernel, the shared
 heads writing straight into the concatenated outputs, the decode kernel and the class-aware NMS.  BN is folded into packed fp32
-weights on the device and refolded when any parameter or buffer changes (only the heads' pieces, in place, when only
-``regressor.*`` / ``classifier.*`` changed: an optimiser step of the fine-tuning keeps the plans); the launches of one batch size
+weights on the device and refolded when any parameter or buffer changes (only the tail of the buffer, in place, when only the
+trainable BiFPN cells or ``regressor.*`` / ``classifier.*`` changed: an optimiser step of the fine-tuning keeps the plans); the launches of one batch size
 are listed once (``_Plan``) and replayed; the last MAX_PLANS batch sizes keep their plans.  Only the kept boxes, scores and labels reach the host.
 
 ``compute_dtype`` is "fp32" (the default), "bf16" or "f16".  Parameters, buffers and ``state_dict()`` are fp32 in every mode and
@@ -21,7 +21,9 @@ value raises FloatingPointError (activations left f16's range: use "bf16"), as H
 stlpose_amd/detector_train.py, csrc/detector_train.hip) is the first stage of
 EfficientDet fine-tuning, the counterpart of ``loss_dict = model(imgs / 255, targets)`` in ``02_train_faster_rcnn.py:212``: the
 backbone and the BiFPN are frozen, every BN stays on its running statistics, and ``sum(loss_dict.values()).backward()`` fills
-``.grad`` of the ``regressor.*`` and ``classifier.*`` parameters.
+``.grad`` of the ``regressor.*`` and ``classifier.*`` parameters.  ``set_train_bifpn(k)`` (fp32) is the next stage: the last k BiFPN
+cells, 1 <= k <= cells - 1, train with the heads (csrc/detector_bifpn.hip; ``detector_train.trainable_parameters``); the first cell and
+the backbone stay frozen.
 """
 from __future__ import annotations
 
@@ -347,8 +349,9 @@ def list_pointwise(ops: LaunchList, code: int, fields, out_f32, z=None) -> None:
     ops.add(*((name, p) if z is None else (train, p, z)))
 
 
-def list_fuse(ops: LaunchList, code: int, out, terms, wparam) -> None:
-    """The BiFPN node `out` [B, H, W, C] = fast-normalised sum of terms [(map, mode)] (wparam None: a plain resample)."""
+def list_fuse(ops: LaunchList, code: int, out, terms, wparam):
+    """The BiFPN node `out` [B, H, W, C] = fast-normalised sum of terms [(map, mode)] (wparam None: a plain resample).  Returns the
+    listed descriptor."""
     f = capi.DetFuse()
     f.B, f.H, f.W, f.C, f.nterms = out.shape[0], out.shape[1], out.shape[2], out.shape[3], len(terms)
     for i, (t, mode) in enumerate(terms):
@@ -360,6 +363,7 @@ def list_fuse(ops: LaunchList, code: int, out, terms, wparam) -> None:
         ops.add("stl_det_fuse16", f, code)
     else:
         ops.add("stl_det_fuse", f)
+    return f
 
 
 class _Plan:
@@ -419,6 +423,7 @@ class _Plan:
         self.backbone = [f for f, _ in feats[-3:]]   # P3, P4, P5
         c = m.fpn_channels
         levels = None
+        self.cells = []   # per BiFPN cell {node: (fused map f, depthwise output d, node output, DetFuse, its term maps)}: the cells' backward reads them
         for cell, lay in zip(m.bifpn, L["bifpn"]):
             levels = self._bifpn(cell, lay, levels, p3, p4, p5, c)
         self.feats = levels
@@ -475,16 +480,17 @@ class _Plan:
         self._cost(2 * m * ci * co, self.es * (m * ci + kp * np_ + (m * co if residual is not None else 0)) + out.element_size() * m * co)
 
     def _fuse(self, out, terms, wparam):
-        list_fuse(self.calls, self.code, out, terms, wparam)
+        f = list_fuse(self.calls, self.code, out, terms, wparam)
         self._cost(out.numel() * (2 * len(terms) + 4), self.es * (out.numel() + sum(t.numel() for t, _ in terms)))
+        return f
 
     def _sep(self, x, pk, h, c):
-        """SeparableConvBlock: depthwise 3x3 (no bias) then 1x1 with bias and BN folded, no activation."""
+        """SeparableConvBlock: depthwise 3x3 (no bias) then 1x1 with bias and BN folded, no activation -> (depthwise output, output)."""
         d = self._buf(self.B, h, h, c)
         self._dw(x, d, pk[0], None, h, c, 3, 1, 0)
         y = self._buf(self.B, h, h, c)
         self._pw(d, y, h * h, c, c, pk[1], act=0)
-        return y
+        return d, y
 
     def _bifpn(self, cell, lay, levels, p3, p4, p5, c):
         B = self.B
@@ -509,10 +515,15 @@ class _Plan:
             (p3_in, _), (p4_in, _), (p5_in, _), (p6_in, _), (p7_in, _) = levels
         hs = [p.shape[1] for p in (p3_in, p4_in, p5_in, p6_in, p7_in)]
 
+        kept = {}
+        self.cells.append(kept)
+
         def node(name, wname, terms, h):
             f = self._buf(B, h, h, c)
-            self._fuse(f, terms, wp[wname])
-            return self._sep(f, lay[name], h, c)
+            desc = self._fuse(f, terms, wp[wname])
+            d, y = self._sep(f, lay[name], h, c)
+            kept[name] = (f, d, y, desc, [t for t, _ in terms])
+            return y
         p6_up = node("conv6_up", "p6_w1", [(p6_in, 0), (p7_in, 1)], hs[3])
         p5_up = node("conv5_up", "p5_w1", [(p5_in, 0), (p6_up, 1)], hs[2])
         p4_up = node("conv4_up", "p4_w1", [(p4_in, 0), (p5_up, 1)], hs[1])
@@ -533,6 +544,8 @@ class _Plan:
     def run(self, stream: int, upto: Optional[int] = None, canvas: Optional[torch.Tensor] = None) -> None:
         """canvas: another fp32 [B, S, S, 3] input than the plan's own (a ``DetBatch``'s): the stem, the first launch and the canvas's
         only reader, reads it where it lies -- nothing is copied."""
+        if self.train is not None:
+            self.train.generation += 1   # the maps a pending backward would read are about to be overwritten
         if canvas is None or canvas.data_ptr() == self.canvas.data_ptr():
             return self.calls.run(stream, 0, upto)
         if tuple(canvas.shape) != tuple(self.canvas.shape) or canvas.dtype != torch.float32 or canvas.device != self.canvas.device \
@@ -591,18 +604,51 @@ class EfficientDetBackbone(nn.Module):
         self._version, self._plans, self._wbuf, self._wbuf16, self._anchor_dev = None, {}, None, None, None
         self._wbufT16, self._layoutT = None, None   # the heads' bf16 transposed packs (_ensure_transposed: models that train only)
         self._batch_tables: dict = {}               # _batch_records: the constant record table of a DetBatch geometry
+        self.train_bifpn = 0                        # set_train_bifpn: how many trailing BiFPN cells detection_loss trains with the heads
         self.eval()
 
     # ---------------------------------------------------------------- state
     def load_state_dict(self, state_dict, strict=True, assign=False):
         return super().load_state_dict(_strip(dict(state_dict)), strict=strict, assign=assign)
 
+    def set_train_bifpn(self, k: int) -> "EfficientDetBackbone":
+        """The last k BiFPN cells train with the heads in detection_loss (0: the heads alone).  The first cell never trains: it alone
+        has the down-channel convs, p5_to_p6 and the unweighted pooled maps, whose backward this engine does not have."""
+        n = len(self.bifpn)
+        if not isinstance(k, int) or isinstance(k, bool) or k < 0 or k > n - 1:
+            raise ValueError(f"EfficientDet.set_train_bifpn: k = {k!r}, expected 0 .. {n - 1}: the first of the {n} BiFPN cells does not "
+                             "train -- it alone has the down-channel convs, p5_to_p6 and the unweighted pooled maps, and only the "
+                             "backward of the cells behind it (five inputs, eight fused nodes) is built")
+        if k != self.train_bifpn:
+            current = self._version is not None and self._state_version() == self._version
+            self.train_bifpn = k
+            self._version = self._state_version() if current else None   # the same weights, split anew; else a full refold
+            for p in self._plans.values():
+                p.train = None   # its backward launches are listed for one k
+        return self
+
     def _state_version(self):
-        """(trunk, heads): data pointer and version of every parameter and buffer outside / inside regressor.* and classifier.*"""
-        heads = [t for h in (self.regressor, self.classifier) for t in list(h.parameters()) + list(h.buffers())]
-        ids = {id(t) for t in heads}
+        """(trunk, cells, heads): data pointer and version of every parameter and buffer of the frozen trunk, of the trainable BiFPN
+        cells (the last train_bifpn) and of regressor.* / classifier.*"""
+        owned = lambda mods: [t for h in mods for t in list(h.parameters()) + list(h.buffers())]   # noqa: E731
+        cells = owned(list(self.bifpn)[len(self.bifpn) - self.train_bifpn:])
+        heads = owned((self.regressor, self.classifier))
+        ids = {id(t) for t in cells + heads}
         trunk = [t for t in list(self.parameters()) + list(self.buffers()) if id(t) not in ids]
-        return tuple(tuple((t.data_ptr(), t._version) for t in ts) for ts in (trunk, heads))
+        return tuple(tuple((t.data_ptr(), t._version) for t in ts) for ts in (trunk, cells, heads))
+
+    @staticmethod
+    def _pack_cell(P: _Packer, cell):
+        """-> (the packed layers' offsets by name, the fusion weights' offsets by name)"""
+        lay = {}
+        for n in _BiFPN.NODES:
+            sep = getattr(cell, n)
+            lay[n] = (P.dw(sep.depthwise_conv.conv)[0], P.pw(sep.pointwise_conv.conv, sep.bn))
+        if cell.first_time:
+            for key in ("p5_down_channel", "p4_down_channel", "p3_down_channel", "p5_to_p6", "p4_down_channel_2", "p5_down_channel_2"):
+                seq = getattr(cell, key)
+                lay[key] = P.pw(seq[0].conv, seq[1])
+        return lay, {n: P.add(getattr(cell, n).detach()) for n, _ in _BiFPN.WEIGHTS}
 
     def _pack_heads(self, P: _Packer) -> dict:
         heads = {}
@@ -613,14 +659,19 @@ class EfficientDetBackbone(nn.Module):
                            "hdw": P.dw(hd.header.depthwise_conv.conv)[0], "hpw": P.pw(hd.header.pointwise_conv.conv)}
         return heads
 
-    def _refold_heads(self) -> None:
-        """Only regressor.* / classifier.* changed (an optimiser step of detection_loss): their pieces are the tail of the weight
-        buffers and are rewritten in place, through the same packing as a full refold (bit-identical); the plans stay."""
-        P = _Packer(COMPUTE_DTYPES[self.compute_dtype][0], transposed=self._wbufT16 is not None)
-        P.n, P.n16 = self._head_off
+    def _refold_tail(self, first: int) -> None:
+        """Only the BiFPN cells from `first` on and regressor.* / classifier.* changed (an optimiser step of detection_loss; first =
+        len(bifpn): the heads alone).  The cells are packed in order and the heads last, so these pieces are one tail of the weight
+        buffers: it is rewritten in place, through the same packing as a full refold (bit-identical); the plans stay."""
+        P = _Packer(COMPUTE_DTYPES[self.compute_dtype][0])
+        n0, n16 = P.n, P.n16 = self._tail_off[first]
+        for j in range(first, len(self.bifpn)):
+            lay, woff = self._pack_cell(P, self.bifpn[j])
+            assert all(lay[k] == self._layout["bifpn"][j][k] for k in lay) and woff == self._woff[j], "EfficientDet: BiFPN layout changed"
+        assert (P.n, P.n16) == self._tail_off[len(self.bifpn)], "EfficientDet: BiFPN layout changed"
+        P.transposed = self._wbufT16 is not None   # the heads alone have transposed packs
         heads = self._pack_heads(P)
         assert all(heads[k] == self._layout[k] for k in heads) and P.n == self._wbuf.numel(), "EfficientDet: head layout changed"
-        n0, n16 = self._head_off
         self._wbuf[n0:].copy_(torch.cat(P.parts).float())
         if P.parts16:
             self._wbuf16[n16:].copy_(torch.cat(P.parts16))
@@ -630,23 +681,24 @@ class EfficientDetBackbone(nn.Module):
 
     def _ensure_transposed(self) -> None:
         """16-bit models that train: the bf16 transposed packs of the heads' pointwise layers (stl_det_pointwise16_bwd_data), built
-        at the first detection_loss after a full fold and refreshed by _refold_heads; the forward buffers are not touched."""
+        at the first detection_loss after a full fold and refreshed by _refold_tail; the forward buffers are not touched."""
         if self._wbufT16 is None:
             P = _Packer(COMPUTE_DTYPES[self.compute_dtype][0], transposed=True)
-            P.n, P.n16 = self._head_off
+            P.n, P.n16 = self._tail_off[len(self.bifpn)]
             self._pack_heads(P)
             self._wbufT16, self._layoutT = torch.cat(P.partsT).to(self._wbuf.device).contiguous(), P.tmap
 
     def ready(self, dev) -> None:
         """Fold BN and pack every weight into one fp32 device buffer (in a 16-bit mode the pointwise weights into a second one of
-        that type); redone when any parameter or buffer has changed (_refold_heads when only the heads' have)."""
+        that type); redone when any parameter or buffer of the frozen trunk has changed (_refold_tail when only the trainable
+        BiFPN cells' or the heads' have)."""
         dev = _device(dev)
         if self.backbone_net.model._bn0.weight.device != dev:
             self.to(dev)
         v = self._state_version()
         if self._version is not None and v[0] == self._version[0] and self._wbuf is not None and self._wbuf.device == dev:
-            if v[1] != self._version[1]:
-                self._refold_heads()
+            if v[1:] != self._version[1:]:
+                self._refold_tail(len(self.bifpn) - (self.train_bifpn if v[1] != self._version[1] else 0))
                 self._version = v
             return
         P = _Packer(COMPUTE_DTYPES[self.compute_dtype][0])
@@ -663,24 +715,18 @@ class EfficientDetBackbone(nn.Module):
             lay["se"] = (P.add(r.weight.detach().reshape(b["se"], b["mid"])), P.add(r.bias.detach()),
                          P.add(e.weight.detach().reshape(b["mid"], b["se"])), P.add(e.bias.detach()))
             blocks.append(lay)
-        cells = []
-        for cell in self.bifpn:
-            lay = {}
-            for n in _BiFPN.NODES:
-                sep = getattr(cell, n)
-                lay[n] = (P.dw(sep.depthwise_conv.conv)[0], P.pw(sep.pointwise_conv.conv, sep.bn))
-            if cell.first_time:
-                for key in ("p5_down_channel", "p4_down_channel", "p3_down_channel", "p5_to_p6", "p4_down_channel_2", "p5_down_channel_2"):
-                    seq = getattr(cell, key)
-                    lay[key] = P.pw(seq[0].conv, seq[1])
-            lay["weights"] = {n: P.add(getattr(cell, n).detach()) for n, _ in _BiFPN.WEIGHTS}
+        cells, self._woff, self._tail_off = [], [], []   # _tail_off[j]: where cell j starts in the two buffers, [len(bifpn)]: where the heads do
+        for cell in self.bifpn:          # (cells in order, the heads last: _refold_tail rewrites the buffers from one of these on)
+            self._tail_off.append((P.n, P.n16))
+            lay, woff = self._pack_cell(P, cell)
             cells.append(lay)
-        self._head_off = (P.n, P.n16)   # the heads are packed last: _refold_heads rewrites the buffers from here on
+            self._woff.append(woff)
+        self._tail_off.append((P.n, P.n16))
         heads = self._pack_heads(P)
         self._wbuf, self._wbuf16 = P.done(dev), P.done16(dev)
         self._wbufT16, self._layoutT = None, None
-        for cell in cells:   # BiFPN weight offsets -> device views
-            cell["weights"] = {n: self._wbuf[o:] for n, o in cell["weights"].items()}
+        for cell, woff in zip(cells, self._woff):   # BiFPN weight offsets -> device views
+            cell["weights"] = {n: self._wbuf[o:] for n, o in woff.items()}
         self._layout = {"stem": stem, "blocks": blocks, "bifpn": cells, **heads}
         self._anchor_dev = torch.from_numpy(self.anchors_np).to(dev)
         self._plans.clear()
@@ -772,8 +818,8 @@ class EfficientDetBackbone(nn.Module):
         classification and smooth-L1 box regression losses of RetinaNet / EfficientDet over IoU-assigned anchors.  inputs as
         forward takes them; targets one dict per image with ``boxes`` [n, 4] (x1, y1, x2, y2 in original pixels) and ``labels``
         [n] in 1 .. num_classes (n = 0 allowed).  Returns {"classification", "regression"}: fp32 device scalars whose backward
-        fills ``.grad`` of every regressor.* and classifier.* parameter; the backbone and the BiFPN are frozen and every BN runs
-        on its running statistics, whatever ``.training`` is.  compute_dtype "fp32", or "f16" (f16 forward tensors, bf16 gradients in
+        fills ``.grad`` of every regressor.* and classifier.* parameter and, after ``set_train_bifpn(k)``, of the last k BiFPN cells'
+        (fp32 only); the backbone and the other cells are frozen and every BN runs on its running statistics, whatever ``.training`` is.  compute_dtype "fp32", or "f16" (f16 forward tensors, bf16 gradients in
         flight, fp32 sums and fp32 ``.grad``; non-finite head outputs raise FloatingPointError); "bf16" raises
         NotImplementedError.  One activation set per batch size: backward before the
         next detection_loss of that batch size (a stale-forward error otherwise).  See stlpose_amd/detector_train.py.
