@@ -186,10 +186,13 @@ int stl_patch3x3(int dtype, const float* img, void* out, int B, int H, int W, in
 int stl_patch3x3_backward(int dtype, const void* dpatch, float* dimg, int B, int H, int W, int stride, const float* std3,
                           void* stream);
 
-/* 1x1 head with bias: NHWC dtype [B,H,W,Ci] -> NCHW fp32 [B,J,H,W]  (HRnet.py:331-337,466). */
+/* 1x1 head with bias: NHWC dtype [B,H,W,Ci] -> NCHW fp32 [B,J,H,W]  (HRnet.py:331-337,466).  J is 16 or 17 (the kernels keep a
+ * pixel's J outputs in registers); forward: Ci % 8 == 0, Ci <= 512, bias may be NULL; backward: Ci % 16 == 0, Ci <= 64 (four
+ * 16-column MFMA tiles) -- the widths of the network's head, 16 .. 64.  Anything else is refused before the launch. */
 int stl_head_forward(int dtype, const void* x, const float* w, const float* bias, float* out,
                      int B, int H, int W, int Ci, int J, void* stream);
-/* its backward: dx (dtype NHWC), per-block partials of dw [J][Ci] and db [J] (fp32). */
+/* its backward: dx (dtype NHWC), per-block partials of dw [J][Ci] and db [J] (fp32): partial[nblk][J*Ci + J], every slab
+ * written (zeros by a block that has no 256-pixel chunk).  dtype: STL_DT2(type of dx, type of x). */
 int stl_head_backward(int dtype, const void* x, const float* w, const float* dout, void* dx,
                       float* partial, int nblk, int B, int H, int W, int Ci, int J, void* stream);
 
@@ -274,8 +277,10 @@ typedef struct stl_bnrec { /* one BatchNorm layer */
 /* running_mean/var momentum update (unbiased var), reference nn.BatchNorm2d(momentum=0.1).
  * overflow (device int32, NULL = off; the caller initialises it to INT32_MAX): range guard of the 16-bit forward tensors.  A raw
  * conv output beyond the storage type's range (STL_F16: |y| > 65504, e.g. a badly scaled checkpoint, lib/model_setup.py:38-42
- * loads arbitrary ones) is stored as infinity and shows in the layer's sums; such a layer keeps its running statistics and the
- * smallest index i of tab[] with non-finite sums is left in *overflow (atomic min).  The optimisers below skip elements whose
+ * loads arbitrary ones) is stored as infinity and shows in the layer's sums; such a layer keeps its running statistics --
+ * EVERY channel of it, not only the channels whose sums are non-finite (with overflow == NULL too); num_batches_tracked still
+ * counts the pass -- and the smallest index i of tab[] with non-finite sums is left in *overflow (atomic min).  A momentum of
+ * 0 leaves the buffers bit-unchanged.  The count is rebuilt as 1 / (double)inv_count.  The optimisers below skip elements whose
  * gradient is not finite, so the step that overflowed leaves the weights as they were; the host reads the word when it reads
  * the loss (TrainStep.check_forward_range) and raises with the layer's name. */
 int stl_bn_running_update(const double* stats, float* buffers, int64_t* num_batches_tracked /* [n] or NULL */,

@@ -896,19 +896,30 @@ __global__ __launch_bounds__(256) void bn_running_kernel(const double* stats, fl
                                                          const stl_bnrec* tab, float momentum, int32_t* overflow) {
     const stl_bnrec e = tab[blockIdx.x];
     const double n = 1.0 / (double)e.inv_count;
-    bool bad = false;
+    // A raw conv output beyond the range of its storage type (f16 forward tensors of the mixed mode: |y| > 65504) was stored
+    // as infinity, and the sums of the values AS STORED carry it: the LAYER's running statistics stay as they are -- every
+    // channel of it, so the block votes over all channels before any thread stores -- and the FIRST such layer (smallest
+    // index) is reported through `overflow` (engine.Engine.check_forward_range).
+    int bad = 0;
     for (int c = threadIdx.x; c < e.C; c += 256) {
         double s0 = 0.0, s1 = 0.0;
         for (int k = 0; k < STL_NSHARD; ++k) {
             s0 += stats[e.stats_off + (int64_t)k * 2 * e.C + c];
             s1 += stats[e.stats_off + (int64_t)k * 2 * e.C + e.C + c];
         }
-        // A raw conv output beyond the range of its storage type (f16 forward tensors of the mixed mode: |y| > 65504) was stored
-        // as infinity, and the sums of the values AS STORED carry it: the layer's running statistics stay as they are and the
-        // FIRST such layer (smallest index) is reported through `overflow` (engine.Engine.check_forward_range).
-        if (!(fabs(s0) <= 1.7e308 && fabs(s1) <= 1.7e308)) {
-            bad = true;
-            continue;
+        if (!(fabs(s0) <= 1.7e308 && fabs(s1) <= 1.7e308)) bad = 1;
+    }
+    bad = __syncthreads_or(bad);
+    if (threadIdx.x == 0 && nbt) nbt[blockIdx.x] += 1;
+    if (bad) {
+        if (threadIdx.x == 0 && overflow) atomicMin(overflow, (int32_t)blockIdx.x);
+        return;
+    }
+    for (int c = threadIdx.x; c < e.C; c += 256) {
+        double s0 = 0.0, s1 = 0.0;
+        for (int k = 0; k < STL_NSHARD; ++k) {
+            s0 += stats[e.stats_off + (int64_t)k * 2 * e.C + c];
+            s1 += stats[e.stats_off + (int64_t)k * 2 * e.C + e.C + c];
         }
         const double mean = s0 / n;
         double var = s1 / n - mean * mean;
@@ -919,8 +930,6 @@ __global__ __launch_bounds__(256) void bn_running_kernel(const double* stats, fl
         rm[c] = (float)((1.0 - momentum) * (double)rm[c] + momentum * mean);
         rv[c] = (float)((1.0 - momentum) * (double)rv[c] + momentum * unb);
     }
-    if (threadIdx.x == 0 && nbt) nbt[blockIdx.x] += 1;
-    if (bad && overflow) atomicMin(overflow, (int32_t)blockIdx.x);
 }
 
 __global__ __launch_bounds__(256) void bn_param_grads_kernel(const double* rstats, float* grads, const stl_bnrec* tab) {
@@ -1409,8 +1418,9 @@ extern "C" int stl_head_backward(int dtype2, const void* x, const float* w, cons
     const int dtype = dtype2 & 0xff, ydtype = (dtype2 >> 8) & 0xff;   // STL_DT2(type of dx, type of x)
     STL_CHECK(ydtype == 0 || ydtype == dtype || (dtype == STL_BF16 && ydtype == STL_F16), "head_bwd: x type %d does not go with dx type %d", ydtype, dtype);
     STL_CHECK(J == 17 || J == 16, "head_bwd: J=%d unsupported", J);
-    STL_CHECK(Ci % 8 == 0 && J * Ci + J <= 1024, "head_bwd: Ci=%d", Ci);
     STL_CHECK(nblk >= 1, "head_bwd: nblk");
+    // (a limit J * Ci + J <= 1024 of the scalar kernel this one replaced stood here and refused Ci = 64, which the kernel runs:
+    // every loop over the J * Ci + J outputs strides by the block, NTMAX = 4 column tiles cover 64 channels, 89 KB of LDS)
     STL_CHECK(Ci % 16 == 0 && Ci <= 64, "head_bwd: Ci=%d must be a multiple of 16, at most 64", Ci);
     size_t lds = (size_t)(((J * Ci + 3) & ~3) + J * 260 + 256 * (Ci + 1)) * 4;
     const size_t lds_red = (size_t)(((J * Ci + 3) & ~3) + J * 260) * 4 + (size_t)4 * 2 * 4 * 64 * 16 + 4 * J * 4;   // reduction buffers alias sx
