@@ -5,7 +5,6 @@ any order and type; the summed slabs must EQUAL the fp64 reference.  A missed, d
 split is a non-zero integer.  Transformed sources (BatchNorm on load, BatchNorm backward on load) are held to an elementwise bound
 computed from the reference side alone (tests/wgrad_ref.py: bound).  Every case names the kernel instantiation it expects.
 All tensors the kernels touch lie between NaN guard bands, so that a stray read shows up as NaN and a stray write in the band."""
-import ctypes as C
 import functools
 
 import pytest
@@ -15,49 +14,10 @@ pytestmark = pytest.mark.gpu
 
 from stlpose_amd import capi  # noqa: E402
 from tests import wgrad_ref as R  # noqa: E402
+from tests.gpu_guard import Guarded, launch  # noqa: E402
 
-GUARD = 64 * 1024   # bytes of NaN on each side of a tensor
 CODE = {"f32": capi.F32, "bf16": capi.BF16, "f16": capi.F16}
 RATIOS = {}         # observed max |err| / E per type (information only: printed, never asserted against)
-
-
-def stream():
-    return torch.cuda.current_stream().cuda_stream
-
-
-def launch(fn, params):
-    """Launch, synchronise and check both return codes.  A GPU fault ends the whole session: nothing more is started on a
-    device that has faulted."""
-    rc = getattr(capi.lib(), fn)(C.byref(params), stream())
-    err = capi.lib().stl_last_error().decode() if rc else ""
-    try:
-        torch.cuda.synchronize()
-    except RuntimeError as e:
-        pytest.exit(f"GPU fault in {fn} ({capi.lib().stl_last_kernel().decode()}): {e}", returncode=3)
-    if "illegal" in err or "fault" in err:
-        pytest.exit(f"GPU fault in {fn}: {err}", returncode=3)
-    return rc, err
-
-
-class Guarded:
-    """n elements between two NaN bands of GUARD bytes."""
-
-    def __init__(self, n, dtype, data=None):
-        self.gel = GUARD // torch.empty((), dtype=dtype).element_size()
-        self.whole = torch.full((n + 2 * self.gel,), float("nan"), dtype=dtype, device="cuda")
-        self.t = self.whole[self.gel:self.gel + n]
-        self.bits = torch.int32 if dtype == torch.float32 else torch.int16
-        self.nan = self.whole[:1].view(self.bits).clone()
-        if data is not None:
-            self.t.copy_(data.reshape(-1).to(dtype))
-        assert self.t.data_ptr() % 16 == 0
-
-    def ptr(self):
-        return self.t.data_ptr()
-
-    def bands_intact(self):
-        lo, hi = self.whole[:self.gel].view(self.bits), self.whole[self.gel + self.t.numel():].view(self.bits)
-        return bool((lo == self.nan).all()) and bool((hi == self.nan).all())
 
 
 @functools.lru_cache(maxsize=None)
