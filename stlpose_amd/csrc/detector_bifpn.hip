@@ -10,6 +10,9 @@
 //                      fuse_bwd_gather_kernel  one launch per requested term of mode 1 / 2, one thread per element of the TERM's map:
 //                                           it gathers the ds of the outputs that read it (for a pooled term: of the windows it
 //                                           won by the forward's scan), so nothing is scattered and there are no atomics
+//   stl_det_pool_bwd   pool_bwd_kernel      the adjoint of a weightless pooled map (the first cell's t -> p6 -> p7): the pooled gather
+//                                           with w^ = 1 and ds = dy, one thread per four channels of the input map (per channel
+//                                           where C % 4 != 0); pool_gather is the one routine of both gathers
 //   stl_det_grad_add   out = sa a + sb b, the scales read from the device (the two heads' gradients of a level, each times the
 //                      gradient of its own loss)
 //
@@ -31,21 +34,79 @@ __host__ __device__ __forceinline__ int same_pad_before(int n, int k, int s) {
     return (extra > 0 ? extra : 0) / 2;
 }
 
+// The forward's scan of window (oy, ox) of the zero-padded 3x3 s2 max-pool of t, for V consecutive channels from c (V = 4: C % 4 == 0
+// and t.x 16-byte aligned): the maximum m[k] and the winner's position (wy[k], wx[k]), the first strict maximum in (ky, kx) order;
+// it lies outside the map when a padded tap (0 at its place) won.
+template <int V>
+__device__ __forceinline__ void pool_scan(const StlDetTerm& t, int b, int oy, int ox, int c, int C, float* m, int* wy, int* wx) {
+    const int py = same_pad_before(t.H, 3, 2), px = same_pad_before(t.W, 3, 2);
+#pragma unroll
+    for (int k = 0; k < V; ++k) m[k] = -INFINITY;
+    for (int ky = 0; ky < 3; ++ky) {
+        const int iy = oy * 2 - py + ky;
+        for (int kx = 0; kx < 3; ++kx) {
+            const int ix = ox * 2 - px + kx;
+            float v[V];
+            if (iy < 0 || iy >= t.H || ix < 0 || ix >= t.W) {
+#pragma unroll
+                for (int k = 0; k < V; ++k) v[k] = 0.f;
+            } else {
+                const float* src = t.x + (((int64_t)b * t.H + iy) * t.W + ix) * C + c;
+                if constexpr (V == 4) {
+                    const float4 q = *reinterpret_cast<const float4*>(src);
+                    v[0] = q.x, v[1] = q.y, v[2] = q.z, v[3] = q.w;
+                } else {
+#pragma unroll
+                    for (int k = 0; k < V; ++k) v[k] = src[k];
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < V; ++k)
+                if (v[k] > m[k]) m[k] = v[k], wy[k] = iy, wx[k] = ix;
+        }
+    }
+}
+
 // fuse_read of detector.hip; for a pooled term also the winner's position (wy, wx), which lies outside the map when padding won
 __device__ __forceinline__ float fuse_read_at(const StlDetTerm& t, int b, int y, int x, int c, int C, int& wy, int& wx) {
     if (t.mode == 0) return t.x[(((int64_t)b * t.H + y) * t.W + x) * C + c];
     if (t.mode == 1) return t.x[(((int64_t)b * t.H + (y >> 1)) * t.W + (x >> 1)) * C + c];
-    const int py = same_pad_before(t.H, 3, 2), px = same_pad_before(t.W, 3, 2);
-    float m = -INFINITY;
-    for (int ky = 0; ky < 3; ++ky) {
-        const int iy = y * 2 - py + ky;
-        for (int kx = 0; kx < 3; ++kx) {
-            const int ix = x * 2 - px + kx;
-            const float v = (iy < 0 || iy >= t.H || ix < 0 || ix >= t.W) ? 0.f : t.x[(((int64_t)b * t.H + iy) * t.W + ix) * C + c];
-            if (v > m) m = v, wy = iy, wx = ix;
-        }
-    }
+    float m;
+    pool_scan<1>(t, b, y, x, c, C, &m, &wy, &wx);
     return m;
+}
+
+// The pooled gather of both backward kernels, for pixel (y, x) and V consecutive channels from c of the pooled map t (pooled into
+// oH x oW): v[k] = the sum of scale * ds[window] over the up to four windows that hold the pixel, row-major, that the pixel won.
+// Window oy holds rows 2 oy - py .. 2 oy - py + 2: oy in [ceil((y + py - 2) / 2), floor((y + py) / 2)], clipped to the output.
+template <int V>
+__device__ __forceinline__ void pool_gather(const StlDetTerm& t, int b, int y, int x, int c, int C, int oH, int oW,
+                                            const float* __restrict__ ds, float scale, float* v) {
+    const int py = same_pad_before(t.H, 3, 2), px = same_pad_before(t.W, 3, 2);
+    const int oy0 = (y + py - 1) >> 1 > 0 ? (y + py - 1) >> 1 : 0, oy1 = (y + py) >> 1 < oH - 1 ? (y + py) >> 1 : oH - 1;
+    const int ox0 = (x + px - 1) >> 1 > 0 ? (x + px - 1) >> 1 : 0, ox1 = (x + px) >> 1 < oW - 1 ? (x + px) >> 1 : oW - 1;
+#pragma unroll
+    for (int k = 0; k < V; ++k) v[k] = 0.f;
+    for (int oy = oy0; oy <= oy1; ++oy)
+        for (int ox = ox0; ox <= ox1; ++ox) {
+            float m[V];
+            int wy[V], wx[V];
+#pragma unroll
+            for (int k = 0; k < V; ++k) wy[k] = wx[k] = -1;
+            pool_scan<V>(t, b, oy, ox, c, C, m, wy, wx);
+            const float* d = ds + (((int64_t)b * oH + oy) * oW + ox) * C + c;
+            if constexpr (V == 4) {
+                const float4 q = *reinterpret_cast<const float4*>(d);
+                const float dv[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+                for (int k = 0; k < 4; ++k)
+                    if (wy[k] == y && wx[k] == x) v[k] += scale * dv[k];
+            } else {
+#pragma unroll
+                for (int k = 0; k < V; ++k)
+                    if (wy[k] == y && wx[k] == x) v[k] += scale * d[k];
+            }
+        }
 }
 
 // the forward's normalised weights: w = relu(p) / (sum relu(p) + 1e-4), summed left to right
@@ -146,19 +207,37 @@ __global__ __launch_bounds__(256) void fuse_bwd_gather_kernel(const StlDetFuse f
         for (int oy = 2 * y; oy <= 2 * y + 1 && oy < f.H; ++oy)
             for (int ox = 2 * x; ox <= 2 * x + 1 && ox < f.W; ++ox) sum += ds[(((int64_t)b * f.H + oy) * f.W + ox) * C + c];
         v = wn[i] * sum;
-    } else {   // window oy holds rows 2 oy - py .. 2 oy - py + 2: oy in [ceil((y + py - 2) / 2), floor((y + py) / 2)], clipped to the output
-        const int py = same_pad_before(t.H, 3, 2), px = same_pad_before(t.W, 3, 2);
-        const int oy0 = (y + py - 1) >> 1 > 0 ? (y + py - 1) >> 1 : 0, oy1 = (y + py) >> 1 < f.H - 1 ? (y + py) >> 1 : f.H - 1;
-        const int ox0 = (x + px - 1) >> 1 > 0 ? (x + px - 1) >> 1 : 0, ox1 = (x + px) >> 1 < f.W - 1 ? (x + px) >> 1 : f.W - 1;
-        v = 0.f;
-        for (int oy = oy0; oy <= oy1; ++oy)
-            for (int ox = ox0; ox <= ox1; ++ox) {
-                int wy = -1, wx = -1;
-                fuse_read_at(t, b, oy, ox, c, C, wy, wx);
-                if (wy == y && wx == x) v += wn[i] * ds[(((int64_t)b * f.H + oy) * f.W + ox) * C + c];
-            }
+    } else {
+        pool_gather<1>(t, b, y, x, c, C, f.H, f.W, ds, wn[i], &v);
     }
     dx[e] = accumulate ? dx[e] + v : v;
+}
+
+// the weightless pooled node f (one mode-2 term): one thread per V consecutive channels of a pixel of the term's map
+template <int V>
+__global__ __launch_bounds__(256) void pool_bwd_kernel(const StlDetFuse f, const float* __restrict__ dy, float* __restrict__ dx,
+                                                       int accumulate) {
+    const StlDetTerm& t = f.t[0];
+    const int C = f.C, CV = C / V;
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= (int64_t)f.B * t.H * t.W * CV) return;
+    const int c = (int)(e % CV) * V;
+    const int64_t pix = e / CV;
+    const int x = (int)(pix % t.W), y = (int)((pix / t.W) % t.H), b = (int)(pix / ((int64_t)t.W * t.H));
+    float v[V];
+    pool_gather<V>(t, b, y, x, c, C, f.H, f.W, dy, 1.f, v);
+    float* o = dx + pix * C + c;
+    if constexpr (V == 4) {
+        float4 q = make_float4(v[0], v[1], v[2], v[3]);
+        if (accumulate) {
+            const float4 a = *reinterpret_cast<const float4*>(o);
+            q = make_float4(a.x + v[0], a.y + v[1], a.z + v[2], a.w + v[3]);
+        }
+        *reinterpret_cast<float4*>(o) = q;
+    } else {
+#pragma unroll
+        for (int k = 0; k < V; ++k) o[k] = accumulate ? o[k] + v[k] : v[k];
+    }
 }
 
 __global__ __launch_bounds__(256) void grad_add_kernel(const float* a, const float* b, const float* __restrict__ sa,
@@ -208,6 +287,29 @@ extern "C" int stl_det_fuse_bwd(const StlDetFuse* f, const float* dy, const StlD
         STL_LAUNCH(fuse_bwd_gather_kernel, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, ST, *f, i, (const float*)ds, g->dx[i], g->accumulate[i]);
         STL_LAUNCH_CHECK("det_fuse_bwd");
     }
+    return 0;
+}
+
+extern "C" int stl_det_pool_bwd(const StlDetFuse* f, const float* dy, float* dx, int accumulate, void* stream) {
+    STL_CHECK(f && dy && dx, "det_pool_bwd: null pointer");
+    STL_CHECK(f->B >= 1 && f->H >= 1 && f->W >= 1 && f->C >= 1, "det_pool_bwd: bad geometry");
+    STL_CHECK(f->nterms == 1 && !f->wparam, "det_pool_bwd: %d terms%s (a weighted node is stl_det_fuse_bwd's)", f->nterms,
+              f->wparam ? ", weights" : "");
+    const StlDetTerm& t = f->t[0];
+    STL_CHECK(t.x, "det_pool_bwd: term null");
+    STL_CHECK(t.mode == 2 && t.H >= 1 && t.W >= 1 && (t.H + 1) / 2 == f->H && (t.W + 1) / 2 == f->W,
+              "det_pool_bwd: term mode %d of %d x %d into %d x %d", t.mode, t.H, t.W, f->H, f->W);
+    const int64_t ny = (int64_t)f->B * f->H * f->W * f->C, nx = (int64_t)f->B * t.H * t.W * f->C;
+    STL_CHECK((nx + 255) / 256 < (1ll << 31), "det_pool_bwd: too large");
+    STL_CHECK((uintptr_t)dy + 4 * (uintptr_t)ny <= (uintptr_t)dx || (uintptr_t)dx + 4 * (uintptr_t)nx <= (uintptr_t)dy,
+              "det_pool_bwd: dy and dx overlap");
+    const bool vec = f->C % 4 == 0 && (((uintptr_t)t.x | (uintptr_t)dy | (uintptr_t)dx) & 15) == 0;
+    if (vec) {
+        STL_LAUNCH(pool_bwd_kernel<4>, dim3((unsigned)((nx / 4 + 255) / 256)), dim3(256), 0, ST, *f, dy, dx, accumulate);
+    } else {
+        STL_LAUNCH(pool_bwd_kernel<1>, dim3((unsigned)((nx + 255) / 256)), dim3(256), 0, ST, *f, dy, dx, accumulate);
+    }
+    STL_LAUNCH_CHECK("det_pool_bwd");
     return 0;
 }
 

@@ -15,7 +15,7 @@ level) from the header down through csrc/detector_train.hip and produces gradien
 ops, and the weights shared by the five levels sum their five contributions.  The first depthwise layer of a (head, level) reads
 a frozen feature map: no data gradient is computed for it.
 
-``model.set_train_bifpn(k)`` (1 <= k <= cells - 1) trains the last k BiFPN cells with the heads, fp32 only.  The forward is not
+``model.set_train_bifpn(k)`` (1 <= k <= cells - 1, or "all": below) trains the last k BiFPN cells with the heads, fp32 only.  The forward is not
 touched: the inference plan keeps every map (``_Plan.cells``), and the backward recomputes each node's pre-activation from them.
 Then the first depthwise layer of every (head, level) also computes its data gradient (stl_det_dwconv_bwd_data without z), the two
 heads' gradients of a level are added regressor first, each times the gradient of its own loss (stl_det_grad_add reads the two
@@ -25,6 +25,14 @@ later ones accumulate, in that fixed order.  Per node: the pointwise layer's wei
 layer's weight gradient (x = f) and data gradient, then stl_det_fuse_bwd (csrc/detector_bifpn.hip), whose destinations are null for
 the frozen inputs of the first trainable cell.  ``cell_raw_grads`` carries the folded gradients to the raw parameters: ``fold_chain``
 for the pointwise layer and its BN, ``fusion_weight_grads`` for ``p*_w1`` / ``p*_w2``.
+
+``model.set_train_bifpn("all")`` trains the first cell too, so everything behind the frozen backbone.  Its eight nodes run through the
+same loop; their inputs are the seven maps the cell makes from P3 / P4 / P5 (``p3_in``, ``p4_in``, ``p5_in``, the second ``p4_in`` /
+``p5_in`` of the down path, ``p6``, ``p7``), which get gradient maps like any node output.  Behind the nodes: stl_det_pool_bwd
+(csrc/detector_bifpn.hip) of ``p6 -> p7``, adding to the gradient of ``p6``, then of ``t -> p6`` (``t`` the output of ``p5_to_p6``'s
+conv and BN), then the weight gradients of the six 1x1 layers (stl_det_pointwise_bwd_weight with x = the backbone map: ``p5_to_p6``,
+the three ``*_down_channel``, the two ``*_down_channel_2``; ``_Plan.first_pools`` / ``first_convs``).  No data gradient is computed for
+P3 / P4 / P5: nothing before them trains.  ``fold_chain`` carries each folded pair to the conv's weight and bias and the BN's.
 
 A model with ``compute_dtype="f16"`` trains in 16 bit, by the recipe of the pose network's mixed mode: the trunk runs as the 16-bit
 inference plan's launches, the heads' forward tensors (every depthwise output d, pre-activation z and swish output t) are f16, the
@@ -123,14 +131,22 @@ class HeadTrain:
         gdtype = torch.bfloat16 if self.h16 else torch.float32
         self.ga, self.gb = torch.empty(m0 * c, device=dev, dtype=gdtype), torch.empty(m0 * c, device=dev, dtype=gdtype)   # gradients in flight, reused
         kmax = max(c, 9 * max(4, nc))
-        self.pw_part = torch.empty(getattr(lib, self._name("stl_det_pointwise_bwd_slabs"))(m0) * (c * kmax + kmax), device=dev)
+        slabs = getattr(lib, self._name("stl_det_pointwise_bwd_slabs"))
+        self.ncells = ncells = m.train_bifpn   # the trailing BiFPN cells that train with the heads
+        self.first = ncells == len(plan.cells)   # every cell: the first one's 1x1 layers (Ci = the backbone's channels) and plain pools too
+        npart = slabs(m0) * (c * kmax + kmax)
+        if self.first:   # the largest slabs * (Ci * Co + Co) that is listed
+            npart = max([npart] + [slabs(x.numel() // x.shape[3]) * (x.shape[3] * c + c) for x, _, _ in plan.first_convs.values()])
+        self.pw_part = torch.empty(npart, device=dev)
         self.dw_part = torch.empty(getattr(lib, self._name("stl_det_dwconv_bwd_parts"))(m0) * 9 * c, device=dev)
         self.grads: Dict[str, Dict[str, torch.Tensor]] = {}
-        self.ncells = ncells = m.train_bifpn   # the trailing BiFPN cells that train with the heads
         if ncells:
             assert not self.h16, "the BiFPN cells train in fp32 only"
             # the gradient of every node output of the trainable cells, by the address of the plan's map
             self.gmap = {y.data_ptr(): torch.empty_like(y) for kept in plan.cells[len(plan.cells) - ncells:] for _, _, y, _, _ in kept.values()}
+            if self.first:   # and of the first cell's seven input maps (p3_in, p4_in, p5_in, p4_in_2, p5_in_2, p6, p7) and of t
+                for y in [y for _, y, _ in plan.first_convs.values()] + [y for _, _, y in plan.first_pools]:
+                    self.gmap[y.data_ptr()] = torch.empty_like(y)
             self.hc = [torch.empty_like(f) for f, _ in plan.feats]   # the classifier's gradient of each level (the regressor's goes to gmap)
             self.scale = torch.ones(2, device=dev)                   # the gradients of (regression, classification): _DetLossFn.backward
         for name, out, k, act in (("regressor", self.reg, 4, 0), ("classifier", self.cls, nc, 2)):
@@ -195,6 +211,28 @@ class HeadTrain:
                         written.add(t.data_ptr())
                 self.bwd.keep_alive(f, d, y, *terms)   # the descriptors hold their addresses
                 self.bwd.add("stl_det_fuse_bwd", desc, self.gb, fb, self.fuse_ws, g["what"])
+        self.fgrads = {}
+        if not self.first:
+            return
+        # behind the first cell's nodes: p6 -> p7 adds to g(p6), which is complete then; t -> p6 writes g(t); then the weight gradients
+        # of the six 1x1 layers, x the frozen backbone map (no data gradient: nothing trains before them), p5_to_p6 first
+        for desc, x, y in reversed(plan.first_pools):
+            assert y.data_ptr() in written, "a pooled map of the first cell without a gradient"
+            self.bwd.keep_alive(x, y)
+            self.bwd.add("stl_det_pool_bwd", desc, self.gmap[y.data_ptr()], self.gmap[x.data_ptr()], int(x.data_ptr() in written))
+            written.add(x.data_ptr())
+        order = ("p5_to_p6", "p3_down_channel", "p4_down_channel", "p5_down_channel", "p4_down_channel_2", "p5_down_channel_2")
+        assert sorted(order) == sorted(plan.first_convs)
+        for key in order:
+            x, y, pk = plan.first_convs[key]
+            assert y.data_ptr() in written, key
+            ci, hw = x.shape[3], x.shape[1] * x.shape[2]
+            g = self.fgrads[key] = dict(pw_w=torch.empty(ci, c, device=dev), pw_b=torch.empty(c, device=dev))
+            dy = self.gmap[y.data_ptr()]
+            p = capi.DetPointwiseBwd(x.data_ptr(), None, dy.data_ptr(), None, g["pw_w"].data_ptr(), g["pw_b"].data_ptr(),
+                                     self.pw_part.data_ptr(), B * hw, hw * c, c, 0, hw, ci, c, pk[2], pk[3], 0)
+            self.bwd.keep_alive(x, dy, g["pw_w"], g["pw_b"])   # the descriptor holds their addresses
+            self.bwd.add("stl_det_pointwise_bwd_weight", p)
 
     def _name(self, name: str) -> str:
         return NAME16[name] if self.h16 else name
@@ -241,8 +279,8 @@ def head_parameters(m) -> List[Tuple[str, torch.nn.Parameter]]:
 
 
 def trainable_parameters(m) -> List[Tuple[str, torch.nn.Parameter]]:
-    """What detection_loss differentiates: the parameters of the last ``m.train_bifpn`` BiFPN cells in state_dict order, then
-    head_parameters(m)."""
+    """What detection_loss differentiates: the parameters of the last ``m.train_bifpn`` BiFPN cells in state_dict order (after
+    ``set_train_bifpn("all")`` every cell's, the first cell's 24 conv and BN tensors among them), then head_parameters(m)."""
     k = getattr(m, "train_bifpn", 0)
     n = len(m.bifpn) if k else 0
     cells = [(f"bifpn.{j}.{name}", p) for j in range(n - k, n) for name, p in m.bifpn[j].named_parameters()]
@@ -271,6 +309,13 @@ def cell_raw_grads(m, tr: HeadTrain) -> Dict[str, torch.Tensor]:
         wname = dict(zip(_BiFPN.NODES, _BiFPN.WEIGHTS))[node][0]
         p = getattr(m.bifpn[j], wname).detach()
         out[f"bifpn.{j}.{wname}"] = fusion_weight_grads(p, g["what"][:p.numel()])
+    for key, g in tr.fgrads.items():   # the first cell's 1x1 layers: Sequential(conv, BN[, pool])
+        seq, pre = getattr(m.bifpn[0], key), f"bifpn.0.{key}."
+        pw, bn = seq[0].conv, seq[1]
+        W, b = pw.weight.detach().reshape(pw.out_channels, pw.in_channels), pw.bias.detach()
+        dW, db, dgam, dbeta = fold_chain(W, b, bn.weight.detach(), bn.running_mean, bn.running_var, bn.eps, g["pw_w"].t(), g["pw_b"])
+        out[pre + "0.conv.weight"], out[pre + "0.conv.bias"] = dW[:, :, None, None], db
+        out[pre + "1.weight"], out[pre + "1.bias"] = dgam, dbeta.clone()
     return out
 
 

@@ -11,7 +11,7 @@
     without waiting;
   * ``setup_optimizer`` (``lib/model_setup.py:109-159``) over ``detector_train.trainable_parameters(model)`` -- the parameters
     ``detection_loss`` trains: the heads, and with ``exp_data["training"]["train_bifpn"] = k`` (default 0, applied to the model by
-    ``set_train_bifpn``) the last k BiFPN cells; everything before them is frozen: Adam, or SGD with momentum, nesterov and weight
+    ``set_train_bifpn``) the last k BiFPN cells, with ``"all"`` every cell; everything before them is frozen: Adam, or SGD with momentum, nesterov and weight
     decay 0.0005;
     ``ReduceLROnPlateau(mode="max", min_lr=1e-8)``, ``StepLR`` or no scheduler;
   * ``detector_logs.json`` as ``create_ / load_ / update_detector_logs`` write it (``lib/utils.py:244-301``);
@@ -108,8 +108,10 @@ class DetectorTrainer:
         self.cur_epoch, self.skipped = 0, 0
         self.train_loss, self.valid_ap, self.valid_stats = float("nan"), -1.0, None
         self.model.to(self.device).eval()
-        k = int(tr.get("train_bifpn", 0))
-        if k != getattr(self.model, "train_bifpn", 0):   # (a model without that stage takes 0 only)
+        k = tr.get("train_bifpn", 0)
+        k = k if k == "all" else int(k)
+        want = len(self.model.bifpn) if k == "all" else k
+        if want != getattr(self.model, "train_bifpn", 0):   # (a model without that stage takes 0 only)
             self.model.set_train_bifpn(k)
         self.optimizer, self.scheduler = setup_optimizer(exp_data, [p for _, p in trainable_parameters(model)])
         self.evaluator = DetectorEvaluator(model, device=self.device, output=output)

@@ -22,8 +22,9 @@ stlpose_amd/detector_train.py, csrc/detector_train.hip) is the first stage of
 EfficientDet fine-tuning, the counterpart of ``loss_dict = model(imgs / 255, targets)`` in ``02_train_faster_rcnn.py:212``: the
 backbone and the BiFPN are frozen, every BN stays on its running statistics, and ``sum(loss_dict.values()).backward()`` fills
 ``.grad`` of the ``regressor.*`` and ``classifier.*`` parameters.  ``set_train_bifpn(k)`` (fp32) is the next stage: the last k BiFPN
-cells, 1 <= k <= cells - 1, train with the heads (csrc/detector_bifpn.hip; ``detector_train.trainable_parameters``); the first cell and
-the backbone stay frozen.
+cells, 1 <= k <= cells - 1, train with the heads (csrc/detector_bifpn.hip; ``detector_train.trainable_parameters``); the cells before
+them and the backbone stay frozen.  ``set_train_bifpn("all")`` trains every cell, the first one with its down-channel convs,
+``p5_to_p6`` and the two plain pooled maps included: everything behind the backbone, which stays frozen.
 """
 from __future__ import annotations
 
@@ -501,13 +502,16 @@ class _Plan:
             self._pw(x5, t, h5 * h5, x5.shape[3], c, lay["p5_to_p6"], act=0)
             h6, h7 = (h5 + 1) // 2, (h5 + 3) // 4
             p6 = self._buf(B, h6, h6, c)
-            self._fuse(p6, [(t, 2)], None)
             p7 = self._buf(B, h7, h7, c)
-            self._fuse(p7, [(p6, 2)], None)
+            # what the first cell's backward reads: its two plain pools (DetFuse, input, output) in forward order and its six 1x1
+            # layers {name: (backbone map, output map, pack)}
+            self.first_pools = [(self._fuse(p6, [(t, 2)], None), t, p6), (self._fuse(p7, [(p6, 2)], None), p6, p7)]
+            self.first_convs = {"p5_to_p6": (x5, t, lay["p5_to_p6"])}
             ins = []
             for (xx, hh), key in ((p3, "p3_down_channel"), (p4, "p4_down_channel"), (p5, "p5_down_channel")):
                 y = self._buf(B, hh, hh, c)
                 self._pw(xx, y, hh * hh, xx.shape[3], c, lay[key], act=0)
+                self.first_convs[key] = (xx, y, lay[key])
                 ins.append(y)
             p3_in, p4_in, p5_in = ins
             p6_in, p7_in = p6, p7
@@ -533,6 +537,7 @@ class _Plan:
             for (xx, hh), key in ((p4, "p4_down_channel_2"), (p5, "p5_down_channel_2")):
                 y = self._buf(B, hh, hh, c)
                 self._pw(xx, y, hh * hh, xx.shape[3], c, lay[key], act=0)
+                self.first_convs[key] = (xx, y, lay[key])
                 ins.append(y)
             p4_in, p5_in = ins
         p4_out = node("conv4_down", "p4_w2", [(p4_in, 0), (p4_up, 0), (p3_out, 2)], hs[1])
@@ -604,21 +609,25 @@ class EfficientDetBackbone(nn.Module):
         self._version, self._plans, self._wbuf, self._wbuf16, self._anchor_dev = None, {}, None, None, None
         self._wbufT16, self._layoutT = None, None   # the heads' bf16 transposed packs (_ensure_transposed: models that train only)
         self._batch_tables: dict = {}               # _batch_records: the constant record table of a DetBatch geometry
-        self.train_bifpn = 0                        # set_train_bifpn: how many trailing BiFPN cells detection_loss trains with the heads
+        self.train_bifpn = 0                        # set_train_bifpn: how many trailing BiFPN cells detection_loss trains with the heads ("all": every cell)
         self.eval()
 
     # ---------------------------------------------------------------- state
     def load_state_dict(self, state_dict, strict=True, assign=False):
         return super().load_state_dict(_strip(dict(state_dict)), strict=strict, assign=assign)
 
-    def set_train_bifpn(self, k: int) -> "EfficientDetBackbone":
-        """The last k BiFPN cells train with the heads in detection_loss (0: the heads alone).  The first cell never trains: it alone
-        has the down-channel convs, p5_to_p6 and the unweighted pooled maps, whose backward this engine does not have."""
+    def set_train_bifpn(self, k) -> "EfficientDetBackbone":
+        """The last k BiFPN cells train with the heads in detection_loss (0: the heads alone), k = 0 .. cells - 1; ``"all"``: every
+        cell, the first one included (``train_bifpn == len(bifpn)``).  The first cell does not train by count: it alone has the
+        down-channel convs, p5_to_p6 and the unweighted pooled maps, where the frozen backbone's P3 / P4 / P5 enter the pyramid,
+        and with it trains everything behind the backbone; the backbone stays frozen and gets no data gradient."""
         n = len(self.bifpn)
-        if not isinstance(k, int) or isinstance(k, bool) or k < 0 or k > n - 1:
+        if isinstance(k, str) and k == "all":
+            k = n
+        elif not isinstance(k, int) or isinstance(k, bool) or k < 0 or k > n - 1:
             raise ValueError(f"EfficientDet.set_train_bifpn: k = {k!r}, expected 0 .. {n - 1}: the first of the {n} BiFPN cells does not "
-                             "train -- it alone has the down-channel convs, p5_to_p6 and the unweighted pooled maps, and only the "
-                             "backward of the cells behind it (five inputs, eight fused nodes) is built")
+                             "train by count -- it alone has the down-channel convs, p5_to_p6 and the unweighted pooled maps; "
+                             "set_train_bifpn(\"all\") trains it with every cell behind it")
         if k != self.train_bifpn:
             current = self._version is not None and self._state_version() == self._version
             self.train_bifpn = k
@@ -819,7 +828,7 @@ class EfficientDetBackbone(nn.Module):
         forward takes them; targets one dict per image with ``boxes`` [n, 4] (x1, y1, x2, y2 in original pixels) and ``labels``
         [n] in 1 .. num_classes (n = 0 allowed).  Returns {"classification", "regression"}: fp32 device scalars whose backward
         fills ``.grad`` of every regressor.* and classifier.* parameter and, after ``set_train_bifpn(k)``, of the last k BiFPN cells'
-        (fp32 only); the backbone and the other cells are frozen and every BN runs on its running statistics, whatever ``.training`` is.  compute_dtype "fp32", or "f16" (f16 forward tensors, bf16 gradients in
+        (``"all"``: of every cell's; fp32 only); the backbone and the other cells are frozen and every BN runs on its running statistics, whatever ``.training`` is.  compute_dtype "fp32", or "f16" (f16 forward tensors, bf16 gradients in
         flight, fp32 sums and fp32 ``.grad``; non-finite head outputs raise FloatingPointError); "bf16" raises
         NotImplementedError.  One activation set per batch size: backward before the
         next detection_loss of that batch size (a stale-forward error otherwise).  See stlpose_amd/detector_train.py.

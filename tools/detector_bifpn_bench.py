@@ -1,14 +1,17 @@
 #!/usr/bin/env python3
 """Fine-tuning step of the EfficientDet heads with the last k BiFPN cells on one MI355X (EfficientDetBackbone.detection_loss +
 backward + an SGD step over detector_train.trainable_parameters), fp32, D0 and D3 at batch 8 and 32, k = 0 (the heads alone: the
-step tools/detector_train_bench.py times), 1 and the model's maximum (cells - 1).  One model per k; everything of one (model,
+step tools/detector_train_bench.py times), 1, the model's maximum (cells - 1) and "all" (every cell: the first one with its 1x1
+layers on the backbone maps and its two plain pools).  One model per k; everything of one (model,
 batch) is timed in one process, the legs alternating, ROUNDS times each, every timing between device synchronisations
 (tools/detector_bench.timed); the medians are reported.
 
 Next to each leg the same trainable part in eager PyTorch under autograd (tests/detector_bifpn_ref.cell_forward with torch's own
 max-pool, tests/detector_train_ref.heads_forward, MIOpen convs) on the maps the plan produced, with the loss and output gradients
 of the same stl_det_loss launch: it times forward, backward and optimiser step of the trainable part, not the frozen trunk.  The
-cells' share is a leg minus the k = 0 leg, native (cells_ms) and eager (eager_cells_ms); at batch 32 and the largest k the cells'
+cells' share is a leg minus the k = 0 leg, native (cells_ms) and eager (eager_cells_ms); the first cell's share is the "all" leg
+minus the k = cells - 1 leg (first_cell_ms, eager_first_cell_ms: tests/detector_bifpn_first_ref.cell0_forward from the plan's P3 /
+P4 / P5); at batch 32, for the largest k and for "all", the cells'
 backward launches are also timed by entry point (cells_bwd_ms_by_launch: each sub-list replayed alone).
 
 Usage: python tools/detector_bifpn_bench.py OUTDIR -> OUTDIR/detector_bifpn_bench.json (commit it as
@@ -25,7 +28,7 @@ sys.path.insert(0, ROOT)
 
 from stlpose_amd import detector_train as T, efficientdet as E  # noqa: E402
 from stlpose_amd.launch import LaunchList  # noqa: E402
-from tests import detector_bifpn_ref as BR, detector_ref as R, detector_train_ref as TR  # noqa: E402
+from tests import detector_bifpn_first_ref as FR, detector_bifpn_ref as BR, detector_ref as R, detector_train_ref as TR  # noqa: E402
 from tools.detector_bench import timed  # noqa: E402
 from tools.detector_train_bench import BOXES, tr_gt  # noqa: E402
 
@@ -39,7 +42,7 @@ def main(outdir):
     ims = R.images()
     rows = []
     for cc in (0, 3):
-        ks = (0, 1, E.FPN_REPEATS[cc] - 1)
+        ks = (0, 1, E.FPN_REPEATS[cc] - 1, "all")
         models = {}
         for k in ks:
             m = E.setup_detector("efficientdet", "d3" if cc else "d0")
@@ -65,8 +68,12 @@ def main(outdir):
             for k in ks:   # the trainable part in eager torch, from the maps the plan of this k made
                 m, p = models[k][0], plans[k]
                 n = len(p.cells)
-                cells = list(range(n - k, n))
-                ins = [p.cells[n - k - 1][name][2].permute(0, 3, 1, 2).contiguous() for name in LEVEL_NODES]
+                nk = n if k == "all" else k
+                cells = list(range(n - nk, n))
+                if k == "all":   # from the backbone's maps
+                    ins = [f.permute(0, 3, 1, 2).contiguous() for f in p.backbone]
+                else:
+                    ins = [p.cells[n - k - 1][name][2].permute(0, 3, 1, 2).contiguous() for name in LEVEL_NODES]
                 esd = BR.train_state(m.state_dict(), cells, torch.float32)
                 esd = {name: v.detach().to(dev).requires_grad_(v.requires_grad) for name, v in esd.items()}
                 eopt = torch.optim.SGD([v for v in esd.values() if v.requires_grad], lr=1e-5)
@@ -76,7 +83,10 @@ def main(outdir):
                     eopt.zero_grad(set_to_none=True)
                     levels = ins
                     for j in cells:
-                        levels = BR.levels_of(BR.cell_forward(esd, j, levels, pool=lambda name, t: R._pool(t)))
+                        if j == 0:
+                            levels = BR.levels_of(FR.cell0_forward(esd, *levels, pool=lambda name, t: R._pool(t)))
+                        else:
+                            levels = BR.levels_of(BR.cell_forward(esd, j, levels, pool=lambda name, t: R._pool(t)))
                     reg, cls = TR.heads_forward(esd, cc, 1, levels)
                     _, dreg, dlogit, _ = torch.ops.stlpose.det_loss(reg.detach(), cls.detach(), m._anchor_dev, gt, off, 0.25, 2.0, 50.0)
                     pd = cls.detach()
@@ -99,7 +109,10 @@ def main(outdir):
                 if k:
                     cells_ms, eager_cells_ms = md["train"] - med[0]["train"], md["eager"] - med[0]["eager"]
                     row.update(cells_ms=cells_ms, eager_cells_ms=eager_cells_ms, eager_cells_over_native=eager_cells_ms / cells_ms)
-                    if B == 32 and k == ks[-1]:
+                    if k == "all":
+                        first_ms, eager_first_ms = md["train"] - med[ks[-2]]["train"], md["eager"] - med[ks[-2]]["eager"]
+                        row.update(first_cell_ms=first_ms, eager_first_cell_ms=eager_first_ms, eager_first_cell_over_native=eager_first_ms / first_ms)
+                    if B == 32 and k in ks[-2:]:
                         first = tr.bwd.names().index("stl_det_grad_add")   # the heads' launches come first
                         cells_bwd = LaunchList(tr.bwd.keep)
                         cells_bwd.calls = tr.bwd.calls[first:]
