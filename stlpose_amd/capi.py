@@ -54,6 +54,8 @@ globals().update({name[len("STL_"):]: value for name, value in DET_BATCH.constan
 # StlDetFuse from stlpose_hip.h
 DET_BIFPN = Header(os.path.join(INCLUDE, "stlpose_hip_det_bifpn.h"), {"StlDetFuseBwd": "DetFuseBwd"}, base=HEADER)
 DetFuseBwd = DET_BIFPN.structs["StlDetFuseBwd"]
+# include/stlpose_hip_det_mbconv.h: the new pieces of an MBConv block's backward (csrc/detector_mbconv.hip), part of the product library
+DET_MBCONV = Header(os.path.join(INCLUDE, "stlpose_hip_det_mbconv.h"))
 # include/stlpose_hip_math.h: the values of stl_conv.math
 MATH = Header(os.path.join(INCLUDE, "stlpose_hip_math.h"))
 globals().update({name[len("STL_"):]: value for name, value in MATH.constants.items()})   # MATH_NATIVE, MATH_BF16X3
@@ -106,7 +108,7 @@ def lib() -> C.CDLL:
         for name, args in SIGNATURES.items():
             fn = getattr(l, name)  # AttributeError if the library lacks a symbol of the header
             fn.argtypes, fn.restype = args, RESTYPES[name]
-        for header in (DETECTIONS, DET_BATCH, DET_BIFPN):
+        for header in (DETECTIONS, DET_BATCH, DET_BIFPN, DET_MBCONV):
             for name, args in header.signatures.items():
                 fn = getattr(l, name)
                 fn.argtypes, fn.restype = args, header.restypes[name]

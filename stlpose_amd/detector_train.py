@@ -34,6 +34,19 @@ conv and BN), then the weight gradients of the six 1x1 layers (stl_det_pointwise
 the three ``*_down_channel``, the two ``*_down_channel_2``; ``_Plan.first_pools`` / ``first_convs``).  No data gradient is computed for
 P3 / P4 / P5: nothing before them trains.  ``fold_chain`` carries each folded pair to the conv's weight and bias and the BN's.
 
+``model.set_train_backbone(k)`` (needs "all"; fp32) trains the last k MBConv blocks of the backbone's final stage too (block 15 of D0,
+blocks 24 / 25 of D3: 3x3 stride-1 depthwise layers).  The forward is the inference forward (no drop-connect, BN on running
+statistics); ``_Plan.blocks`` keeps each block's input, expand output e, depthwise output a, gate g and output.  Behind the cells'
+launches (``_blocks_bwd``): stl_det_pointwise_bwd_data of ``p5_to_p6``, ``p5_down_channel`` and ``p5_down_channel_2`` into a buffer
+each, joined in that order by stl_det_grad_add -- the gradient of P5; then per block, the last first, with the folded weights: D = dy
+Wp'^T (stl_det_pointwise_bwd_data); stl_det_mbconv_gate_bwd (csrc/detector_mbconv.hip: xs = a g, sum a, sum D a); the projection's
+weight gradient with x = xs; stl_det_se_bwd (dpool and the four SE gradients); the depthwise pre-activation u recomputed by
+stl_det_dwconv at act 0; stl_det_mbconv_act_bwd (du = (D g + dpool / HW) swish'(u) over D, and the folded BN's bias gradient);
+stl_det_dwconv_bwd_weight (x = e); the expand layer's pre-activation recomputed by stl_det_pointwise at act 0;
+stl_det_dwconv_bwd_data (times swish' of it); the expand layer's weight gradient (x = the block input); and, where the block in front
+trains too, its data gradient plus dy through the skip.  ``block_raw_grads`` carries the folded gradients to the raw parameters
+(``fold_chain`` without a conv bias, ``dw_fold_chain``).  P3 / P4 and every block in front stay frozen.
+
 A model with ``compute_dtype="f16"`` trains in 16 bit, by the recipe of the pose network's mixed mode: the trunk runs as the 16-bit
 inference plan's launches, the heads' forward tensors (every depthwise output d, pre-activation z and swish output t) are f16, the
 gradients in flight are bf16, every sum is fp32, and the folded gradients come out in the same fp32 ``grads`` tensors, so
@@ -99,11 +112,21 @@ def pack_targets(targets, sizes: Sequence[Tuple[int, int]], num_classes: int):
 def fold_chain(W, b, gamma, mean, var, eps, GW, Gb):
     """Gradients of the folded pointwise layer W' = W s[:, None], b' = b s + beta - mean s, s = gamma / sqrt(var + eps) (frozen
     running statistics), carried to the raw parameters: W, GW [co, ci]; b, gamma, mean, var, Gb [co].  Returns (dW, db, dgamma,
-    dbeta)."""
+    dbeta).  b None: a conv without bias (b' = beta - mean s); db is None then."""
     r = torch.rsqrt(var + eps)
     s = gamma * r
-    ds = (GW * W).sum(1) + Gb * (b - mean)
-    return GW * s[:, None], Gb * s, ds * r, Gb
+    ds = (GW * W).sum(1) + Gb * ((b - mean) if b is not None else -mean)
+    return GW * s[:, None], None if b is None else Gb * s, ds * r, Gb
+
+
+def dw_fold_chain(w, gamma, mean, var, eps, Gw, Gb):
+    """fold_chain's depthwise counterpart: gradients of the folded depthwise layer w' = w s[:, None, None], b' = beta - mean s (a
+    conv without bias under a frozen BN) carried to the raw parameters: w, Gw [c, k, k]; gamma, mean, var, Gb [c].  Returns (dw,
+    dgamma, dbeta)."""
+    r = torch.rsqrt(var + eps)
+    s = gamma * r
+    ds = (Gw * w).sum((1, 2)) - Gb * mean
+    return Gw * s[:, None, None], ds * r, Gb
 
 
 # ------------------------------------------------------------------------------------------------ launches
@@ -134,9 +157,14 @@ class HeadTrain:
         slabs = getattr(lib, self._name("stl_det_pointwise_bwd_slabs"))
         self.ncells = ncells = m.train_bifpn   # the trailing BiFPN cells that train with the heads
         self.first = ncells == len(plan.cells)   # every cell: the first one's 1x1 layers (Ci = the backbone's channels) and plain pools too
+        self.nblocks = nblocks = getattr(m, "train_backbone", 0)   # the trailing MBConv blocks that train with them
+        assert not nblocks or self.first, "the backbone's blocks train with every BiFPN cell only"
         npart = slabs(m0) * (c * kmax + kmax)
         if self.first:   # the largest slabs * (Ci * Co + Co) that is listed
             npart = max([npart] + [slabs(x.numel() // x.shape[3]) * (x.shape[3] * c + c) for x, _, _ in plan.first_convs.values()])
+        for inp, _, a, _, y in plan.blocks[len(plan.blocks) - nblocks:]:   # the blocks' expand and project layers
+            ci, mid, co = inp.shape[3], a.shape[3], y.shape[3]
+            npart = max(npart, slabs(a.numel() // mid) * max(ci * mid + mid, mid * co + co))
         self.pw_part = torch.empty(npart, device=dev)
         self.dw_part = torch.empty(getattr(lib, self._name("stl_det_dwconv_bwd_parts"))(m0) * 9 * c, device=dev)
         self.grads: Dict[str, Dict[str, torch.Tensor]] = {}
@@ -180,6 +208,9 @@ class HeadTrain:
                 aoff += hh * hh * 9
         if ncells:
             self._cells_bwd(plan, L)
+        self.bgrads = {}
+        if nblocks:
+            self._blocks_bwd(m, plan, L)
 
     def _cells_bwd(self, plan, L) -> None:
         """The backward launches of the trainable cells, behind the heads'."""
@@ -234,6 +265,85 @@ class HeadTrain:
             self.bwd.keep_alive(x, dy, g["pw_w"], g["pw_b"])   # the descriptor holds their addresses
             self.bwd.add("stl_det_pointwise_bwd_weight", p)
 
+    def _pw_bwd_data(self, plan, pk, dy, dx, hw, ci, co) -> None:
+        """The data gradient alone of the pointwise layer packed as pk: dx [B hw, ci] = dy [B hw, co] W'^T."""
+        p = capi.DetPointwiseBwd(None, plan.wbuf[pk[0]:].data_ptr(), dy.data_ptr(), dx.data_ptr(), None, None, None, self.B * hw, hw * co,
+                                 co, 0, hw, ci, co, pk[2], pk[3], 0)
+        self.bwd.keep_alive(dy, dx)   # the descriptor holds their addresses
+        self.bwd.add("stl_det_pointwise_bwd_data", p)
+
+    def _pw_bwd_weight(self, pk, x, dy, gw, gb, hw, ci, co) -> None:
+        """The weight and bias gradient alone of the pointwise layer packed as pk, x [B hw, ci], dy [B hw, co]."""
+        p = capi.DetPointwiseBwd(x.data_ptr(), None, dy.data_ptr(), None, gw.data_ptr(), gb.data_ptr(), self.pw_part.data_ptr(),
+                                 self.B * hw, hw * co, co, 0, hw, ci, co, pk[2], pk[3], 0)
+        self.bwd.keep_alive(x, dy, gw, gb)   # the descriptor holds their addresses
+        self.bwd.add("stl_det_pointwise_bwd_weight", p)
+
+    def _blocks_bwd(self, m, plan, L) -> None:
+        """The backward launches of the trainable MBConv blocks (csrc/detector_mbconv.hip), behind the cells': the data gradient of P5
+        through the three 1x1 layers of the first cell that read it, then the blocks, the last one first."""
+        B, dev, lib = self.B, self.dev, capi.lib()
+        specs, nb = m.backbone_net.model.specs, len(plan.blocks)
+        p5 = plan.backbone[2]
+        h, c5 = p5.shape[1], p5.shape[3]
+        hw = h * h
+        assert plan.blocks[-1][4] is p5
+        self.blocks_start = len(self.bwd)   # bwd.calls[blocks_start:] are these launches
+        parts = []
+        for key in ("p5_to_p6", "p5_down_channel", "p5_down_channel_2"):   # each into a buffer of its own, joined in this order
+            x, y, pk = plan.first_convs[key]
+            assert x is p5, key
+            parts.append(torch.empty_like(p5))
+            self._pw_bwd_data(plan, pk, self.gmap[y.data_ptr()], parts[-1], hw, c5, self.c)
+        dy = self.gp5 = parts[0]   # the gradient of P5
+        for t in parts[1:]:
+            self.bwd.add("stl_det_grad_add", dy, t, None, None, dy, dy.numel())
+        self.bwd.keep_alive(*parts)
+        first = nb - self.nblocks
+        mids = [specs[i]["mid"] for i in range(first, nb)]
+        ses = [specs[i]["se"] for i in range(first, nb)]
+        # scratch shared by the blocks, sized for the widest: D / du, xs / u / z_e, dz_e; and the small ones
+        s1, s2, s3 = (torch.empty(B * hw * max(mids), device=dev) for _ in range(3))
+        gate_ws = torch.empty(max(lib.stl_det_mbconv_gate_bwd_workspace(B, hw, mid) for mid in mids), device=dev)
+        act_ws = torch.empty(max(lib.stl_det_mbconv_act_bwd_workspace(B, hw, mid) for mid in mids), device=dev)
+        se_ws = torch.empty(max(lib.stl_det_se_bwd_workspace(B, mid, cs) for mid, cs in zip(mids, ses)), device=dev)
+        asum, dgate, dpool = (torch.empty(B * max(mids), device=dev) for _ in range(3))
+        dwb_part = torch.empty(lib.stl_det_dwconv_bwd_parts(B * hw) * 9 * max(mids), device=dev)
+        self.bwd.keep_alive(s1, s2, s3, gate_ws, act_ws, se_ws, asum, dgate, dpool, dwb_part)
+        for i in range(nb - 1, first - 1, -1):
+            b, lay = specs[i], L["blocks"][i]
+            inp, e, a, gate, y = plan.blocks[i]
+            ci, mid, co, cs = b["ci"], b["mid"], b["co"], b["se"]
+            assert b["k"] == 3 and b["s"] == 1 and e is not None and a.shape[1] == h and dy.shape == y.shape, i
+            g = self.bgrads[i] = dict(exp_w=torch.empty(ci, mid, device=dev), exp_b=torch.empty(mid, device=dev),
+                                      dw=torch.empty(3, 3, mid, device=dev), dw_b=torch.empty(mid, device=dev),
+                                      se_w1=torch.empty(cs, mid, device=dev), se_b1=torch.empty(cs, device=dev),
+                                      se_w2=torch.empty(mid, cs, device=dev), se_b2=torch.empty(mid, device=dev),
+                                      proj_w=torch.empty(mid, co, device=dev), proj_b=torch.empty(co, device=dev))
+            self.bwd.keep_alive(inp, e, a, gate, y, *g.values())
+            wd, bd = plan._w(lay["dw"][0]), plan._w(lay["dw"][1])
+            # the projection: D = dy Wp'^T; xs = a g, asum, dgate; dWp', dbp' with x = xs
+            self._pw_bwd_data(plan, lay["project"], dy, s1, hw, mid, co)
+            self.bwd.add("stl_det_mbconv_gate_bwd", a, s1, gate, s2, gate_ws, asum, dgate, B, hw, mid)
+            self._pw_bwd_weight(lay["project"], s2, dy, g["proj_w"], g["proj_b"], hw, mid, co)
+            # the gate: dpool and the SE gradients
+            self.bwd.add("stl_det_se_bwd", asum, dgate, gate, B, hw, mid, cs, *[plan._w(o) for o in lay["se"]], se_ws, dpool,
+                         g["se_w1"], g["se_b1"], g["se_w2"], g["se_b2"])
+            # the depthwise layer: u recomputed by the forward's launch without the activation; du overwrites D; db_d'; dw_d'
+            list_dwconv(self.bwd, 0, e, wd, bd, s2, B, h, mid, 3, 1, 0)
+            self.bwd.add("stl_det_mbconv_act_bwd", s1, s2, gate, dpool, s1, act_ws, g["dw_b"], B, hw, mid)
+            self.bwd.add("stl_det_dwconv_bwd_weight", e, s1, dwb_part, g["dw"], B, h, h, mid)
+            # the expand layer: its pre-activation z_e recomputed the same way, dz_e = dwconv^T(du) swish'(z_e); dWe', dbe'
+            list_pointwise(self.bwd, 0, plan.pw_fields(inp, s2, hw, ci, mid, lay["expand"], 0), False)
+            self.bwd.add("stl_det_dwconv_bwd_data", s1, wd, s2, s3, B, h, h, mid)
+            self._pw_bwd_weight(lay["expand"], inp, s3, g["exp_w"], g["exp_b"], hw, ci, mid)
+            if i > first:   # the block in front trains too: the gradient of this block's input, plus dy through the skip
+                dx = torch.empty_like(inp)
+                self._pw_bwd_data(plan, lay["expand"], s3, dx, hw, ci, mid)
+                if b["skip"]:
+                    self.bwd.add("stl_det_grad_add", dx, dy, None, None, dx, dx.numel())
+                dy = dx
+
     def _name(self, name: str) -> str:
         return NAME16[name] if self.h16 else name
 
@@ -279,12 +389,17 @@ def head_parameters(m) -> List[Tuple[str, torch.nn.Parameter]]:
 
 
 def trainable_parameters(m) -> List[Tuple[str, torch.nn.Parameter]]:
-    """What detection_loss differentiates: the parameters of the last ``m.train_bifpn`` BiFPN cells in state_dict order (after
-    ``set_train_bifpn("all")`` every cell's, the first cell's 24 conv and BN tensors among them), then head_parameters(m)."""
+    """What detection_loss differentiates: the parameters of the last ``m.train_backbone`` MBConv blocks in state_dict order (expand
+    conv and BN, depthwise conv and BN, the two SE convs, project conv and BN), then those of the last ``m.train_bifpn`` BiFPN cells
+    in state_dict order (after ``set_train_bifpn("all")`` every cell's, the first cell's 24 conv and BN tensors among them), then
+    head_parameters(m)."""
+    kb = getattr(m, "train_backbone", 0)
+    allb = m.backbone_net.model._blocks if kb else ()
+    blocks = [(f"backbone_net.model._blocks.{i}.{name}", p) for i in range(len(allb) - kb, len(allb)) for name, p in allb[i].named_parameters()]
     k = getattr(m, "train_bifpn", 0)
     n = len(m.bifpn) if k else 0
     cells = [(f"bifpn.{j}.{name}", p) for j in range(n - k, n) for name, p in m.bifpn[j].named_parameters()]
-    return cells + head_parameters(m)
+    return blocks + cells + head_parameters(m)
 
 
 def fusion_weight_grads(p: torch.Tensor, dwhat: torch.Tensor, eps: float = 1e-4) -> torch.Tensor:
@@ -316,6 +431,28 @@ def cell_raw_grads(m, tr: HeadTrain) -> Dict[str, torch.Tensor]:
         dW, db, dgam, dbeta = fold_chain(W, b, bn.weight.detach(), bn.running_mean, bn.running_var, bn.eps, g["pw_w"].t(), g["pw_b"])
         out[pre + "0.conv.weight"], out[pre + "0.conv.bias"] = dW[:, :, None, None], db
         out[pre + "1.weight"], out[pre + "1.bias"] = dgam, dbeta.clone()
+    return out
+
+
+def block_raw_grads(m, tr: HeadTrain) -> Dict[str, torch.Tensor]:
+    """{parameter name: gradient} of every parameter of the trainable MBConv blocks from the folded per-block gradients of tr: the
+    two pointwise layers by ``fold_chain`` (convs without bias), the depthwise layer by ``dw_fold_chain``, the SE convs as they are."""
+    out = {}
+    for i, g in tr.bgrads.items():
+        blk, pre = m.backbone_net.model._blocks[i], f"backbone_net.model._blocks.{i}."
+        for conv, bn, gw, gb in (("_expand_conv", "_bn0", g["exp_w"], g["exp_b"]), ("_project_conv", "_bn2", g["proj_w"], g["proj_b"])):
+            pw, n = getattr(blk, conv).conv, getattr(blk, bn)
+            W = pw.weight.detach().reshape(pw.out_channels, pw.in_channels)
+            dW, _, dgam, dbeta = fold_chain(W, None, n.weight.detach(), n.running_mean, n.running_var, n.eps, gw.t(), gb)
+            out[pre + conv + ".conv.weight"] = dW[:, :, None, None]
+            out[pre + bn + ".weight"], out[pre + bn + ".bias"] = dgam, dbeta.clone()
+        n = blk._bn1
+        dw, dgam, dbeta = dw_fold_chain(blk._depthwise_conv.conv.weight.detach()[:, 0], n.weight.detach(), n.running_mean, n.running_var,
+                                        n.eps, g["dw"].permute(2, 0, 1), g["dw_b"])
+        out[pre + "_depthwise_conv.conv.weight"] = dw[:, None]
+        out[pre + "_bn1.weight"], out[pre + "_bn1.bias"] = dgam, dbeta.clone()
+        out[pre + "_se_reduce.conv.weight"], out[pre + "_se_reduce.conv.bias"] = g["se_w1"][:, :, None, None].clone(), g["se_b1"].clone()
+        out[pre + "_se_expand.conv.weight"], out[pre + "_se_expand.conv.bias"] = g["se_w2"][:, :, None, None].clone(), g["se_b2"].clone()
     return out
 
 
@@ -367,10 +504,13 @@ class _DetLossFn(torch.autograd.Function):
             tr.backward(ops._st())
             grads = raw_grads(ctx.m, tr)
             scale = {"regressor": gr, "classifier": gc}   # dreg / dlogit are the gradients of the regression / classification loss
-            out = [grads[n].contiguous() * scale[n.split(".", 1)[0]] for n in ctx.names if not n.startswith("bifpn.")]
+            out = [grads[n].contiguous() * scale[n.split(".", 1)[0]] for n in ctx.names if n.startswith(HEADS)]
             if tr.ncells:
                 cells = cell_raw_grads(ctx.m, tr)
                 out = [cells[n].contiguous() for n in ctx.names if n.startswith("bifpn.")] + out
+            if tr.nblocks:
+                blocks = block_raw_grads(ctx.m, tr)
+                out = [blocks[n].contiguous() for n in ctx.names if n.startswith("backbone_net.")] + out
         return (None, None, None, None, *out)
 
 
@@ -397,7 +537,7 @@ def detection_loss(m, inputs, targets, alpha: float = 0.25, gamma: float = 2.0, 
             p, _, keep = m._preprocess(srcs, 1, dev)
         canvas, gt_dev, offsets_dev = None, torch.from_numpy(gt).to(dev), torch.from_numpy(offsets).to(dev)
     with torch.no_grad():
-        if p.train is None or p.train.ncells != m.train_bifpn:
+        if p.train is None or p.train.ncells != m.train_bifpn or p.train.nblocks != m.train_backbone:
             p.train = HeadTrain(m, p)
         tr = p.train
         p.run(st, upto=p.head_start, canvas=canvas)

@@ -24,7 +24,10 @@ backbone and the BiFPN are frozen, every BN stays on its running statistics, and
 ``.grad`` of the ``regressor.*`` and ``classifier.*`` parameters.  ``set_train_bifpn(k)`` (fp32) is the next stage: the last k BiFPN
 cells, 1 <= k <= cells - 1, train with the heads (csrc/detector_bifpn.hip; ``detector_train.trainable_parameters``); the cells before
 them and the backbone stay frozen.  ``set_train_bifpn("all")`` trains every cell, the first one with its down-channel convs,
-``p5_to_p6`` and the two plain pooled maps included: everything behind the backbone, which stays frozen.
+``p5_to_p6`` and the two plain pooled maps included: everything behind the backbone, which stays frozen unless
+``set_train_backbone(k)`` (after "all"; fp32) also trains the last k MBConv blocks, 0 <= k <= the blocks of the final stage (1 for D0, 2
+for D3: the ones that produce P5; csrc/detector_mbconv.hip).  The blocks are packed in front of the cells, so an optimiser step still
+rewrites one tail of the weight buffer.
 """
 from __future__ import annotations
 
@@ -391,6 +394,7 @@ class _Plan:
         self._cost(2 * x.numel() * 27, 4 * self.canvas.numel() + self.es * x.numel())
         h = H
         feats, specs = [], net.specs
+        self.blocks = []   # per MBConv block (input, expand output e or None, depthwise output a, SE gate, output): the blocks' backward reads them
         for i, (b, lay) in enumerate(zip(specs, L["blocks"])):
             if b["s"] == 2:   # the wrapper keeps the input of every stride-2 block (efficientdet_utils/model.py:413-414)
                 feats.append((x, h))
@@ -399,6 +403,7 @@ class _Plan:
                 y = self._buf(B, h, h, b["mid"])
                 self._pw(x, y, h * h, b["ci"], b["mid"], lay["expand"], act=1)
                 x = y
+            e = x if b["e"] != 1 else None
             ho = (h + b["s"] - 1) // b["s"]
             y = self._buf(B, ho, ho, b["mid"])
             scale = torch.empty(B, b["mid"], device=dev)
@@ -418,6 +423,7 @@ class _Plan:
                 self._cost(x.numel() + 4 * B * b["mid"] * b["se"], 4 * x.numel(), launches=2)
             y = self._buf(B, h, h, b["co"])
             self._pw(x, y, h * h, b["mid"], b["co"], lay["project"], act=0, in_scale=scale, residual=inp if b["skip"] else None)
+            self.blocks.append((inp, e, x, scale, y))
             x = y
         feats.append((x, h))
         p3, p4, p5 = feats[-3:]
@@ -610,6 +616,7 @@ class EfficientDetBackbone(nn.Module):
         self._wbufT16, self._layoutT = None, None   # the heads' bf16 transposed packs (_ensure_transposed: models that train only)
         self._batch_tables: dict = {}               # _batch_records: the constant record table of a DetBatch geometry
         self.train_bifpn = 0                        # set_train_bifpn: how many trailing BiFPN cells detection_loss trains with the heads ("all": every cell)
+        self.train_backbone = 0                     # set_train_backbone: how many trailing MBConv blocks train with them (the final stage's)
         self.eval()
 
     # ---------------------------------------------------------------- state
@@ -628,6 +635,9 @@ class EfficientDetBackbone(nn.Module):
             raise ValueError(f"EfficientDet.set_train_bifpn: k = {k!r}, expected 0 .. {n - 1}: the first of the {n} BiFPN cells does not "
                              "train by count -- it alone has the down-channel convs, p5_to_p6 and the unweighted pooled maps; "
                              "set_train_bifpn(\"all\") trains it with every cell behind it")
+        if self.train_backbone and k != n:
+            raise ValueError(f"EfficientDet.set_train_bifpn: {self.train_backbone} backbone block(s) train, which needs every BiFPN cell to "
+                             "train (the gradient of P5 exists only when the first cell trains): call set_train_backbone(0) first")
         if k != self.train_bifpn:
             current = self._version is not None and self._state_version() == self._version
             self.train_bifpn = k
@@ -636,15 +646,57 @@ class EfficientDetBackbone(nn.Module):
                 p.train = None   # its backward launches are listed for one k
         return self
 
+    def final_stage_blocks(self) -> int:
+        """The number of MBConv blocks of the backbone's final stage, the ones that produce P5 (from ``block_specs``: the trailing
+        expanding blocks whose depthwise layer is 3 x 3, stride 1 -- what the blocks' backward covers)."""
+        specs, n = self.backbone_net.model.specs, 0
+        while n < len(specs) and specs[-1 - n]["k"] == 3 and specs[-1 - n]["s"] == 1 and specs[-1 - n]["e"] != 1:
+            n += 1
+        return n
+
+    def set_train_backbone(self, k) -> "EfficientDetBackbone":
+        """The last k MBConv blocks of the backbone train with the BiFPN and the heads in detection_loss (0: none), k = 0 .. the
+        blocks of the final stage (1 for D0, 2 for D3), the ones that produce P5.  Needs ``set_train_bifpn("all")``: the gradient of
+        P5 exists only when the first cell trains.  fp32 only; every BN stays on its running statistics; drop-connect is not
+        applied (the training forward is the inference forward)."""
+        n = self.final_stage_blocks()
+        if not isinstance(k, int) or isinstance(k, bool) or k < 0:
+            raise ValueError(f"EfficientDet.set_train_backbone: k = {k!r}, expected 0 .. {n}")
+        if k > n:
+            raise ValueError(f"EfficientDet.set_train_backbone: k = {k!r}, expected 0 .. {n}: only the {n} block(s) of the backbone's final "
+                             "stage train -- the blocks in front have 5x5 / stride-2 depthwise layers whose backward does not exist yet")
+        if k and self.train_bifpn != len(self.bifpn):
+            raise ValueError("EfficientDet.set_train_backbone: the gradient of P5 exists only when the first BiFPN cell trains: call "
+                             "set_train_bifpn(\"all\") first")
+        if k != self.train_backbone:
+            current = self._version is not None and self._state_version() == self._version
+            self.train_backbone = k
+            self._version = self._state_version() if current else None   # the same weights, split anew; else a full refold
+            for p in self._plans.values():
+                p.train = None   # its backward launches are listed for one k
+        return self
+
     def _state_version(self):
-        """(trunk, cells, heads): data pointer and version of every parameter and buffer of the frozen trunk, of the trainable BiFPN
-        cells (the last train_bifpn) and of regressor.* / classifier.*"""
+        """(trunk, blocks, cells, heads): data pointer and version of every parameter and buffer of the frozen trunk, of the trainable
+        MBConv blocks (the last train_backbone), of the trainable BiFPN cells (the last train_bifpn) and of regressor.* / classifier.*"""
         owned = lambda mods: [t for h in mods for t in list(h.parameters()) + list(h.buffers())]   # noqa: E731
+        allb = list(self.backbone_net.model._blocks)
+        blocks = owned(allb[len(allb) - self.train_backbone:])
         cells = owned(list(self.bifpn)[len(self.bifpn) - self.train_bifpn:])
         heads = owned((self.regressor, self.classifier))
-        ids = {id(t) for t in cells + heads}
+        ids = {id(t) for t in blocks + cells + heads}
         trunk = [t for t in list(self.parameters()) + list(self.buffers()) if id(t) not in ids]
-        return tuple(tuple((t.data_ptr(), t._version) for t in ts) for ts in (trunk, cells, heads))
+        return tuple(tuple((t.data_ptr(), t._version) for t in ts) for ts in (trunk, blocks, cells, heads))
+
+    @staticmethod
+    def _pack_block(P: _Packer, blk, b) -> dict:
+        lay = {"dw": P.dw(blk._depthwise_conv.conv, blk._bn1), "project": P.pw(blk._project_conv.conv, blk._bn2)}
+        if b["e"] != 1:
+            lay["expand"] = P.pw(blk._expand_conv.conv, blk._bn0)
+        r, e = blk._se_reduce.conv, blk._se_expand.conv
+        lay["se"] = (P.add(r.weight.detach().reshape(b["se"], b["mid"])), P.add(r.bias.detach()),
+                     P.add(e.weight.detach().reshape(b["mid"], b["se"])), P.add(e.bias.detach()))
+        return lay
 
     @staticmethod
     def _pack_cell(P: _Packer, cell):
@@ -668,12 +720,19 @@ class EfficientDetBackbone(nn.Module):
                            "hdw": P.dw(hd.header.depthwise_conv.conv)[0], "hpw": P.pw(hd.header.pointwise_conv.conv)}
         return heads
 
-    def _refold_tail(self, first: int) -> None:
+    def _refold_tail(self, first: int, block: Optional[int] = None) -> None:
         """Only the BiFPN cells from `first` on and regressor.* / classifier.* changed (an optimiser step of detection_loss; first =
         len(bifpn): the heads alone).  The cells are packed in order and the heads last, so these pieces are one tail of the weight
-        buffers: it is rewritten in place, through the same packing as a full refold (bit-identical); the plans stay."""
+        buffers: it is rewritten in place, through the same packing as a full refold (bit-identical); the plans stay.  block: the
+        MBConv blocks from that one on changed too (first = 0 then); they are packed in front of the cells: a longer tail."""
         P = _Packer(COMPUTE_DTYPES[self.compute_dtype][0])
-        n0, n16 = P.n, P.n16 = self._tail_off[first]
+        net = self.backbone_net.model
+        n0, n16 = P.n, P.n16 = self._tail_off[first] if block is None else self._block_off[block]
+        if block is not None:
+            assert first == 0, "EfficientDet: trainable blocks without every cell"
+            for i in range(block, len(net._blocks)):
+                assert self._pack_block(P, net._blocks[i], net.specs[i]) == self._layout["blocks"][i], "EfficientDet: block layout changed"
+            assert (P.n, P.n16) == self._tail_off[0], "EfficientDet: block layout changed"
         for j in range(first, len(self.bifpn)):
             lay, woff = self._pack_cell(P, self.bifpn[j])
             assert all(lay[k] == self._layout["bifpn"][j][k] for k in lay) and woff == self._woff[j], "EfficientDet: BiFPN layout changed"
@@ -706,24 +765,21 @@ class EfficientDetBackbone(nn.Module):
             self.to(dev)
         v = self._state_version()
         if self._version is not None and v[0] == self._version[0] and self._wbuf is not None and self._wbuf.device == dev:
-            if v[1:] != self._version[1:]:
-                self._refold_tail(len(self.bifpn) - (self.train_bifpn if v[1] != self._version[1] else 0))
-                self._version = v
+            if v[1] != self._version[1]:   # the trainable blocks moved: with them every cell trains
+                self._refold_tail(0, len(self.backbone_net.model._blocks) - self.train_backbone)
+            elif v[2:] != self._version[2:]:
+                self._refold_tail(len(self.bifpn) - (self.train_bifpn if v[2] != self._version[2] else 0))
+            self._version = v
             return
         P = _Packer(COMPUTE_DTYPES[self.compute_dtype][0])
         net = self.backbone_net.model
         s, t = _fold(net._bn0)
         stem = (P.add((net._conv_stem.conv.weight.detach().double() * s[:, None, None, None]).permute(2, 3, 1, 0).contiguous()),
                 P.add(t))
-        blocks = []
+        blocks, self._block_off = [], []   # _block_off[i]: where block i starts in the two buffers (the blocks in order, in front of the cells)
         for blk, b in zip(net._blocks, net.specs):
-            lay = {"dw": P.dw(blk._depthwise_conv.conv, blk._bn1), "project": P.pw(blk._project_conv.conv, blk._bn2)}
-            if b["e"] != 1:
-                lay["expand"] = P.pw(blk._expand_conv.conv, blk._bn0)
-            r, e = blk._se_reduce.conv, blk._se_expand.conv
-            lay["se"] = (P.add(r.weight.detach().reshape(b["se"], b["mid"])), P.add(r.bias.detach()),
-                         P.add(e.weight.detach().reshape(b["mid"], b["se"])), P.add(e.bias.detach()))
-            blocks.append(lay)
+            self._block_off.append((P.n, P.n16))
+            blocks.append(self._pack_block(P, blk, b))
         cells, self._woff, self._tail_off = [], [], []   # _tail_off[j]: where cell j starts in the two buffers, [len(bifpn)]: where the heads do
         for cell in self.bifpn:          # (cells in order, the heads last: _refold_tail rewrites the buffers from one of these on)
             self._tail_off.append((P.n, P.n16))
@@ -828,7 +884,7 @@ class EfficientDetBackbone(nn.Module):
         forward takes them; targets one dict per image with ``boxes`` [n, 4] (x1, y1, x2, y2 in original pixels) and ``labels``
         [n] in 1 .. num_classes (n = 0 allowed).  Returns {"classification", "regression"}: fp32 device scalars whose backward
         fills ``.grad`` of every regressor.* and classifier.* parameter and, after ``set_train_bifpn(k)``, of the last k BiFPN cells'
-        (``"all"``: of every cell's; fp32 only); the backbone and the other cells are frozen and every BN runs on its running statistics, whatever ``.training`` is.  compute_dtype "fp32", or "f16" (f16 forward tensors, bf16 gradients in
+        (``"all"``: of every cell's; fp32 only) and, after ``set_train_backbone(k)``, of the backbone's last k MBConv blocks'; the rest of the backbone and the other cells are frozen and every BN runs on its running statistics, whatever ``.training`` is.  compute_dtype "fp32", or "f16" (f16 forward tensors, bf16 gradients in
         flight, fp32 sums and fp32 ``.grad``; non-finite head outputs raise FloatingPointError); "bf16" raises
         NotImplementedError.  One activation set per batch size: backward before the
         next detection_loss of that batch size (a stale-forward error otherwise).  See stlpose_amd/detector_train.py.
