@@ -26,7 +26,10 @@ extern "C" {
 #endif
 
 /* The pixel ranges one image's HW pixels are split into by gate_bwd and act_bwd: one workgroup and one partial sum per (image,
- * range, 64 or 256 channels).  1 .. 16. */
+ * range, 64 or 256 channels).  1 .. 16 up to 1024 pixels; above that ranges of 64 pixels, at most 1024 of them.
+ * A change for direct callers: up to 1024 pixels the results and the workspace sizes are what they were, bit for bit; above 1024
+ * pixels the count was 16 before, so the *_workspace queries return up to 64 times as much (call them again, do not keep an old
+ * size) and asum, dgate and db come out in other bits, closer to the exact sums. */
 int stl_det_mbconv_parts(int HW);
 
 /* One pass over a and D [B, HW, C]: xs [B, HW, C] = a * g[b, c]; asum [B, C] = sum_hw a; dgate [B, C] = sum_hw D * a.  g [B, C].
@@ -52,11 +55,41 @@ int64_t stl_det_se_bwd_workspace(int B, int C, int Cs);
 /* du [B, HW, C] = (D * g[b, c] + dpool[b, c] / HW) * swish'(u), u the depthwise layer's pre-activation (stl_det_dwconv with act 0);
  * du may be D.  db [C] = sum_{b, hw} du: one partial sum per (image, pixel range) -- stl_det_mbconv_act_bwd_parts(B, HW) of them,
  * summed as in gate_bwd -- added in (image, range) order by a second launch (fp64, rounded once).  partial:
- * stl_det_mbconv_act_bwd_workspace(B, HW, C) floats.  The vector path as in gate_bwd.  Two launches. */
+ * stl_det_mbconv_act_bwd_workspace(B, HW, C) floats.  The vector path as in gate_bwd.  Two launches; above 1024 pixels three: an
+ * image's ranges first (fp64, kept as a float pair), then the images in order. */
 int stl_det_mbconv_act_bwd(const float* D, const float* u, const float* g, const float* dpool, float* du, float* partial, float* db, int B,
                            int HW, int C, void* stream);
 int64_t stl_det_mbconv_act_bwd_workspace(int B, int HW, int C);
 int stl_det_mbconv_act_bwd_parts(int B, int HW);
+
+/* ---- the rest of the trunk (stlpose_amd/csrc/detector_trunk.hip; ``model.set_train_trunk(k)`` trains the last k blocks of the whole
+ * backbone, "all" the stem too): the depthwise backward for every kernel size and stride of the backbone, k in {3, 5}, s in {1, 2},
+ * under the forward's TF "same" padding (stl_det_dwconv: before = max(0, (ceil(n / s) - 1) s - n + k) / 2 per axis), and the stem's
+ * weight gradient.  Four channels per thread, 16 bytes per lane: C % 4 == 0 and 16-byte aligned tensors, anything else is an error
+ * before a launch.  The 3 x 3 / 1 entry points of the heads (stl_det_dwconv_bwd_data / _weight, stlpose_hip.h) stay as they are. */
+
+/* dx [B, H, W, C] = the adjoint of stl_det_dwconv(k, s) applied to dy [B, ceil(H / s), ceil(W / s), C], w [k][k][C]; times swish'(z), z
+ * [B, H, W, C], where z is not NULL.  Gather form: one thread per (pixel of dx, 4 channels); s = 2 visits only the taps whose parity
+ * matches the pixel's (at most 3 x 3 of the 25 at k = 5).  dx may not overlap dy or w.  One launch. */
+int stl_det_dwconv_bwd_data_ks(const float* dy, const float* w, const float* z, float* dx, int B, int H, int W, int C, int k, int s,
+                               void* stream);
+
+/* dw [k][k][C] = sum over the OUTPUT pixels of x[the tap's input pixel] dy, x [B, H, W, C], dy [B, ceil(H / s), ceil(W / s), C].  One
+ * partial sum per workgroup, stl_det_dwconv_bwd_ks_parts(B ceil(H / s) ceil(W / s)) pixel ranges (a thread adds every P-th pixel of its
+ * range in order, the P pixel lanes of the workgroup are added in lane order), then a second launch adds the ranges in range order.
+ * partial: parts k k C floats.  partial and dw may not overlap each other, x or dy.  Two launches. */
+int stl_det_dwconv_bwd_weight_ks(const float* x, const float* dy, float* partial, float* dw, int B, int H, int W, int C, int k, int s,
+                                 void* stream);
+int stl_det_dwconv_bwd_ks_parts(int64_t npix);
+
+/* The weight gradient of stl_det_stem (3 -> Co, 3 x 3 / 2, folded BN, swish): x the canvas [B, H, W, 3], w [3][3][3][Co] and bias [Co] as
+ * the forward takes them, dy [B, ceil(H / 2), ceil(W / 2), Co] the gradient of the stem's output.  The pre-activation z of an output
+ * pixel is recomputed from the canvas with the forward's expression; dz = dy swish'(z); dw [3][3][3][Co] = sum x dz, db [Co] = sum dz
+ * through stl_det_stem_bwd_parts(B ceil(H / 2) ceil(W / 2)) ordered partial sums as above.  partial: parts 28 Co floats.  No image
+ * gradient.  Two launches. */
+int stl_det_stem_bwd(const float* x, const float* w, const float* bias, const float* dy, float* partial, float* dw, float* db, int B,
+                     int H, int W, int Co, void* stream);
+int stl_det_stem_bwd_parts(int64_t npix);
 
 #ifdef __cplusplus
 }

@@ -21,6 +21,7 @@ UNITS = [("capi.hip", "capi", []), ("conv_core.hip", "conv_core_bf16", ["-DSTL_D
          ("program.hip", "program", []), ("retrieval.hip", "retrieval", []),
          ("topdown.hip", "topdown", []), ("detector.hip", "detector", []), ("detector_train.hip", "detector_train", []),
          ("detector_bifpn.hip", "detector_bifpn", []), ("detector_mbconv.hip", "detector_mbconv", []),
+         ("detector_trunk.hip", "detector_trunk", []),
          ("adain.hip", "adain", []), ("box_ap.hip", "box_ap", []), ("keypoint_eval.hip", "keypoint_eval", []),
          ("eval_tail.hip", "eval_tail", []), ("pose_batch.hip", "pose_batch", ["-ffp-contract=off"]),
          ("detections.hip", "detections", ["-ffp-contract=off"]), ("det_batch.hip", "det_batch", ["-ffp-contract=off"])]

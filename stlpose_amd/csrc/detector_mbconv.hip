@@ -29,7 +29,15 @@ __device__ __forceinline__ float dswishf(float z) {
 }
 
 constexpr int kPartsMax = 16, kPartPix = 16;   // at most 16 pixel ranges per image, of at least 16 pixels
+// Above 1024 pixels (the blocks in front of the final stage: up to 256 x 256) ranges of 64 pixels, at most 1024 of them: a thread's
+// fp32 chain stays 16 terms long -- with 16 ranges it would be 1024 terms at 256 x 256, and the sums' error several times that of a
+// pairwise sum -- and the ranges are added in fp64.
+constexpr int kLargeHW = 1024, kLargePartPix = 64, kLargePartsMax = 1024;
 static inline int parts_of(int HW) {
+    if (HW > kLargeHW) {
+        const int p = (HW + kLargePartPix - 1) / kLargePartPix;
+        return p > kLargePartsMax ? kLargePartsMax : p;
+    }
     const int p = (HW + kPartPix - 1) / kPartPix;
     return p < 1 ? 1 : (p > kPartsMax ? kPartsMax : p);
 }
@@ -161,6 +169,32 @@ __global__ __launch_bounds__(256) void act_sum_kernel(const float* __restrict__ 
     if (c >= C) return;
     double s = 0.0;
     for (int j = 0; j < n; ++j) s += (double)partial[(int64_t)j * C + c];
+    db[c] = (float)s;
+}
+
+// HW above kLargeHW (up to 1024 ranges per image: one thread per channel over all B * parts would be a chain of 32768 loads): first one
+// thread per (image, channel) adds the image's ranges in range order, fp64, and leaves the sum as a float pair (hi, lo) in the image's
+// first two ranges -- it alone reads or writes that column of that image --, then one thread per channel adds the images in order
+__global__ __launch_bounds__(256) void act_sum_image_kernel(float* partial, int parts, int B, int C) {
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= (int64_t)B * C) return;
+    float* q = partial + (e / C) * parts * C + e % C;
+    double s = 0.0;
+    for (int sp = 0; sp < parts; ++sp) s += (double)q[(int64_t)sp * C];
+    const float hi = (float)s;
+    q[0] = hi;
+    q[C] = (float)(s - (double)hi);
+}
+
+__global__ __launch_bounds__(256) void act_sum_images_kernel(const float* __restrict__ partial, int parts, int B, int C,
+                                                             float* __restrict__ db) {
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= C) return;
+    double s = 0.0;
+    for (int b = 0; b < B; ++b) {
+        const float* q = partial + (int64_t)b * parts * C + c;
+        s += (double)q[0] + (double)q[C];
+    }
     db[c] = (float)s;
 }
 
@@ -319,7 +353,15 @@ extern "C" int stl_det_mbconv_act_bwd(const float* D, const float* u, const floa
         STL_LAUNCH(act_bwd_kernel<1>, dim3((unsigned)((C + 63) / 64), parts, B), dim3(256), 0, ST, D, u, g, dpool, du, partial, HW, C, per);
     }
     STL_LAUNCH_CHECK("det_mbconv_act_bwd");
-    STL_LAUNCH(act_sum_kernel, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, ST, (const float*)partial, B * parts, C, db);
+    if (HW > kLargeHW) {
+        // act_sum_image_kernel keeps an image's (hi, lo) pair in its first two ranges: HW > kLargeHW gives at least 17
+        static_assert((kLargeHW + kLargePartPix) / kLargePartPix >= 2 && kLargePartsMax >= 2, "the two-stage bias sum needs two ranges");
+        STL_LAUNCH(act_sum_image_kernel, dim3((unsigned)(((int64_t)B * C + 255) / 256)), dim3(256), 0, ST, partial, parts, B, C);
+        STL_LAUNCH_CHECK("det_mbconv_act_bwd");
+        STL_LAUNCH(act_sum_images_kernel, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, ST, (const float*)partial, parts, B, C, db);
+    } else {
+        STL_LAUNCH(act_sum_kernel, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, ST, (const float*)partial, B * parts, C, db);
+    }
     STL_LAUNCH_CHECK("det_mbconv_act_bwd");
     return 0;
 }

@@ -47,6 +47,18 @@ stl_det_dwconv_bwd_data (times swish' of it); the expand layer's weight gradient
 trains too, its data gradient plus dy through the skip.  ``block_raw_grads`` carries the folded gradients to the raw parameters
 (``fold_chain`` without a conv bias, ``dw_fold_chain``).  P3 / P4 and every block in front stay frozen.
 
+``model.set_train_trunk(k)`` reaches further back: the last k blocks of the whole backbone, ``"all"`` the stem too.  The final stage's
+blocks keep the launches above; a block in front of it runs the same sequence with stl_det_dwconv_bwd_weight_ks / _data_ks
+(csrc/detector_trunk.hip: k 3 / 5, s 1 / 2 under TF "same" padding), the projection, gate, SE and act steps at the block's output
+resolution, the expand recompute, the depthwise data gradient and the expand gradients at its input resolution.  A block without an
+expand layer (e = 1) has no ``exp_w`` / ``exp_b``: its depthwise layer reads the block input, and stl_det_dwconv_bwd_data_ks without z
+is the input's gradient.  The gradient of a block's input is joined in a fixed order: the block's own data gradient, dy through the
+skip, then -- where the input is P4 / P3, the inputs of the last two stride-2 blocks -- stl_det_pointwise_bwd_data of
+``p4_down_channel`` and ``p4_down_channel_2`` / of ``p3_down_channel``, each into a buffer of its own and added by stl_det_grad_add.
+``tr.block_dy[i]`` keeps the joined gradient of block i's output, ``tr.stem_dy`` that of the stem's.  With the stem, block 0 also
+produces its input's gradient and stl_det_stem_bwd follows (the pre-activation recomputed from the canvas the forward read; no image
+gradient); its ``[3][3][3][Co]`` gradient is permuted to ``[Co, 3, 3, 3]`` and folded through ``_bn0`` as a conv without bias.
+
 A model with ``compute_dtype="f16"`` trains in 16 bit, by the recipe of the pose network's mixed mode: the trunk runs as the 16-bit
 inference plan's launches, the heads' forward tensors (every depthwise output d, pre-activation z and swish output t) are f16, the
 gradients in flight are bf16, every sum is fp32, and the folded gradients come out in the same fp32 ``grads`` tensors, so
@@ -56,6 +68,7 @@ not train: its forward error is several times that of f16.
 """
 from __future__ import annotations
 
+import ctypes
 from typing import Dict, List, Sequence, Tuple
 
 import numpy as np
@@ -158,13 +171,18 @@ class HeadTrain:
         self.ncells = ncells = m.train_bifpn   # the trailing BiFPN cells that train with the heads
         self.first = ncells == len(plan.cells)   # every cell: the first one's 1x1 layers (Ci = the backbone's channels) and plain pools too
         self.nblocks = nblocks = getattr(m, "train_backbone", 0)   # the trailing MBConv blocks that train with them
+        self.stem = bool(getattr(m, "train_stem", False))          # and the stem (with every block)
+        self.own_canvas = plan.canvas.data_ptr()
         assert not nblocks or self.first, "the backbone's blocks train with every BiFPN cell only"
+        assert not self.stem or nblocks == len(plan.blocks), "the stem trains with every block only"
         npart = slabs(m0) * (c * kmax + kmax)
         if self.first:   # the largest slabs * (Ci * Co + Co) that is listed
             npart = max([npart] + [slabs(x.numel() // x.shape[3]) * (x.shape[3] * c + c) for x, _, _ in plan.first_convs.values()])
-        for inp, _, a, _, y in plan.blocks[len(plan.blocks) - nblocks:]:   # the blocks' expand and project layers
+        for inp, e, a, _, y in plan.blocks[len(plan.blocks) - nblocks:]:   # the blocks' expand (input resolution) and project layers
             ci, mid, co = inp.shape[3], a.shape[3], y.shape[3]
-            npart = max(npart, slabs(a.numel() // mid) * max(ci * mid + mid, mid * co + co))
+            npart = max(npart, slabs(a.numel() // mid) * (mid * co + co))
+            if e is not None:
+                npart = max(npart, slabs(e.numel() // mid) * (ci * mid + mid))
         self.pw_part = torch.empty(npart, device=dev)
         self.dw_part = torch.empty(getattr(lib, self._name("stl_det_dwconv_bwd_parts"))(m0) * 9 * c, device=dev)
         self.grads: Dict[str, Dict[str, torch.Tensor]] = {}
@@ -279,14 +297,27 @@ class HeadTrain:
         self.bwd.keep_alive(x, dy, gw, gb)   # the descriptor holds their addresses
         self.bwd.add("stl_det_pointwise_bwd_weight", p)
 
+    def _join(self, plan, dx, x, keys) -> None:
+        """dx, the gradient of the backbone map x, += the data gradients of the first cell's 1x1 layers `keys` that read x: each into a
+        buffer of its own, added in the order of `keys`."""
+        hw, ci = x.shape[1] * x.shape[2], x.shape[3]
+        for key in keys:
+            xx, y, pk = plan.first_convs[key]
+            assert xx is x, key
+            t = torch.empty_like(x)
+            self._pw_bwd_data(plan, pk, self.gmap[y.data_ptr()], t, hw, ci, self.c)
+            self.bwd.add("stl_det_grad_add", dx, t, None, None, dx, dx.numel())
+            self.bwd.keep_alive(t)
+
     def _blocks_bwd(self, m, plan, L) -> None:
-        """The backward launches of the trainable MBConv blocks (csrc/detector_mbconv.hip), behind the cells': the data gradient of P5
-        through the three 1x1 layers of the first cell that read it, then the blocks, the last one first."""
+        """The backward launches of the trainable MBConv blocks (csrc/detector_mbconv.hip, csrc/detector_trunk.hip), behind the cells':
+        the data gradient of P5 through the three 1x1 layers of the first cell that read it, then the blocks, the last one first, then
+        the stem's weight gradient when it trains."""
         B, dev, lib = self.B, self.dev, capi.lib()
-        specs, nb = m.backbone_net.model.specs, len(plan.blocks)
-        p5 = plan.backbone[2]
+        net = m.backbone_net.model
+        specs, nb = net.specs, len(plan.blocks)
+        p3, p4, p5 = plan.backbone
         h, c5 = p5.shape[1], p5.shape[3]
-        hw = h * h
         assert plan.blocks[-1][4] is p5
         self.blocks_start = len(self.bwd)   # bwd.calls[blocks_start:] are these launches
         parts = []
@@ -294,55 +325,107 @@ class HeadTrain:
             x, y, pk = plan.first_convs[key]
             assert x is p5, key
             parts.append(torch.empty_like(p5))
-            self._pw_bwd_data(plan, pk, self.gmap[y.data_ptr()], parts[-1], hw, c5, self.c)
+            self._pw_bwd_data(plan, pk, self.gmap[y.data_ptr()], parts[-1], h * h, c5, self.c)
         dy = self.gp5 = parts[0]   # the gradient of P5
         for t in parts[1:]:
             self.bwd.add("stl_det_grad_add", dy, t, None, None, dy, dy.numel())
         self.bwd.keep_alive(*parts)
         first = nb - self.nblocks
-        mids = [specs[i]["mid"] for i in range(first, nb)]
-        ses = [specs[i]["se"] for i in range(first, nb)]
-        # scratch shared by the blocks, sized for the widest: D / du, xs / u / z_e, dz_e; and the small ones
-        s1, s2, s3 = (torch.empty(B * hw * max(mids), device=dev) for _ in range(3))
-        gate_ws = torch.empty(max(lib.stl_det_mbconv_gate_bwd_workspace(B, hw, mid) for mid in mids), device=dev)
-        act_ws = torch.empty(max(lib.stl_det_mbconv_act_bwd_workspace(B, hw, mid) for mid in mids), device=dev)
+        heads_form = nb - m.final_stage_blocks()   # from this block on: 3 x 3 / 1, the heads' depthwise backward entry points
+        todo = range(first, nb)
+        mids = [specs[i]["mid"] for i in todo]
+        ses = [specs[i]["se"] for i in todo]
+        hin = [plan.blocks[i][0].shape[1] for i in todo]
+        hout = [plan.blocks[i][2].shape[1] for i in todo]
+        # scratch shared by the blocks, sized for the largest h^2 mid among them: D / du (output resolution); xs / u (output) and z_e
+        # (input resolution); dz_e (input resolution); and the small ones
+        n1 = max(ho * ho * mid for ho, mid in zip(hout, mids))
+        n2 = max(max(ho * ho, hi * hi if specs[i]["e"] != 1 else 0) * mid for i, hi, ho, mid in zip(todo, hin, hout, mids))
+        n3 = max([hi * hi * mid for i, hi, mid in zip(todo, hin, mids) if specs[i]["e"] != 1] + [1])
+        s1, s2, s3 = (torch.empty(B * n, device=dev) for n in (n1, n2, n3))
+        gate_ws = torch.empty(max(lib.stl_det_mbconv_gate_bwd_workspace(B, ho * ho, mid) for ho, mid in zip(hout, mids)), device=dev)
+        act_ws = torch.empty(max(lib.stl_det_mbconv_act_bwd_workspace(B, ho * ho, mid) for ho, mid in zip(hout, mids)), device=dev)
         se_ws = torch.empty(max(lib.stl_det_se_bwd_workspace(B, mid, cs) for mid, cs in zip(mids, ses)), device=dev)
         asum, dgate, dpool = (torch.empty(B * max(mids), device=dev) for _ in range(3))
-        dwb_part = torch.empty(lib.stl_det_dwconv_bwd_parts(B * hw) * 9 * max(mids), device=dev)
-        self.bwd.keep_alive(s1, s2, s3, gate_ws, act_ws, se_ws, asum, dgate, dpool, dwb_part)
+        dwb_part = torch.empty(lib.stl_det_dwconv_bwd_parts(B * h * h) * 9 * max(mids[max(heads_form - first, 0):]), device=dev)
+        ks_part = torch.empty(max([lib.stl_det_dwconv_bwd_ks_parts(B * ho * ho) * specs[i]["k"] ** 2 * mid
+                                   for i, ho, mid in zip(todo, hout, mids) if i < heads_form] + [1]), device=dev)
+        self.bwd.keep_alive(s1, s2, s3, gate_ws, act_ws, se_ws, asum, dgate, dpool, dwb_part, ks_part)
+        self.block_dy = {}   # block -> the gradient of its output, after every join
+        self.stem_dy = None  # the gradient of the stem's output (train_stem)
         for i in range(nb - 1, first - 1, -1):
             b, lay = specs[i], L["blocks"][i]
             inp, e, a, gate, y = plan.blocks[i]
-            ci, mid, co, cs = b["ci"], b["mid"], b["co"], b["se"]
-            assert b["k"] == 3 and b["s"] == 1 and e is not None and a.shape[1] == h and dy.shape == y.shape, i
-            g = self.bgrads[i] = dict(exp_w=torch.empty(ci, mid, device=dev), exp_b=torch.empty(mid, device=dev),
-                                      dw=torch.empty(3, 3, mid, device=dev), dw_b=torch.empty(mid, device=dev),
-                                      se_w1=torch.empty(cs, mid, device=dev), se_b1=torch.empty(cs, device=dev),
-                                      se_w2=torch.empty(mid, cs, device=dev), se_b2=torch.empty(mid, device=dev),
-                                      proj_w=torch.empty(mid, co, device=dev), proj_b=torch.empty(co, device=dev))
+            ci, mid, co, cs, k, s = b["ci"], b["mid"], b["co"], b["se"], b["k"], b["s"]
+            hi, ho = inp.shape[1], a.shape[1]
+            hwi, hwo = hi * hi, ho * ho
+            old = i >= heads_form
+            assert dy.shape == y.shape and (e is None) == (b["e"] == 1) and ho == (hi + s - 1) // s, i
+            assert not old or (k == 3 and s == 1 and e is not None), i
+            self.block_dy[i] = dy
+            g = self.bgrads[i] = dict(exp_w=torch.empty(ci, mid, device=dev), exp_b=torch.empty(mid, device=dev)) if e is not None else {}
+            g.update(dw=torch.empty(k, k, mid, device=dev), dw_b=torch.empty(mid, device=dev),
+                     se_w1=torch.empty(cs, mid, device=dev), se_b1=torch.empty(cs, device=dev),
+                     se_w2=torch.empty(mid, cs, device=dev), se_b2=torch.empty(mid, device=dev),
+                     proj_w=torch.empty(mid, co, device=dev), proj_b=torch.empty(co, device=dev))
             self.bwd.keep_alive(inp, e, a, gate, y, *g.values())
             wd, bd = plan._w(lay["dw"][0]), plan._w(lay["dw"][1])
+            xd = inp if e is None else e   # what the depthwise layer reads
             # the projection: D = dy Wp'^T; xs = a g, asum, dgate; dWp', dbp' with x = xs
-            self._pw_bwd_data(plan, lay["project"], dy, s1, hw, mid, co)
-            self.bwd.add("stl_det_mbconv_gate_bwd", a, s1, gate, s2, gate_ws, asum, dgate, B, hw, mid)
-            self._pw_bwd_weight(lay["project"], s2, dy, g["proj_w"], g["proj_b"], hw, mid, co)
+            self._pw_bwd_data(plan, lay["project"], dy, s1, hwo, mid, co)
+            self.bwd.add("stl_det_mbconv_gate_bwd", a, s1, gate, s2, gate_ws, asum, dgate, B, hwo, mid)
+            self._pw_bwd_weight(lay["project"], s2, dy, g["proj_w"], g["proj_b"], hwo, mid, co)
             # the gate: dpool and the SE gradients
-            self.bwd.add("stl_det_se_bwd", asum, dgate, gate, B, hw, mid, cs, *[plan._w(o) for o in lay["se"]], se_ws, dpool,
+            self.bwd.add("stl_det_se_bwd", asum, dgate, gate, B, hwo, mid, cs, *[plan._w(o) for o in lay["se"]], se_ws, dpool,
                          g["se_w1"], g["se_b1"], g["se_w2"], g["se_b2"])
             # the depthwise layer: u recomputed by the forward's launch without the activation; du overwrites D; db_d'; dw_d'
-            list_dwconv(self.bwd, 0, e, wd, bd, s2, B, h, mid, 3, 1, 0)
-            self.bwd.add("stl_det_mbconv_act_bwd", s1, s2, gate, dpool, s1, act_ws, g["dw_b"], B, hw, mid)
-            self.bwd.add("stl_det_dwconv_bwd_weight", e, s1, dwb_part, g["dw"], B, h, h, mid)
-            # the expand layer: its pre-activation z_e recomputed the same way, dz_e = dwconv^T(du) swish'(z_e); dWe', dbe'
-            list_pointwise(self.bwd, 0, plan.pw_fields(inp, s2, hw, ci, mid, lay["expand"], 0), False)
-            self.bwd.add("stl_det_dwconv_bwd_data", s1, wd, s2, s3, B, h, h, mid)
-            self._pw_bwd_weight(lay["expand"], inp, s3, g["exp_w"], g["exp_b"], hw, ci, mid)
-            if i > first:   # the block in front trains too: the gradient of this block's input, plus dy through the skip
-                dx = torch.empty_like(inp)
-                self._pw_bwd_data(plan, lay["expand"], s3, dx, hw, ci, mid)
+            list_dwconv(self.bwd, 0, xd, wd, bd, s2, B, hi, mid, k, s, 0)
+            self.bwd.add("stl_det_mbconv_act_bwd", s1, s2, gate, dpool, s1, act_ws, g["dw_b"], B, hwo, mid)
+            if old:
+                self.bwd.add("stl_det_dwconv_bwd_weight", xd, s1, dwb_part, g["dw"], B, hi, hi, mid)
+            else:
+                self.bwd.add("stl_det_dwconv_bwd_weight_ks", xd, s1, ks_part, g["dw"], B, hi, hi, mid, k, s)
+            need_dx = i > first or self.stem   # the block (or the stem) in front trains too: the gradient of this block's input
+            dx = torch.empty_like(inp) if need_dx else None
+            if e is not None:
+                # the expand layer: its pre-activation z_e recomputed the same way, dz_e = dwconv^T(du) swish'(z_e); dWe', dbe'
+                list_pointwise(self.bwd, 0, plan.pw_fields(inp, s2, hwi, ci, mid, lay["expand"], 0), False)
+                if old:
+                    self.bwd.add("stl_det_dwconv_bwd_data", s1, wd, s2, s3, B, hi, hi, mid)
+                else:
+                    self.bwd.add("stl_det_dwconv_bwd_data_ks", s1, wd, s2, s3, B, hi, hi, mid, k, s)
+                self._pw_bwd_weight(lay["expand"], inp, s3, g["exp_w"], g["exp_b"], hwi, ci, mid)
+                if need_dx:
+                    self._pw_bwd_data(plan, lay["expand"], s3, dx, hwi, ci, mid)
+            elif need_dx:   # no expand layer: the depthwise layer reads the block input, its data gradient is the input's
+                self.bwd.add("stl_det_dwconv_bwd_data_ks", s1, wd, None, dx, B, hi, hi, mid, k, s)
+            if need_dx:
+                # joined in this order: the block's own data gradient, dy through the skip, then -- where the input is P4 / P3 -- the
+                # data gradients of the first cell's 1x1 layers that read it: p4_down_channel, p4_down_channel_2 / p3_down_channel
                 if b["skip"]:
                     self.bwd.add("stl_det_grad_add", dx, dy, None, None, dx, dx.numel())
+                if inp is p4:
+                    self._join(plan, dx, p4, ("p4_down_channel", "p4_down_channel_2"))
+                elif inp is p3:
+                    self._join(plan, dx, p3, ("p3_down_channel",))
                 dy = dx
+        if self.stem:
+            assert first == 0 and dy.shape == plan.blocks[0][0].shape
+            self.stem_dy = dy
+            S, co = plan.canvas.shape[1], dy.shape[3]
+            ho = dy.shape[1]
+            self.sgrads = dict(w=torch.empty(3, 3, 3, co, device=dev), b=torch.empty(co, device=dev))
+            stem_part = torch.empty(lib.stl_det_stem_bwd_parts(B * ho * ho) * 28 * co, device=dev)
+            # the canvas the forward read: the plan's own, or the batch's (set_canvas before each backward)
+            self.canvas_arg = ctypes.c_void_p(plan.canvas.data_ptr())
+            self.bwd.keep_alive(plan.canvas, dy, stem_part, *self.sgrads.values())
+            self.bwd.add("stl_det_stem_bwd", self.canvas_arg, plan._w(L["stem"][0]), plan._w(L["stem"][1]), dy, stem_part, self.sgrads["w"],
+                         self.sgrads["b"], B, S, S, co)
+
+    def set_canvas(self, canvas) -> None:
+        """The canvas the forward about to be differentiated read (None: the plan's own); the caller keeps it alive until the backward."""
+        if self.stem:
+            self.canvas_arg.value = self.own_canvas if canvas is None else canvas.data_ptr()
 
     def _name(self, name: str) -> str:
         return NAME16[name] if self.h16 else name
@@ -389,13 +472,18 @@ def head_parameters(m) -> List[Tuple[str, torch.nn.Parameter]]:
 
 
 def trainable_parameters(m) -> List[Tuple[str, torch.nn.Parameter]]:
-    """What detection_loss differentiates: the parameters of the last ``m.train_backbone`` MBConv blocks in state_dict order (expand
-    conv and BN, depthwise conv and BN, the two SE convs, project conv and BN), then those of the last ``m.train_bifpn`` BiFPN cells
+    """What detection_loss differentiates: with ``m.train_stem`` the stem's conv weight and its BN's weight and bias, then the parameters
+    of the last ``m.train_backbone`` MBConv blocks in state_dict order (expand conv and BN -- not in a block without an expand layer --,
+    depthwise conv and BN, the two SE convs, project conv and BN), then those of the last ``m.train_bifpn`` BiFPN cells
     in state_dict order (after ``set_train_bifpn("all")`` every cell's, the first cell's 24 conv and BN tensors among them), then
     head_parameters(m)."""
     kb = getattr(m, "train_backbone", 0)
     allb = m.backbone_net.model._blocks if kb else ()
     blocks = [(f"backbone_net.model._blocks.{i}.{name}", p) for i in range(len(allb) - kb, len(allb)) for name, p in allb[i].named_parameters()]
+    if getattr(m, "train_stem", False):   # set_train_trunk("all"): the stem's three tensors first (a block without an expand layer has 10, the others 13)
+        net = m.backbone_net.model
+        blocks = [("backbone_net.model._conv_stem.conv.weight", net._conv_stem.conv.weight), ("backbone_net.model._bn0.weight", net._bn0.weight),
+                  ("backbone_net.model._bn0.bias", net._bn0.bias)] + blocks
     k = getattr(m, "train_bifpn", 0)
     n = len(m.bifpn) if k else 0
     cells = [(f"bifpn.{j}.{name}", p) for j in range(n - k, n) for name, p in m.bifpn[j].named_parameters()]
@@ -440,7 +528,8 @@ def block_raw_grads(m, tr: HeadTrain) -> Dict[str, torch.Tensor]:
     out = {}
     for i, g in tr.bgrads.items():
         blk, pre = m.backbone_net.model._blocks[i], f"backbone_net.model._blocks.{i}."
-        for conv, bn, gw, gb in (("_expand_conv", "_bn0", g["exp_w"], g["exp_b"]), ("_project_conv", "_bn2", g["proj_w"], g["proj_b"])):
+        layers = [("_expand_conv", "_bn0", g["exp_w"], g["exp_b"])] if "exp_w" in g else []   # (a block without an expand layer)
+        for conv, bn, gw, gb in layers + [("_project_conv", "_bn2", g["proj_w"], g["proj_b"])]:
             pw, n = getattr(blk, conv).conv, getattr(blk, bn)
             W = pw.weight.detach().reshape(pw.out_channels, pw.in_channels)
             dW, _, dgam, dbeta = fold_chain(W, None, n.weight.detach(), n.running_mean, n.running_var, n.eps, gw.t(), gb)
@@ -453,6 +542,13 @@ def block_raw_grads(m, tr: HeadTrain) -> Dict[str, torch.Tensor]:
         out[pre + "_bn1.weight"], out[pre + "_bn1.bias"] = dgam, dbeta.clone()
         out[pre + "_se_reduce.conv.weight"], out[pre + "_se_reduce.conv.bias"] = g["se_w1"][:, :, None, None].clone(), g["se_b1"].clone()
         out[pre + "_se_expand.conv.weight"], out[pre + "_se_expand.conv.bias"] = g["se_w2"][:, :, None, None].clone(), g["se_b2"].clone()
+    if tr.stem:   # the stem: [3][3][3][Co] -> [Co, 3, 3, 3], folded through _bn0 as a conv without bias
+        net, pre, g = m.backbone_net.model, "backbone_net.model.", tr.sgrads
+        W, n = net._conv_stem.conv.weight.detach(), net._bn0
+        dW, _, dgam, dbeta = fold_chain(W.reshape(W.shape[0], -1), None, n.weight.detach(), n.running_mean, n.running_var, n.eps,
+                                        g["w"].permute(3, 2, 0, 1).reshape(W.shape[0], -1), g["b"])
+        out[pre + "_conv_stem.conv.weight"] = dW.reshape(W.shape)
+        out[pre + "_bn0.weight"], out[pre + "_bn0.bias"] = dgam, dbeta.clone()
     return out
 
 
@@ -537,9 +633,10 @@ def detection_loss(m, inputs, targets, alpha: float = 0.25, gamma: float = 2.0, 
             p, _, keep = m._preprocess(srcs, 1, dev)
         canvas, gt_dev, offsets_dev = None, torch.from_numpy(gt).to(dev), torch.from_numpy(offsets).to(dev)
     with torch.no_grad():
-        if p.train is None or p.train.ncells != m.train_bifpn or p.train.nblocks != m.train_backbone:
+        if p.train is None or p.train.ncells != m.train_bifpn or p.train.nblocks != m.train_backbone or p.train.stem != m.train_stem:
             p.train = HeadTrain(m, p)
         tr = p.train
+        tr.set_canvas(canvas)
         p.run(st, upto=p.head_start, canvas=canvas)
         tr.forward(st)
         p._inflight = keep

@@ -12,7 +12,8 @@
   * ``setup_optimizer`` (``lib/model_setup.py:109-159``) over ``detector_train.trainable_parameters(model)`` -- the parameters
     ``detection_loss`` trains: the heads, and with ``exp_data["training"]["train_bifpn"] = k`` (default 0, applied to the model by
     ``set_train_bifpn``) the last k BiFPN cells, with ``"all"`` every cell, and with ``"all"`` and ``exp_data["training"]["train_backbone"] = k`` (default 0,
-    ``set_train_backbone``) the last k MBConv blocks of the backbone's final stage; everything before them is frozen: Adam, or SGD with momentum, nesterov and weight
+    ``set_train_backbone``) the last k MBConv blocks of the backbone's final stage, or instead with ``exp_data["training"]["train_trunk"] = k``
+    (``set_train_trunk``; giving both keys is a ValueError) the last k blocks of the whole backbone, with ``"all"`` every block and the stem; everything before them is frozen: Adam, or SGD with momentum, nesterov and weight
     decay 0.0005;
     ``ReduceLROnPlateau(mode="max", min_lr=1e-8)``, ``StepLR`` or no scheduler;
   * ``detector_logs.json`` as ``create_ / load_ / update_detector_logs`` write it (``lib/utils.py:244-301``);
@@ -112,12 +113,21 @@ class DetectorTrainer:
         k = tr.get("train_bifpn", 0)
         k = k if k == "all" else int(k)
         want = len(self.model.bifpn) if k == "all" else k
+        if "train_trunk" in tr and "train_backbone" in tr:
+            raise ValueError("DetectorTrainer: exp_data[\"training\"] has both train_backbone and train_trunk; give one (train_trunk reaches "
+                             "every block, and with \"all\" the stem)")
         kb = int(tr.get("train_backbone", 0))   # the trailing MBConv blocks that train too: needs train_bifpn "all"
-        if kb == 0 and getattr(self.model, "train_backbone", 0):
+        kt = tr.get("train_trunk")              # the same without the final stage's limit (set_train_trunk), an int or "all"
+        kt = None if kt is None else kt if kt == "all" else int(kt)
+        none = kt == 0 if kt is not None else kb == 0
+        if none and (getattr(self.model, "train_backbone", 0) or getattr(self.model, "train_stem", False)):
             self.model.set_train_backbone(0)
         if want != getattr(self.model, "train_bifpn", 0):   # (a model without that stage takes 0 only)
             self.model.set_train_bifpn(k)
-        if kb != getattr(self.model, "train_backbone", 0):
+        if kt is not None:
+            if not none:
+                self.model.set_train_trunk(kt)
+        elif kb != getattr(self.model, "train_backbone", 0) or getattr(self.model, "train_stem", False):
             self.model.set_train_backbone(kb)
         self.optimizer, self.scheduler = setup_optimizer(exp_data, [p for _, p in trainable_parameters(model)])
         self.evaluator = DetectorEvaluator(model, device=self.device, output=output)

@@ -27,7 +27,9 @@ them and the backbone stay frozen.  ``set_train_bifpn("all")`` trains every cell
 ``p5_to_p6`` and the two plain pooled maps included: everything behind the backbone, which stays frozen unless
 ``set_train_backbone(k)`` (after "all"; fp32) also trains the last k MBConv blocks, 0 <= k <= the blocks of the final stage (1 for D0, 2
 for D3: the ones that produce P5; csrc/detector_mbconv.hip).  The blocks are packed in front of the cells, so an optimiser step still
-rewrites one tail of the weight buffer.
+rewrites one tail of the weight buffer.  ``set_train_trunk(k)`` has no such limit: the last k blocks of the whole backbone, 0 <= k <= 16 /
+26, and with ``"all"`` the stem too (``train_stem``; csrc/detector_trunk.hip: the depthwise backward at k 3 / 5, s 1 / 2 and the stem's
+weight gradient), which is every parameter of the detector; the stem is packed first, so its step rewrites the whole buffer in place.
 """
 from __future__ import annotations
 
@@ -616,7 +618,8 @@ class EfficientDetBackbone(nn.Module):
         self._wbufT16, self._layoutT = None, None   # the heads' bf16 transposed packs (_ensure_transposed: models that train only)
         self._batch_tables: dict = {}               # _batch_records: the constant record table of a DetBatch geometry
         self.train_bifpn = 0                        # set_train_bifpn: how many trailing BiFPN cells detection_loss trains with the heads ("all": every cell)
-        self.train_backbone = 0                     # set_train_backbone: how many trailing MBConv blocks train with them (the final stage's)
+        self.train_backbone = 0                     # set_train_backbone / set_train_trunk: how many trailing MBConv blocks train with them
+        self.train_stem = False                     # set_train_trunk("all"): the stem (_conv_stem, _bn0) trains too, with every block
         self.eval()
 
     # ---------------------------------------------------------------- state
@@ -635,7 +638,7 @@ class EfficientDetBackbone(nn.Module):
             raise ValueError(f"EfficientDet.set_train_bifpn: k = {k!r}, expected 0 .. {n - 1}: the first of the {n} BiFPN cells does not "
                              "train by count -- it alone has the down-channel convs, p5_to_p6 and the unweighted pooled maps; "
                              "set_train_bifpn(\"all\") trains it with every cell behind it")
-        if self.train_backbone and k != n:
+        if (self.train_backbone or self.train_stem) and k != n:
             raise ValueError(f"EfficientDet.set_train_bifpn: {self.train_backbone} backbone block(s) train, which needs every BiFPN cell to "
                              "train (the gradient of P5 exists only when the first cell trains): call set_train_backbone(0) first")
         if k != self.train_bifpn:
@@ -664,13 +667,32 @@ class EfficientDetBackbone(nn.Module):
             raise ValueError(f"EfficientDet.set_train_backbone: k = {k!r}, expected 0 .. {n}")
         if k > n:
             raise ValueError(f"EfficientDet.set_train_backbone: k = {k!r}, expected 0 .. {n}: only the {n} block(s) of the backbone's final "
-                             "stage train -- the blocks in front have 5x5 / stride-2 depthwise layers whose backward does not exist yet")
+                             "stage train -- the blocks in front have 5x5 / stride-2 depthwise layers whose backward does not exist yet "
+                             "in this setter's contract; set_train_trunk(k) reaches them (any block, \"all\": the stem too)")
+        return self._set_trunk("set_train_backbone", k, False)
+
+    def set_train_trunk(self, k) -> "EfficientDetBackbone":
+        """``set_train_backbone`` without the final stage's limit: the last k MBConv blocks of the whole backbone train, k = 0 .. the
+        number of blocks (16 for D0, 26 for D3) -- the 5 x 5 and stride-2 depthwise layers and the blocks without an expand layer among
+        them (csrc/detector_trunk.hip); ``"all"``: every block and the stem (``_conv_stem``, ``_bn0``; ``train_stem``).  The count goes to
+        ``train_backbone``; up to ``final_stage_blocks()`` the two setters do the same.  The same preconditions and contract: needs
+        ``set_train_bifpn("all")``, fp32 only, every BN on its running statistics, no drop-connect, the forward launch list unchanged."""
+        n = len(self.backbone_net.model._blocks)
+        stem = isinstance(k, str) and k == "all"
+        if stem:
+            k = n
+        elif not isinstance(k, int) or isinstance(k, bool) or k < 0 or k > n:
+            raise ValueError(f"EfficientDet.set_train_trunk: k = {k!r}, expected 0 .. {n} (the last k MBConv blocks) or \"all\" (every block "
+                             "and the stem)")
+        return self._set_trunk("set_train_trunk", k, stem)
+
+    def _set_trunk(self, who: str, k: int, stem: bool) -> "EfficientDetBackbone":
         if k and self.train_bifpn != len(self.bifpn):
-            raise ValueError("EfficientDet.set_train_backbone: the gradient of P5 exists only when the first BiFPN cell trains: call "
+            raise ValueError(f"EfficientDet.{who}: the gradient of P5 exists only when the first BiFPN cell trains: call "
                              "set_train_bifpn(\"all\") first")
-        if k != self.train_backbone:
+        if k != self.train_backbone or stem != self.train_stem:
             current = self._version is not None and self._state_version() == self._version
-            self.train_backbone = k
+            self.train_backbone, self.train_stem = k, stem
             self._version = self._state_version() if current else None   # the same weights, split anew; else a full refold
             for p in self._plans.values():
                 p.train = None   # its backward launches are listed for one k
@@ -681,12 +703,19 @@ class EfficientDetBackbone(nn.Module):
         MBConv blocks (the last train_backbone), of the trainable BiFPN cells (the last train_bifpn) and of regressor.* / classifier.*"""
         owned = lambda mods: [t for h in mods for t in list(h.parameters()) + list(h.buffers())]   # noqa: E731
         allb = list(self.backbone_net.model._blocks)
-        blocks = owned(allb[len(allb) - self.train_backbone:])
+        net = self.backbone_net.model
+        blocks = owned(([net._conv_stem, net._bn0] if self.train_stem else []) + allb[len(allb) - self.train_backbone:])   # the stem with them
         cells = owned(list(self.bifpn)[len(self.bifpn) - self.train_bifpn:])
         heads = owned((self.regressor, self.classifier))
         ids = {id(t) for t in blocks + cells + heads}
         trunk = [t for t in list(self.parameters()) + list(self.buffers()) if id(t) not in ids]
         return tuple(tuple((t.data_ptr(), t._version) for t in ts) for ts in (trunk, blocks, cells, heads))
+
+    def _pack_stem(self, P: _Packer):
+        """-> (w offset [3][3][3][Co], bias offset) of the stem with its BN folded"""
+        net = self.backbone_net.model
+        s, t = _fold(net._bn0)
+        return (P.add((net._conv_stem.conv.weight.detach().double() * s[:, None, None, None]).permute(2, 3, 1, 0).contiguous()), P.add(t))
 
     @staticmethod
     def _pack_block(P: _Packer, blk, b) -> dict:
@@ -727,10 +756,12 @@ class EfficientDetBackbone(nn.Module):
         MBConv blocks from that one on changed too (first = 0 then); they are packed in front of the cells: a longer tail."""
         P = _Packer(COMPUTE_DTYPES[self.compute_dtype][0])
         net = self.backbone_net.model
-        n0, n16 = P.n, P.n16 = self._tail_off[first] if block is None else self._block_off[block]
+        n0, n16 = P.n, P.n16 = self._tail_off[first] if block is None else (0, 0) if block < 0 else self._block_off[block]
         if block is not None:
             assert first == 0, "EfficientDet: trainable blocks without every cell"
-            for i in range(block, len(net._blocks)):
+            if block < 0:   # the stem trains: it is packed first, so the tail is the whole buffer
+                assert self._pack_stem(P) == self._layout["stem"] and (P.n, P.n16) == self._block_off[0], "EfficientDet: stem layout changed"
+            for i in range(max(block, 0), len(net._blocks)):
                 assert self._pack_block(P, net._blocks[i], net.specs[i]) == self._layout["blocks"][i], "EfficientDet: block layout changed"
             assert (P.n, P.n16) == self._tail_off[0], "EfficientDet: block layout changed"
         for j in range(first, len(self.bifpn)):
@@ -766,16 +797,14 @@ class EfficientDetBackbone(nn.Module):
         v = self._state_version()
         if self._version is not None and v[0] == self._version[0] and self._wbuf is not None and self._wbuf.device == dev:
             if v[1] != self._version[1]:   # the trainable blocks moved: with them every cell trains
-                self._refold_tail(0, len(self.backbone_net.model._blocks) - self.train_backbone)
+                self._refold_tail(0, -1 if self.train_stem else len(self.backbone_net.model._blocks) - self.train_backbone)
             elif v[2:] != self._version[2:]:
                 self._refold_tail(len(self.bifpn) - (self.train_bifpn if v[2] != self._version[2] else 0))
             self._version = v
             return
         P = _Packer(COMPUTE_DTYPES[self.compute_dtype][0])
         net = self.backbone_net.model
-        s, t = _fold(net._bn0)
-        stem = (P.add((net._conv_stem.conv.weight.detach().double() * s[:, None, None, None]).permute(2, 3, 1, 0).contiguous()),
-                P.add(t))
+        stem = self._pack_stem(P)
         blocks, self._block_off = [], []   # _block_off[i]: where block i starts in the two buffers (the blocks in order, in front of the cells)
         for blk, b in zip(net._blocks, net.specs):
             self._block_off.append((P.n, P.n16))
