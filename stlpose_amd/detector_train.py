@@ -1,4 +1,4 @@
-"""Fine-tuning the EfficientDet heads on the MI355X: ``EfficientDetBackbone.detection_loss`` (the counterpart of
+"""Fine-tuning the EfficientDet detector on the MI355X: ``EfficientDetBackbone.detection_loss`` (the counterpart of
 ``loss_dict = self.model(imgs / 255, targets)`` + ``loss.backward()`` in reference ``src/02_train_faster_rcnn.py:189-239``).
 
 The reference has no detection loss for its own EfficientDet; the loss is the published RetinaNet / EfficientDet one (focal
@@ -7,57 +7,19 @@ tests/detector_train_ref.py.  This is the first stage of fine-tuning: the backbo
 inference plan's launches, every BN stays on its running statistics (the reference model's ``freeze_bn()``), and the
 ``regressor.*`` / ``classifier.*`` parameters get gradients.
 
-``HeadTrain`` belongs to one inference plan (one batch size).  Its forward runs the heads with the inference kernels -- ``reg`` and
-``cls`` equal the inference plan's bit for bit -- and keeps what the backward needs: every depthwise output, and the pre-activation
-``z`` of every swish, written by the pointwise launch that applies it (stl_det_pointwise_train).  Its backward walks each (head,
-level) from the header down through csrc/detector_train.hip and produces gradients of the *folded* weights W' = W s, b' = b s + t
-(s, t the frozen BN's scale and shift) per level; ``fold_chain`` carries them to W, b, gamma and beta in a few elementwise torch
-ops, and the weights shared by the five levels sum their five contributions.  The first depthwise layer of a (head, level) reads
-a frozen feature map: no data gradient is computed for it.
+``HeadTrain`` belongs to one inference plan (one batch size) and lists the training launches once: the heads' forward, then the
+backward of every stage that trains, in the reverse of the forward order, one builder per stage, each described where it stands:
 
-``model.set_train_bifpn(k)`` (1 <= k <= cells - 1, or "all": below) trains the last k BiFPN cells with the heads, fp32 only.  The forward is not
-touched: the inference plan keeps every map (``_Plan.cells``), and the backward recomputes each node's pre-activation from them.
-Then the first depthwise layer of every (head, level) also computes its data gradient (stl_det_dwconv_bwd_data without z), the two
-heads' gradients of a level are added regressor first, each times the gradient of its own loss (stl_det_grad_add reads the two
-scalars on the device), and the cells run in reverse, the nodes of a cell in the reverse of the forward order.  Every consumer of a
-map comes later in the forward order, so a map's gradient is complete when its node is reached; the first contribution writes, the
-later ones accumulate, in that fixed order.  Per node: the pointwise layer's weight and data gradient (x = d), the depthwise
-layer's weight gradient (x = f) and data gradient, then stl_det_fuse_bwd (csrc/detector_bifpn.hip), whose destinations are null for
-the frozen inputs of the first trainable cell.  ``cell_raw_grads`` carries the folded gradients to the raw parameters: ``fold_chain``
-for the pointwise layer and its BN, ``fusion_weight_grads`` for ``p*_w1`` / ``p*_w2``.
+    ``_head``         the heads (always)                                               csrc/detector_train.hip
+    ``_node``         the last ``train_bifpn`` BiFPN cells (``set_train_bifpn(k)``)          csrc/detector_bifpn.hip
+    ``_first_cell``   behind the first cell's nodes (``set_train_bifpn("all")``)
+    ``_p5_join``      the gradient of P5 (``set_train_backbone(k)`` / ``set_train_trunk(k)``)
+    ``_block``        the last ``train_backbone`` MBConv blocks, the last one first      csrc/detector_mbconv.hip, detector_trunk.hip
+    ``_stem``         the stem (``set_train_trunk("all")``)
 
-``model.set_train_bifpn("all")`` trains the first cell too, so everything behind the frozen backbone.  Its eight nodes run through the
-same loop; their inputs are the seven maps the cell makes from P3 / P4 / P5 (``p3_in``, ``p4_in``, ``p5_in``, the second ``p4_in`` /
-``p5_in`` of the down path, ``p6``, ``p7``), which get gradient maps like any node output.  Behind the nodes: stl_det_pool_bwd
-(csrc/detector_bifpn.hip) of ``p6 -> p7``, adding to the gradient of ``p6``, then of ``t -> p6`` (``t`` the output of ``p5_to_p6``'s
-conv and BN), then the weight gradients of the six 1x1 layers (stl_det_pointwise_bwd_weight with x = the backbone map: ``p5_to_p6``,
-the three ``*_down_channel``, the two ``*_down_channel_2``; ``_Plan.first_pools`` / ``first_convs``).  No data gradient is computed for
-P3 / P4 / P5: nothing before them trains.  ``fold_chain`` carries each folded pair to the conv's weight and bias and the BN's.
-
-``model.set_train_backbone(k)`` (needs "all"; fp32) trains the last k MBConv blocks of the backbone's final stage too (block 15 of D0,
-blocks 24 / 25 of D3: 3x3 stride-1 depthwise layers).  The forward is the inference forward (no drop-connect, BN on running
-statistics); ``_Plan.blocks`` keeps each block's input, expand output e, depthwise output a, gate g and output.  Behind the cells'
-launches (``_blocks_bwd``): stl_det_pointwise_bwd_data of ``p5_to_p6``, ``p5_down_channel`` and ``p5_down_channel_2`` into a buffer
-each, joined in that order by stl_det_grad_add -- the gradient of P5; then per block, the last first, with the folded weights: D = dy
-Wp'^T (stl_det_pointwise_bwd_data); stl_det_mbconv_gate_bwd (csrc/detector_mbconv.hip: xs = a g, sum a, sum D a); the projection's
-weight gradient with x = xs; stl_det_se_bwd (dpool and the four SE gradients); the depthwise pre-activation u recomputed by
-stl_det_dwconv at act 0; stl_det_mbconv_act_bwd (du = (D g + dpool / HW) swish'(u) over D, and the folded BN's bias gradient);
-stl_det_dwconv_bwd_weight (x = e); the expand layer's pre-activation recomputed by stl_det_pointwise at act 0;
-stl_det_dwconv_bwd_data (times swish' of it); the expand layer's weight gradient (x = the block input); and, where the block in front
-trains too, its data gradient plus dy through the skip.  ``block_raw_grads`` carries the folded gradients to the raw parameters
-(``fold_chain`` without a conv bias, ``dw_fold_chain``).  P3 / P4 and every block in front stay frozen.
-
-``model.set_train_trunk(k)`` reaches further back: the last k blocks of the whole backbone, ``"all"`` the stem too.  The final stage's
-blocks keep the launches above; a block in front of it runs the same sequence with stl_det_dwconv_bwd_weight_ks / _data_ks
-(csrc/detector_trunk.hip: k 3 / 5, s 1 / 2 under TF "same" padding), the projection, gate, SE and act steps at the block's output
-resolution, the expand recompute, the depthwise data gradient and the expand gradients at its input resolution.  A block without an
-expand layer (e = 1) has no ``exp_w`` / ``exp_b``: its depthwise layer reads the block input, and stl_det_dwconv_bwd_data_ks without z
-is the input's gradient.  The gradient of a block's input is joined in a fixed order: the block's own data gradient, dy through the
-skip, then -- where the input is P4 / P3, the inputs of the last two stride-2 blocks -- stl_det_pointwise_bwd_data of
-``p4_down_channel`` and ``p4_down_channel_2`` / of ``p3_down_channel``, each into a buffer of its own and added by stl_det_grad_add.
-``tr.block_dy[i]`` keeps the joined gradient of block i's output, ``tr.stem_dy`` that of the stem's.  With the stem, block 0 also
-produces its input's gradient and stl_det_stem_bwd follows (the pre-activation recomputed from the canvas the forward read; no image
-gradient); its ``[3][3][3][Co]`` gradient is permuted to ``[Co, 3, 3, 3]`` and folded through ``_bn0`` as a conv without bias.
+``_workspaces`` sizes every shared buffer before anything is listed.  The forward is never touched: the inference plan keeps every map a
+backward reads (``_Plan.cells`` / ``first_convs`` / ``first_pools`` / ``blocks``) and every pre-activation is recomputed.  The launches produce
+gradients of the *folded* weights; ``raw_grads``, ``cell_raw_grads`` and ``block_raw_grads`` carry them to the raw parameters.
 
 A model with ``compute_dtype="f16"`` trains in 16 bit, by the recipe of the pose network's mixed mode: the trunk runs as the 16-bit
 inference plan's launches, the heads' forward tensors (every depthwise output d, pre-activation z and swish output t) are f16, the
@@ -69,6 +31,7 @@ not train: its forward error is several times that of f16.
 from __future__ import annotations
 
 import ctypes
+from types import SimpleNamespace
 from typing import Dict, List, Sequence, Tuple
 
 import numpy as np
@@ -83,6 +46,9 @@ HEADS = ("regressor", "classifier")
 NAME16 = {"stl_det_pointwise_bwd_slabs": "stl_det_pointwise16_bwd_slabs", "stl_det_dwconv_bwd_parts": "stl_det_dwconv16_bwd_parts",
           "stl_det_pointwise_bwd_weight": "stl_det_pointwise16_bwd_weight", "stl_det_pointwise_bwd_data": "stl_det_pointwise16_bwd_data",
           "stl_det_dwconv_bwd_weight": "stl_det_dwconv16_bwd_weight", "stl_det_dwconv_bwd_data": "stl_det_dwconv16_bwd_data"}
+# the first cell's 1x1 layers in the order their weight gradients are listed, and the readers of P5 / P4 / P3 in the order their data gradients join
+FIRST_CONVS = ("p5_to_p6", "p3_down_channel", "p4_down_channel", "p5_down_channel", "p4_down_channel_2", "p5_down_channel_2")
+P5_READERS, P4_READERS, P3_READERS = ("p5_to_p6", "p5_down_channel", "p5_down_channel_2"), ("p4_down_channel", "p4_down_channel_2"), ("p3_down_channel",)
 
 
 # ------------------------------------------------------------------------------------------------ targets
@@ -142,307 +108,133 @@ def dw_fold_chain(w, gamma, mean, var, eps, Gw, Gb):
     return Gw * s[:, None, None], ds * r, Gb
 
 
+def pw_raw_grads(conv, bn, gw, gb):
+    """The folded gradients gw [ci, co], gb [co] of the 1x1 ``conv`` under the frozen ``bn`` carried to the raw parameters by
+    ``fold_chain``: (conv.weight's [co, ci, 1, 1], conv.bias's or None for a conv without bias, bn.weight's, bn.bias's)."""
+    W = conv.weight.detach().reshape(conv.out_channels, conv.in_channels)
+    b = None if conv.bias is None else conv.bias.detach()
+    dW, db, dgam, dbeta = fold_chain(W, b, bn.weight.detach(), bn.running_mean, bn.running_var, bn.eps, gw.t(), gb)
+    return dW[:, :, None, None], db, dgam, dbeta.clone()
+
+
 # ------------------------------------------------------------------------------------------------ launches
 class HeadTrain:
-    """Training forward and backward of the two heads on the features of one inference plan (efficientdet._Plan)."""
+    """The training launches on one inference plan (efficientdet._Plan): the heads' forward (``fwd``) and the backward of every stage
+    that trains (``bwd``), the stages in the reverse of the forward order (module docstring)."""
 
     def __init__(self, m, plan):
-        self.B, self.dev = B, dev = plan.B, plan.dev
+        self.B, self.dev, self.c, self.nlayers = plan.B, plan.dev, m.fpn_channels, len(m.regressor.conv_list)
         self.generation = 0   # forwards through these buffers (the stale-backward check of _DetLossFn)
         self.fwd = LaunchList()
         self.bwd = LaunchList(self.fwd.keep)
         self.hdr = {h: [] for h in HEADS}   # the headers' backward descriptors, the very objects `bwd` passes by reference: set_grads sets their dy
-        L = m._layout
-        c, A, nc = m.fpn_channels, m.num_anchors_total, m.num_classes
-        self.c, self.nlayers = c, len(m.regressor.conv_list)
-        self.reg = torch.empty(B, A, 4, device=dev)
-        self.cls = torch.empty(B, A, nc, device=dev)
-        lib = capi.lib()
-        h0 = plan.feats[0][1]
-        m0 = B * h0 * h0
         self.h16, self.code, self.adtype = plan.h16, plan.code, plan.adtype   # 16-bit: d / z / t in adtype, ga / gb bf16
         if self.h16:
             m._ensure_transposed()
             self.wbufT, self.layoutT = m._wbufT16, m._layoutT
-        gdtype = torch.bfloat16 if self.h16 else torch.float32
-        self.ga, self.gb = torch.empty(m0 * c, device=dev, dtype=gdtype), torch.empty(m0 * c, device=dev, dtype=gdtype)   # gradients in flight, reused
+        self.ncells = m.train_bifpn                    # the trailing BiFPN cells that train with the heads
+        self.first = self.ncells == len(plan.cells)    # every cell: the first one's 1x1 layers (Ci = the backbone's channels) and plain pools too
+        self.nblocks = m.train_backbone                # the trailing MBConv blocks that train with them
+        self.stem = bool(m.train_stem)                 # and the stem (with every block)
+        self.specs, nb = m.backbone_net.model.specs, len(plan.blocks)
+        self.heads_form = nb - m.final_stage_blocks()  # from this block on: 3 x 3 / 1, the heads' depthwise backward entry points
+        self.own_canvas = plan.canvas.data_ptr()
+        assert not self.ncells or not self.h16, "the BiFPN cells train in fp32 only"
+        assert not self.nblocks or self.first, "the backbone's blocks train with every BiFPN cell only"
+        assert not self.stem or self.nblocks == nb, "the stem trains with every block only"
+        L, A, nc, dev = m._layout, m.num_anchors_total, m.num_classes, self.dev
+        self.reg, self.cls = torch.empty(self.B, A, 4, device=dev), torch.empty(self.B, A, nc, device=dev)
+        self._workspaces(plan, nc)
+        self.grads, self.cgrads, self.fgrads, self.bgrads = {}, {}, {}, {}   # the folded gradients of the heads, the nodes, the first cell's 1x1 layers, the blocks
+        for name, out, k, act in (("regressor", self.reg, 4, 0), ("classifier", self.cls, nc, 2)):
+            n, c, aoff = self.nlayers, self.c, 0
+            self.grads[name] = dict(pw_w=torch.empty(5, n, c, c, device=dev), pw_b=torch.empty(5, n, c, device=dev),
+                                    dw=torch.empty(5, n, 3, 3, c, device=dev), hpw_w=torch.empty(5, c, 9 * k, device=dev),
+                                    hpw_b=torch.empty(5, 9 * k, device=dev), hdw=torch.empty(5, 3, 3, c, device=dev))
+            for lv, (f, hh) in enumerate(plan.feats):
+                self._head(plan, L[name], name, lv, f, hh, out, k, act, dict(img_stride=A * k, row_stride=9 * k, off=aoff * k))
+                aoff += hh * hh * 9
+        if self.ncells:
+            self._levels_join(plan)
+            for j in range(len(plan.cells) - 1, len(plan.cells) - self.ncells - 1, -1):
+                for node in reversed(_BiFPN.NODES):   # the forward runs them in this tuple's order
+                    self._node(plan, L["bifpn"][j][node], j, node)
+        if self.first:
+            self._first_cell(plan)
+        if self.nblocks:
+            self.blocks_start = len(self.bwd)   # bwd.calls[blocks_start:] are these launches
+            self.block_dy, self.stem_dy = {}, None   # block -> the gradient of its output, after every join; that of the stem's output (train_stem)
+            dy = self.gp5 = self._p5_join(plan)
+            for i in range(nb - 1, nb - self.nblocks - 1, -1):
+                dy = self._block(plan, L["blocks"][i], i, dy, i > nb - self.nblocks or self.stem)
+            if self.stem:
+                self._stem(plan, L["stem"], dy)
+
+    def _workspaces(self, plan, nc) -> None:
+        """Every buffer that launches share, sized from the plan's shapes before anything is listed: the gradients in flight ``ga`` /
+        ``gb`` (the largest level), the slab workspaces of the weight gradients (``pw_part``: the largest slabs * (Ci * Co + Co) that is
+        listed), the cells' gradient maps (``gmap``) and the scratch the blocks share (``ws``)."""
+        B, c, dev, lib = self.B, self.c, self.dev, capi.lib()
+        m0 = B * plan.feats[0][1] ** 2
+        self.ga, self.gb = (torch.empty(m0 * c, device=dev, dtype=torch.bfloat16 if self.h16 else torch.float32) for _ in range(2))   # reused
         kmax = max(c, 9 * max(4, nc))
         slabs = getattr(lib, self._name("stl_det_pointwise_bwd_slabs"))
-        self.ncells = ncells = m.train_bifpn   # the trailing BiFPN cells that train with the heads
-        self.first = ncells == len(plan.cells)   # every cell: the first one's 1x1 layers (Ci = the backbone's channels) and plain pools too
-        self.nblocks = nblocks = getattr(m, "train_backbone", 0)   # the trailing MBConv blocks that train with them
-        self.stem = bool(getattr(m, "train_stem", False))          # and the stem (with every block)
-        self.own_canvas = plan.canvas.data_ptr()
-        assert not nblocks or self.first, "the backbone's blocks train with every BiFPN cell only"
-        assert not self.stem or nblocks == len(plan.blocks), "the stem trains with every block only"
-        npart = slabs(m0) * (c * kmax + kmax)
-        if self.first:   # the largest slabs * (Ci * Co + Co) that is listed
-            npart = max([npart] + [slabs(x.numel() // x.shape[3]) * (x.shape[3] * c + c) for x, _, _ in plan.first_convs.values()])
-        for inp, e, a, _, y in plan.blocks[len(plan.blocks) - nblocks:]:   # the blocks' expand (input resolution) and project layers
-            ci, mid, co = inp.shape[3], a.shape[3], y.shape[3]
-            npart = max(npart, slabs(a.numel() // mid) * (mid * co + co))
-            if e is not None:
-                npart = max(npart, slabs(e.numel() // mid) * (ci * mid + mid))
-        self.pw_part = torch.empty(npart, device=dev)
+        recs = plan.blocks[len(plan.blocks) - self.nblocks:]
+        npart = [slabs(m0) * (c * kmax + kmax)]
+        if self.first:
+            npart += [slabs(r.x.numel() // r.x.shape[3]) * (r.x.shape[3] * c + c) for r in plan.first_convs.values()]
+        for r in recs:   # the blocks' project and expand (input resolution) layers
+            ci, mid, co = r.inp.shape[3], r.a.shape[3], r.y.shape[3]
+            npart += [slabs(r.a.numel() // mid) * (mid * co + co), slabs(r.e.numel() // mid) * (ci * mid + mid) if r.e is not None else 0]
+        self.pw_part = torch.empty(max(npart), device=dev)
         self.dw_part = torch.empty(getattr(lib, self._name("stl_det_dwconv_bwd_parts"))(m0) * 9 * c, device=dev)
-        self.grads: Dict[str, Dict[str, torch.Tensor]] = {}
-        if ncells:
-            assert not self.h16, "the BiFPN cells train in fp32 only"
+        if self.ncells:
             # the gradient of every node output of the trainable cells, by the address of the plan's map
-            self.gmap = {y.data_ptr(): torch.empty_like(y) for kept in plan.cells[len(plan.cells) - ncells:] for _, _, y, _, _ in kept.values()}
+            self.gmap = {r.y.data_ptr(): torch.empty_like(r.y) for kept in plan.cells[len(plan.cells) - self.ncells:] for r in kept.values()}
             if self.first:   # and of the first cell's seven input maps (p3_in, p4_in, p5_in, p4_in_2, p5_in_2, p6, p7) and of t
-                for y in [y for _, y, _ in plan.first_convs.values()] + [y for _, _, y in plan.first_pools]:
-                    self.gmap[y.data_ptr()] = torch.empty_like(y)
+                self.gmap.update({r.y.data_ptr(): torch.empty_like(r.y) for r in [*plan.first_convs.values(), *plan.first_pools]})
+            self.written = set()   # the maps whose gradient has its first contribution
             self.hc = [torch.empty_like(f) for f, _ in plan.feats]   # the classifier's gradient of each level (the regressor's goes to gmap)
             self.scale = torch.ones(2, device=dev)                   # the gradients of (regression, classification): _DetLossFn.backward
-        for name, out, k, act in (("regressor", self.reg, 4, 0), ("classifier", self.cls, nc, 2)):
-            lay, n = L[name], self.nlayers
-            g = dict(pw_w=torch.empty(5, n, c, c, device=dev), pw_b=torch.empty(5, n, c, device=dev),
-                     dw=torch.empty(5, n, 3, 3, c, device=dev), hpw_w=torch.empty(5, c, 9 * k, device=dev),
-                     hpw_b=torch.empty(5, 9 * k, device=dev), hdw=torch.empty(5, 3, 3, c, device=dev))
-            self.grads[name] = g
-            aoff = 0
-            for lv, (f, hh) in enumerate(plan.feats):
-                M = B * hh * hh
-                buf = lambda: torch.empty(B, hh, hh, c, device=dev, dtype=self.adtype)   # noqa: E731
-                t, d, z = [f], [], []
-                for i in range(n):
-                    d.append(buf()), z.append(buf()), t.append(buf())
-                    list_dwconv(self.fwd, self.code, t[i], plan._w(lay["dw"][i]), None, d[i], B, hh, c, 3, 1, 0)
-                    list_pointwise(self.fwd, self.code, plan.pw_fields(d[i], t[i + 1], hh * hh, c, c, lay["pw"][lv][i], 1), False, z=z[i])
-                dh = buf()
-                list_dwconv(self.fwd, self.code, t[n], plan._w(lay["hdw"]), None, dh, B, hh, c, 3, 1, 0)
-                strides = dict(img_stride=A * k, row_stride=9 * k, off=aoff * k)
-                list_pointwise(self.fwd, self.code, plan.pw_fields(dh, out, hh * hh, c, 9 * k, lay["hpw"], act, **strides), True)
-                self.fwd.keep_alive(*d, *t, dh)   # the pointwise descriptors hold their addresses
-                # backward, from the header down; ga / gb alternate as the gradient of a depthwise / a pointwise output
-                self.hdr[name].append(self._pw_bwd(plan, dh, None, self.ga, M, hh * hh, c, 9 * k, lay["hpw"], g["hpw_w"][lv],
-                                                   g["hpw_b"][lv], **strides))
-                self._dw_bwd(t[n], self.ga, plan._w(lay["hdw"]), g["hdw"][lv], z[n - 1], self.gb, hh)
-                for i in range(n - 1, -1, -1):
-                    self._pw_bwd(plan, d[i], self.gb, self.ga, M, hh * hh, c, c, lay["pw"][lv][i], g["pw_w"][lv, i], g["pw_b"][lv, i])
-                    dx0 = None if not ncells else (self.gmap[f.data_ptr()] if name == "regressor" else self.hc[lv])
-                    self._dw_bwd(t[i], self.ga, plan._w(lay["dw"][i]), g["dw"][lv, i], z[i - 1] if i else None, self.gb if i else dx0, hh)
-                aoff += hh * hh * 9
-        if ncells:
-            self._cells_bwd(plan, L)
-        self.bgrads = {}
-        if nblocks:
-            self._blocks_bwd(m, plan, L)
-
-    def _cells_bwd(self, plan, L) -> None:
-        """The backward launches of the trainable cells, behind the heads'."""
-        B, c, dev = self.B, self.c, self.dev
-        written = set()   # the maps whose gradient has its first contribution
-        for lv, (f, _) in enumerate(plan.feats):
-            g = self.gmap[f.data_ptr()]
-            self.bwd.add("stl_det_grad_add", g, self.hc[lv], self.scale, self.scale[1:], g, g.numel())
-            written.add(f.data_ptr())
-        self.fuse_ws = torch.empty(capi.lib().stl_det_fuse_bwd_workspace(self.ga.numel()), device=dev)
-        first = len(plan.cells) - self.ncells
-        self.cgrads = {}
-        for j in range(len(plan.cells) - 1, first - 1, -1):
-            lay, kept = L["bifpn"][j], plan.cells[j]
-            for name in reversed(_BiFPN.NODES):   # the forward runs them in this tuple's order
-                f, d, y, desc, terms = kept[name]
-                assert y.data_ptr() in written, (j, name)
-                h = y.shape[1]
-                g = dict(pw_w=torch.empty(c, c, device=dev), pw_b=torch.empty(c, device=dev), dw=torch.empty(3, 3, c, device=dev),
-                         what=torch.zeros(3, device=dev))
-                self.cgrads[j, name] = g
-                self._pw_bwd(plan, d, self.gmap[y.data_ptr()], self.ga, B * h * h, h * h, c, c, lay[name][1], g["pw_w"], g["pw_b"])
-                self._dw_bwd(f, self.ga, plan._w(lay[name][0]), g["dw"], None, self.gb, h)
-                fb = capi.DetFuseBwd()
-                for i, t in enumerate(terms):   # a term outside gmap is an input of the first trainable cell: frozen
-                    dst = self.gmap.get(t.data_ptr())
-                    if dst is not None:
-                        fb.dx[i], fb.accumulate[i] = dst.data_ptr(), int(t.data_ptr() in written)
-                        written.add(t.data_ptr())
-                self.bwd.keep_alive(f, d, y, *terms)   # the descriptors hold their addresses
-                self.bwd.add("stl_det_fuse_bwd", desc, self.gb, fb, self.fuse_ws, g["what"])
-        self.fgrads = {}
-        if not self.first:
+            self.fuse_ws = torch.empty(lib.stl_det_fuse_bwd_workspace(self.ga.numel()), device=dev)
+        if not recs:
             return
-        # behind the first cell's nodes: p6 -> p7 adds to g(p6), which is complete then; t -> p6 writes g(t); then the weight gradients
-        # of the six 1x1 layers, x the frozen backbone map (no data gradient: nothing trains before them), p5_to_p6 first
-        for desc, x, y in reversed(plan.first_pools):
-            assert y.data_ptr() in written, "a pooled map of the first cell without a gradient"
-            self.bwd.keep_alive(x, y)
-            self.bwd.add("stl_det_pool_bwd", desc, self.gmap[y.data_ptr()], self.gmap[x.data_ptr()], int(x.data_ptr() in written))
-            written.add(x.data_ptr())
-        order = ("p5_to_p6", "p3_down_channel", "p4_down_channel", "p5_down_channel", "p4_down_channel_2", "p5_down_channel_2")
-        assert sorted(order) == sorted(plan.first_convs)
-        for key in order:
-            x, y, pk = plan.first_convs[key]
-            assert y.data_ptr() in written, key
-            ci, hw = x.shape[3], x.shape[1] * x.shape[2]
-            g = self.fgrads[key] = dict(pw_w=torch.empty(ci, c, device=dev), pw_b=torch.empty(c, device=dev))
-            dy = self.gmap[y.data_ptr()]
-            p = capi.DetPointwiseBwd(x.data_ptr(), None, dy.data_ptr(), None, g["pw_w"].data_ptr(), g["pw_b"].data_ptr(),
-                                     self.pw_part.data_ptr(), B * hw, hw * c, c, 0, hw, ci, c, pk[2], pk[3], 0)
-            self.bwd.keep_alive(x, dy, g["pw_w"], g["pw_b"])   # the descriptor holds their addresses
-            self.bwd.add("stl_det_pointwise_bwd_weight", p)
-
-    def _pw_bwd_data(self, plan, pk, dy, dx, hw, ci, co) -> None:
-        """The data gradient alone of the pointwise layer packed as pk: dx [B hw, ci] = dy [B hw, co] W'^T."""
-        p = capi.DetPointwiseBwd(None, plan.wbuf[pk[0]:].data_ptr(), dy.data_ptr(), dx.data_ptr(), None, None, None, self.B * hw, hw * co,
-                                 co, 0, hw, ci, co, pk[2], pk[3], 0)
-        self.bwd.keep_alive(dy, dx)   # the descriptor holds their addresses
-        self.bwd.add("stl_det_pointwise_bwd_data", p)
-
-    def _pw_bwd_weight(self, pk, x, dy, gw, gb, hw, ci, co) -> None:
-        """The weight and bias gradient alone of the pointwise layer packed as pk, x [B hw, ci], dy [B hw, co]."""
-        p = capi.DetPointwiseBwd(x.data_ptr(), None, dy.data_ptr(), None, gw.data_ptr(), gb.data_ptr(), self.pw_part.data_ptr(),
-                                 self.B * hw, hw * co, co, 0, hw, ci, co, pk[2], pk[3], 0)
-        self.bwd.keep_alive(x, dy, gw, gb)   # the descriptor holds their addresses
-        self.bwd.add("stl_det_pointwise_bwd_weight", p)
-
-    def _join(self, plan, dx, x, keys) -> None:
-        """dx, the gradient of the backbone map x, += the data gradients of the first cell's 1x1 layers `keys` that read x: each into a
-        buffer of its own, added in the order of `keys`."""
-        hw, ci = x.shape[1] * x.shape[2], x.shape[3]
-        for key in keys:
-            xx, y, pk = plan.first_convs[key]
-            assert xx is x, key
-            t = torch.empty_like(x)
-            self._pw_bwd_data(plan, pk, self.gmap[y.data_ptr()], t, hw, ci, self.c)
-            self.bwd.add("stl_det_grad_add", dx, t, None, None, dx, dx.numel())
-            self.bwd.keep_alive(t)
-
-    def _blocks_bwd(self, m, plan, L) -> None:
-        """The backward launches of the trainable MBConv blocks (csrc/detector_mbconv.hip, csrc/detector_trunk.hip), behind the cells':
-        the data gradient of P5 through the three 1x1 layers of the first cell that read it, then the blocks, the last one first, then
-        the stem's weight gradient when it trains."""
-        B, dev, lib = self.B, self.dev, capi.lib()
-        net = m.backbone_net.model
-        specs, nb = net.specs, len(plan.blocks)
-        p3, p4, p5 = plan.backbone
-        h, c5 = p5.shape[1], p5.shape[3]
-        assert plan.blocks[-1][4] is p5
-        self.blocks_start = len(self.bwd)   # bwd.calls[blocks_start:] are these launches
-        parts = []
-        for key in ("p5_to_p6", "p5_down_channel", "p5_down_channel_2"):   # each into a buffer of its own, joined in this order
-            x, y, pk = plan.first_convs[key]
-            assert x is p5, key
-            parts.append(torch.empty_like(p5))
-            self._pw_bwd_data(plan, pk, self.gmap[y.data_ptr()], parts[-1], h * h, c5, self.c)
-        dy = self.gp5 = parts[0]   # the gradient of P5
-        for t in parts[1:]:
-            self.bwd.add("stl_det_grad_add", dy, t, None, None, dy, dy.numel())
-        self.bwd.keep_alive(*parts)
-        first = nb - self.nblocks
-        heads_form = nb - m.final_stage_blocks()   # from this block on: 3 x 3 / 1, the heads' depthwise backward entry points
-        todo = range(first, nb)
-        mids = [specs[i]["mid"] for i in todo]
-        ses = [specs[i]["se"] for i in todo]
-        hin = [plan.blocks[i][0].shape[1] for i in todo]
-        hout = [plan.blocks[i][2].shape[1] for i in todo]
         # scratch shared by the blocks, sized for the largest h^2 mid among them: D / du (output resolution); xs / u (output) and z_e
         # (input resolution); dz_e (input resolution); and the small ones
-        n1 = max(ho * ho * mid for ho, mid in zip(hout, mids))
-        n2 = max(max(ho * ho, hi * hi if specs[i]["e"] != 1 else 0) * mid for i, hi, ho, mid in zip(todo, hin, hout, mids))
-        n3 = max([hi * hi * mid for i, hi, mid in zip(todo, hin, mids) if specs[i]["e"] != 1] + [1])
-        s1, s2, s3 = (torch.empty(B * n, device=dev) for n in (n1, n2, n3))
-        gate_ws = torch.empty(max(lib.stl_det_mbconv_gate_bwd_workspace(B, ho * ho, mid) for ho, mid in zip(hout, mids)), device=dev)
-        act_ws = torch.empty(max(lib.stl_det_mbconv_act_bwd_workspace(B, ho * ho, mid) for ho, mid in zip(hout, mids)), device=dev)
-        se_ws = torch.empty(max(lib.stl_det_se_bwd_workspace(B, mid, cs) for mid, cs in zip(mids, ses)), device=dev)
-        asum, dgate, dpool = (torch.empty(B * max(mids), device=dev) for _ in range(3))
-        dwb_part = torch.empty(lib.stl_det_dwconv_bwd_parts(B * h * h) * 9 * max(mids[max(heads_form - first, 0):]), device=dev)
-        ks_part = torch.empty(max([lib.stl_det_dwconv_bwd_ks_parts(B * ho * ho) * specs[i]["k"] ** 2 * mid
-                                   for i, ho, mid in zip(todo, hout, mids) if i < heads_form] + [1]), device=dev)
-        self.bwd.keep_alive(s1, s2, s3, gate_ws, act_ws, se_ws, asum, dgate, dpool, dwb_part, ks_part)
-        self.block_dy = {}   # block -> the gradient of its output, after every join
-        self.stem_dy = None  # the gradient of the stem's output (train_stem)
-        for i in range(nb - 1, first - 1, -1):
-            b, lay = specs[i], L["blocks"][i]
-            inp, e, a, gate, y = plan.blocks[i]
-            ci, mid, co, cs, k, s = b["ci"], b["mid"], b["co"], b["se"], b["k"], b["s"]
-            hi, ho = inp.shape[1], a.shape[1]
-            hwi, hwo = hi * hi, ho * ho
-            old = i >= heads_form
-            assert dy.shape == y.shape and (e is None) == (b["e"] == 1) and ho == (hi + s - 1) // s, i
-            assert not old or (k == 3 and s == 1 and e is not None), i
-            self.block_dy[i] = dy
-            g = self.bgrads[i] = dict(exp_w=torch.empty(ci, mid, device=dev), exp_b=torch.empty(mid, device=dev)) if e is not None else {}
-            g.update(dw=torch.empty(k, k, mid, device=dev), dw_b=torch.empty(mid, device=dev),
-                     se_w1=torch.empty(cs, mid, device=dev), se_b1=torch.empty(cs, device=dev),
-                     se_w2=torch.empty(mid, cs, device=dev), se_b2=torch.empty(mid, device=dev),
-                     proj_w=torch.empty(mid, co, device=dev), proj_b=torch.empty(co, device=dev))
-            self.bwd.keep_alive(inp, e, a, gate, y, *g.values())
-            wd, bd = plan._w(lay["dw"][0]), plan._w(lay["dw"][1])
-            xd = inp if e is None else e   # what the depthwise layer reads
-            # the projection: D = dy Wp'^T; xs = a g, asum, dgate; dWp', dbp' with x = xs
-            self._pw_bwd_data(plan, lay["project"], dy, s1, hwo, mid, co)
-            self.bwd.add("stl_det_mbconv_gate_bwd", a, s1, gate, s2, gate_ws, asum, dgate, B, hwo, mid)
-            self._pw_bwd_weight(lay["project"], s2, dy, g["proj_w"], g["proj_b"], hwo, mid, co)
-            # the gate: dpool and the SE gradients
-            self.bwd.add("stl_det_se_bwd", asum, dgate, gate, B, hwo, mid, cs, *[plan._w(o) for o in lay["se"]], se_ws, dpool,
-                         g["se_w1"], g["se_b1"], g["se_w2"], g["se_b2"])
-            # the depthwise layer: u recomputed by the forward's launch without the activation; du overwrites D; db_d'; dw_d'
-            list_dwconv(self.bwd, 0, xd, wd, bd, s2, B, hi, mid, k, s, 0)
-            self.bwd.add("stl_det_mbconv_act_bwd", s1, s2, gate, dpool, s1, act_ws, g["dw_b"], B, hwo, mid)
-            if old:
-                self.bwd.add("stl_det_dwconv_bwd_weight", xd, s1, dwb_part, g["dw"], B, hi, hi, mid)
-            else:
-                self.bwd.add("stl_det_dwconv_bwd_weight_ks", xd, s1, ks_part, g["dw"], B, hi, hi, mid, k, s)
-            need_dx = i > first or self.stem   # the block (or the stem) in front trains too: the gradient of this block's input
-            dx = torch.empty_like(inp) if need_dx else None
-            if e is not None:
-                # the expand layer: its pre-activation z_e recomputed the same way, dz_e = dwconv^T(du) swish'(z_e); dWe', dbe'
-                list_pointwise(self.bwd, 0, plan.pw_fields(inp, s2, hwi, ci, mid, lay["expand"], 0), False)
-                if old:
-                    self.bwd.add("stl_det_dwconv_bwd_data", s1, wd, s2, s3, B, hi, hi, mid)
-                else:
-                    self.bwd.add("stl_det_dwconv_bwd_data_ks", s1, wd, s2, s3, B, hi, hi, mid, k, s)
-                self._pw_bwd_weight(lay["expand"], inp, s3, g["exp_w"], g["exp_b"], hwi, ci, mid)
-                if need_dx:
-                    self._pw_bwd_data(plan, lay["expand"], s3, dx, hwi, ci, mid)
-            elif need_dx:   # no expand layer: the depthwise layer reads the block input, its data gradient is the input's
-                self.bwd.add("stl_det_dwconv_bwd_data_ks", s1, wd, None, dx, B, hi, hi, mid, k, s)
-            if need_dx:
-                # joined in this order: the block's own data gradient, dy through the skip, then -- where the input is P4 / P3 -- the
-                # data gradients of the first cell's 1x1 layers that read it: p4_down_channel, p4_down_channel_2 / p3_down_channel
-                if b["skip"]:
-                    self.bwd.add("stl_det_grad_add", dx, dy, None, None, dx, dx.numel())
-                if inp is p4:
-                    self._join(plan, dx, p4, ("p4_down_channel", "p4_down_channel_2"))
-                elif inp is p3:
-                    self._join(plan, dx, p3, ("p3_down_channel",))
-                dy = dx
-        if self.stem:
-            assert first == 0 and dy.shape == plan.blocks[0][0].shape
-            self.stem_dy = dy
-            S, co = plan.canvas.shape[1], dy.shape[3]
-            ho = dy.shape[1]
-            self.sgrads = dict(w=torch.empty(3, 3, 3, co, device=dev), b=torch.empty(co, device=dev))
-            stem_part = torch.empty(lib.stl_det_stem_bwd_parts(B * ho * ho) * 28 * co, device=dev)
-            # the canvas the forward read: the plan's own, or the batch's (set_canvas before each backward)
-            self.canvas_arg = ctypes.c_void_p(plan.canvas.data_ptr())
-            self.bwd.keep_alive(plan.canvas, dy, stem_part, *self.sgrads.values())
-            self.bwd.add("stl_det_stem_bwd", self.canvas_arg, plan._w(L["stem"][0]), plan._w(L["stem"][1]), dy, stem_part, self.sgrads["w"],
-                         self.sgrads["b"], B, S, S, co)
-
-    def set_canvas(self, canvas) -> None:
-        """The canvas the forward about to be differentiated read (None: the plan's own); the caller keeps it alive until the backward."""
-        if self.stem:
-            self.canvas_arg.value = self.own_canvas if canvas is None else canvas.data_ptr()
+        first, h5 = len(plan.blocks) - len(recs), plan.backbone[2].shape[1]
+        dims = [(i, r.inp.shape[1] ** 2 if r.e is not None else 0, r.a.shape[1] ** 2, r.a.shape[3]) for i, r in enumerate(recs, first)]
+        flat = lambda n: torch.empty(n, device=dev)   # noqa: E731
+        self.ws = ws = SimpleNamespace(
+            s1=flat(B * max(hwo * mid for _, _, hwo, mid in dims)),
+            s2=flat(B * max(max(hwo, hwe) * mid for _, hwe, hwo, mid in dims)),
+            s3=flat(B * max(max(hwe * mid for _, hwe, _, mid in dims), 1)),
+            gate_ws=flat(max(lib.stl_det_mbconv_gate_bwd_workspace(B, hwo, mid) for _, _, hwo, mid in dims)),
+            act_ws=flat(max(lib.stl_det_mbconv_act_bwd_workspace(B, hwo, mid) for _, _, hwo, mid in dims)),
+            se_ws=flat(max(lib.stl_det_se_bwd_workspace(B, mid, self.specs[i]["se"]) for i, _, _, mid in dims)),
+            asum=flat(B * max(d[3] for d in dims)), dgate=flat(B * max(d[3] for d in dims)), dpool=flat(B * max(d[3] for d in dims)),   # [B, mid]
+            dwb_part=flat(lib.stl_det_dwconv_bwd_parts(B * h5 * h5) * 9 * max(mid for i, _, _, mid in dims if i >= self.heads_form)),
+            ks_part=flat(max([lib.stl_det_dwconv_bwd_ks_parts(B * hwo) * self.specs[i]["k"] ** 2 * mid
+                              for i, _, hwo, mid in dims if i < self.heads_form] + [1])))
+        self.bwd.keep_alive(*vars(ws).values())
 
     def _name(self, name: str) -> str:
         return NAME16[name] if self.h16 else name
 
-    def _pw_bwd(self, plan, x, dy, dx, M, hw, ci, co, pk, gw, gb, img_stride=None, row_stride=None, off=0):
-        """Weight and data gradient of one pointwise layer; dy None: a header, whose dy (dreg / dlogit, fp32) set_grads fills in."""
+    def _pw_desc(self, plan, pk, x, dy, dx, gw, gb, hw, ci, co, img_stride=None, row_stride=None, off=0):
+        """The backward descriptor of the pointwise layer packed as pk = (w, bias, Kp, Np), x [B hw, ci], dy [B hw, co], for
+        stl_det_pointwise_bwd_weight (x, gw, gb, and the slab workspace with them), stl_det_pointwise_bwd_data (dx [B hw, ci] = dy W'^T,
+        and the folded weight with it) or both; the strides and the offset place dy's rows inside a larger output.  dy None: a header,
+        whose dy (dreg / dlogit, fp32) set_grads fills in.  Keeps the owners alive."""
         w, _, kp, np_ = pk
-        ptrs = (None if dy is None else dy.data_ptr(), dx.data_ptr(), gw.data_ptr(), gb.data_ptr(), self.pw_part.data_ptr(), M,
+        ptr = lambda t: None if t is None else t.data_ptr()   # noqa: E731
+        rest = (ptr(dy), ptr(dx), ptr(gw), ptr(gb), None if gw is None else self.pw_part.data_ptr(), self.B * hw,
                 hw * co if img_stride is None else img_stride, co if row_stride is None else row_stride, off, hw, ci, co)
         if self.h16:
             wt, kt, nt = self.layoutT[w]
-            p = capi.DetPointwise16Bwd(x.data_ptr(), self.wbufT[wt:].data_ptr(), *ptrs, kt, nt, self.code, 1 if dy is None else 0, 0)
+            p = capi.DetPointwise16Bwd(ptr(x), self.wbufT[wt:].data_ptr(), *rest, kt, nt, self.code, 1 if dy is None else 0, 0)
         else:
-            p = capi.DetPointwiseBwd(x.data_ptr(), plan.wbuf[w:].data_ptr(), *ptrs, kp, np_, 0)
-        self.bwd.keep_alive(x, gw, gb)   # the descriptor holds their addresses
-        self.bwd.add(self._name("stl_det_pointwise_bwd_weight"), p)
-        self.bwd.add(self._name("stl_det_pointwise_bwd_data"), p)
+            p = capi.DetPointwiseBwd(ptr(x), None if dx is None else plan.wbuf[w:].data_ptr(), *rest, kp, np_, 0)
+        self.bwd.keep_alive(x, dy, dx, gw, gb)   # the descriptor holds their addresses
         return p
 
     def _dw_bwd(self, x, dy, w, gw, z, dx, h):
@@ -451,6 +243,215 @@ class HeadTrain:
         self.bwd.add(self._name("stl_det_dwconv_bwd_weight"), *code, x, dy, self.dw_part, gw, self.B, h, h, self.c)
         if dx is not None:
             self.bwd.add(self._name("stl_det_dwconv_bwd_data"), dy, w, z, dx, self.B, h, h, self.c, *code)
+
+    def _head(self, plan, lay, name, lv, f, hh, out, k, act, strides) -> None:
+        """One (head, level).  Its forward runs the head with the inference kernels -- ``reg`` and ``cls`` equal the inference plan's
+        bit for bit -- and keeps what the backward needs: every depthwise output, and the pre-activation ``z`` of every swish, written
+        by the pointwise launch that applies it (stl_det_pointwise_train).  Its backward walks from the header down through
+        csrc/detector_train.hip and produces gradients of the *folded* weights W' = W s, b' = b s + t (s, t the frozen BN's scale and
+        shift) per level; ``fold_chain`` carries them to W, b, gamma and beta in a few elementwise torch ops, and the weights shared
+        by the five levels sum their five contributions.  The first depthwise layer of a (head, level) reads a frozen feature map:
+        no data gradient is computed for it.  Where cells train, it also computes its data gradient (stl_det_dwconv_bwd_data without
+        z): the regressor's into the level's gradient map, the classifier's into ``hc``."""
+        B, c, n, g, hw = self.B, self.c, self.nlayers, self.grads[name], hh * hh
+        buf = lambda: torch.empty(B, hh, hh, c, device=self.dev, dtype=self.adtype)   # noqa: E731
+        t, d, z = [f], [], []
+        for i in range(n):
+            d.append(buf()), z.append(buf()), t.append(buf())
+            list_dwconv(self.fwd, self.code, t[i], plan._w(lay["dw"][i]), None, d[i], B, hh, c, 3, 1, 0)
+            list_pointwise(self.fwd, self.code, plan.pw_fields(d[i], t[i + 1], hw, c, c, lay["pw"][lv][i], 1), False, z=z[i])
+        dh = buf()
+        list_dwconv(self.fwd, self.code, t[n], plan._w(lay["hdw"]), None, dh, B, hh, c, 3, 1, 0)
+        list_pointwise(self.fwd, self.code, plan.pw_fields(dh, out, hw, c, 9 * k, lay["hpw"], act, **strides), True)
+        self.fwd.keep_alive(*d, *t, dh)   # the pointwise descriptors hold their addresses
+        # backward, from the header down; ga / gb alternate as the gradient of a depthwise / a pointwise output
+        weight, data = self._name("stl_det_pointwise_bwd_weight"), self._name("stl_det_pointwise_bwd_data")
+        p = self._pw_desc(plan, lay["hpw"], dh, None, self.ga, g["hpw_w"][lv], g["hpw_b"][lv], hw, c, 9 * k, **strides)
+        self.hdr[name].append(p)
+        self.bwd.add(weight, p)
+        self.bwd.add(data, p)
+        self._dw_bwd(t[n], self.ga, plan._w(lay["hdw"]), g["hdw"][lv], z[n - 1], self.gb, hh)
+        for i in range(n - 1, -1, -1):
+            p = self._pw_desc(plan, lay["pw"][lv][i], d[i], self.gb, self.ga, g["pw_w"][lv, i], g["pw_b"][lv, i], hw, c, c)
+            self.bwd.add(weight, p)
+            self.bwd.add(data, p)
+            dx0 = None if not self.ncells else (self.gmap[f.data_ptr()] if name == "regressor" else self.hc[lv])
+            self._dw_bwd(t[i], self.ga, plan._w(lay["dw"][i]), g["dw"][lv, i], z[i - 1] if i else None, self.gb if i else dx0, hh)
+
+    def _levels_join(self, plan) -> None:
+        """Behind the heads where cells train: the two heads' gradients of a level are added regressor first, each times the gradient
+        of its own loss (stl_det_grad_add reads the two scalars on the device)."""
+        for lv, (f, _) in enumerate(plan.feats):
+            g = self.gmap[f.data_ptr()]
+            self.bwd.add("stl_det_grad_add", g, self.hc[lv], self.scale, self.scale[1:], g, g.numel())
+            self.written.add(f.data_ptr())
+
+    def _node(self, plan, lay, j, node) -> None:
+        """One node of a trainable cell: ``model.set_train_bifpn(k)`` (1 <= k <= cells - 1, or "all": ``_first_cell``) trains the last k
+        BiFPN cells with the heads, fp32 only.  The forward is not touched: the inference plan keeps every map (``_Plan.cells``), and
+        the backward recomputes each node's pre-activation from them.  The cells run in reverse, the nodes of a cell in the reverse
+        of the forward order.  Every consumer of a map comes later in the forward order, so a map's gradient is complete when its
+        node is reached; the first contribution writes, the later ones accumulate, in that fixed order.  Per node: the pointwise
+        layer's weight and data gradient (x = d), the depthwise layer's weight gradient (x = f) and data gradient, then
+        stl_det_fuse_bwd (csrc/detector_bifpn.hip), whose destinations are null for the frozen inputs of the first trainable cell.
+        ``cell_raw_grads`` carries the folded gradients to the raw parameters: ``fold_chain`` for the pointwise layer and its BN,
+        ``fusion_weight_grads`` for ``p*_w1`` / ``p*_w2``."""
+        r, c, dev = plan.cells[j][node], self.c, self.dev
+        assert r.y.data_ptr() in self.written, (j, node)
+        h = r.y.shape[1]
+        g = self.cgrads[j, node] = dict(pw_w=torch.empty(c, c, device=dev), pw_b=torch.empty(c, device=dev),
+                                        dw=torch.empty(3, 3, c, device=dev), what=torch.zeros(3, device=dev))
+        p = self._pw_desc(plan, lay[1], r.d, self.gmap[r.y.data_ptr()], self.ga, g["pw_w"], g["pw_b"], h * h, c, c)
+        self.bwd.add("stl_det_pointwise_bwd_weight", p)
+        self.bwd.add("stl_det_pointwise_bwd_data", p)
+        self._dw_bwd(r.f, self.ga, plan._w(lay[0]), g["dw"], None, self.gb, h)
+        fb = capi.DetFuseBwd()
+        for i, t in enumerate(r.terms):   # a term outside gmap is an input of the first trainable cell: frozen
+            dst = self.gmap.get(t.data_ptr())
+            if dst is not None:
+                fb.dx[i], fb.accumulate[i] = dst.data_ptr(), int(t.data_ptr() in self.written)
+                self.written.add(t.data_ptr())
+        self.bwd.keep_alive(r.f, r.d, r.y, *r.terms)   # the descriptors hold their addresses
+        self.bwd.add("stl_det_fuse_bwd", r.desc, self.gb, fb, self.fuse_ws, g["what"])
+
+    def _first_cell(self, plan) -> None:
+        """``model.set_train_bifpn("all")`` trains the first cell too, so everything behind the frozen backbone.  Its eight nodes run
+        through ``_node``; their inputs are the seven maps the cell makes from P3 / P4 / P5 (``p3_in``, ``p4_in``, ``p5_in``, the second
+        ``p4_in`` / ``p5_in`` of the down path, ``p6``, ``p7``), which get gradient maps like any node output.  Behind the nodes:
+        stl_det_pool_bwd (csrc/detector_bifpn.hip) of ``p6 -> p7``, adding to the gradient of ``p6``, which is complete then, then of
+        ``t -> p6`` (``t`` the output of ``p5_to_p6``'s conv and BN), then the weight gradients of the six 1x1 layers
+        (stl_det_pointwise_bwd_weight with x = the backbone map: ``p5_to_p6``, the three ``*_down_channel``, the two
+        ``*_down_channel_2``; ``_Plan.first_pools`` / ``first_convs``).  No data gradient is computed for P3 / P4 / P5 here (``_p5_join``,
+        ``_block``: where blocks train).  ``fold_chain`` carries each folded pair to the conv's weight and bias and the BN's."""
+        c, dev = self.c, self.dev
+        for r in reversed(plan.first_pools):
+            assert r.y.data_ptr() in self.written, "a pooled map of the first cell without a gradient"
+            self.bwd.keep_alive(r.x, r.y)
+            self.bwd.add("stl_det_pool_bwd", r.desc, self.gmap[r.y.data_ptr()], self.gmap[r.x.data_ptr()], int(r.x.data_ptr() in self.written))
+            self.written.add(r.x.data_ptr())
+        assert sorted(FIRST_CONVS) == sorted(plan.first_convs)
+        for key in FIRST_CONVS:
+            r = plan.first_convs[key]
+            assert r.y.data_ptr() in self.written, key
+            ci, hw = r.x.shape[3], r.x.shape[1] * r.x.shape[2]
+            g = self.fgrads[key] = dict(pw_w=torch.empty(ci, c, device=dev), pw_b=torch.empty(c, device=dev))
+            self.bwd.add("stl_det_pointwise_bwd_weight",
+                         self._pw_desc(plan, r.pk, r.x, self.gmap[r.y.data_ptr()], None, g["pw_w"], g["pw_b"], hw, ci, c))
+
+    def _first_conv_bwd_data(self, plan, key, x) -> torch.Tensor:
+        """The data gradient of the first cell's 1x1 layer ``key``, which reads the backbone map x, into a buffer of its own."""
+        r = plan.first_convs[key]
+        assert r.x is x, key
+        t = torch.empty_like(x)
+        self.bwd.add("stl_det_pointwise_bwd_data",
+                     self._pw_desc(plan, r.pk, None, self.gmap[r.y.data_ptr()], t, None, None, x.shape[1] * x.shape[2], x.shape[3], self.c))
+        return t
+
+    def _p5_join(self, plan) -> torch.Tensor:
+        """``model.set_train_backbone(k)`` (needs "all"; fp32) trains the last k MBConv blocks of the backbone's final stage too (block 15
+        of D0, blocks 24 / 25 of D3: 3x3 stride-1 depthwise layers).  Behind the cells' launches: stl_det_pointwise_bwd_data of
+        ``p5_to_p6``, ``p5_down_channel`` and ``p5_down_channel_2`` into a buffer each, joined in that order by stl_det_grad_add -- the
+        gradient of P5, which this returns."""
+        p5 = plan.backbone[2]
+        assert plan.blocks[-1].y is p5
+        parts = [self._first_conv_bwd_data(plan, key, p5) for key in P5_READERS]
+        for t in parts[1:]:
+            self.bwd.add("stl_det_grad_add", parts[0], t, None, None, parts[0], parts[0].numel())
+        return parts[0]
+
+    def _block_dw_bwd(self, i, kind, hi, *ptrs) -> None:
+        """Lists the depthwise weight gradient (kind "weight": x, dy, gw) or data gradient ("data": dy, w, z, dx) of block i on its hi x hi
+        input: a block of the final stage through the heads' entry points, one in front of it through stl_det_dwconv_bwd_weight_ks /
+        _data_ks (csrc/detector_trunk.hip: k 3 / 5, s 1 / 2 under TF "same" padding).  The two sum in different orders: the split is fixed."""
+        b, old = self.specs[i], i >= self.heads_form
+        assert not old or (b["k"] == 3 and b["s"] == 1 and b["e"] != 1), i
+        if kind == "weight":
+            ptrs = (*ptrs[:2], self.ws.dwb_part if old else self.ws.ks_part, ptrs[2])
+        self.bwd.add(f"stl_det_dwconv_bwd_{kind}" + ("" if old else "_ks"), *ptrs, self.B, hi, hi, b["mid"], *(() if old else (b["k"], b["s"])))
+
+    def _block(self, plan, lay, i, dy, need_dx):
+        """MBConv block i from dy, the gradient of its output; need_dx: the block (or the stem) in front trains too, and the gradient
+        of this block's input is returned.  The forward is the inference forward (no drop-connect, BN on running statistics);
+        ``_Plan.blocks`` keeps each block's input, expand output e, depthwise output a, gate g and output.  With the folded weights: D =
+        dy Wp'^T (stl_det_pointwise_bwd_data); stl_det_mbconv_gate_bwd (csrc/detector_mbconv.hip: xs = a g, sum a, sum D a); the
+        projection's weight gradient with x = xs; stl_det_se_bwd (dpool and the four SE gradients); the depthwise pre-activation u
+        recomputed by stl_det_dwconv at act 0; stl_det_mbconv_act_bwd (du = (D g + dpool / HW) swish'(u) over D, and the folded BN's
+        bias gradient); stl_det_dwconv_bwd_weight (x = e); the expand layer's pre-activation recomputed by stl_det_pointwise at act 0;
+        stl_det_dwconv_bwd_data (times swish' of it); the expand layer's weight gradient (x = the block input); and, where the block
+        in front trains too, its data gradient plus dy through the skip.  ``block_raw_grads`` carries the folded gradients to the raw
+        parameters (``fold_chain`` without a conv bias, ``dw_fold_chain``).
+
+        ``model.set_train_trunk(k)`` reaches further back: the last k blocks of the whole backbone, ``"all"`` the stem too.  The final
+        stage's blocks keep the launches above; a block in front of it runs the same sequence with the k x k / s depthwise entry
+        points (``_block_dw_bwd``), the projection, gate, SE and act steps at the block's output resolution, the expand recompute, the
+        depthwise data gradient and the expand gradients at its input resolution.  A block without an expand layer (e = 1) has no
+        ``exp_w`` / ``exp_b``: its depthwise layer reads the block input, and stl_det_dwconv_bwd_data_ks without z is the input's
+        gradient.  The gradient of a block's input is joined in a fixed order: the block's own data gradient, dy through the skip,
+        then -- where the input is P4 / P3, the inputs of the last two stride-2 blocks -- stl_det_pointwise_bwd_data of
+        ``p4_down_channel`` and ``p4_down_channel_2`` / of ``p3_down_channel``, each into a buffer of its own and added by
+        stl_det_grad_add.  ``tr.block_dy[i]`` keeps the joined gradient of block i's output."""
+        B, dev, ws, b, r = self.B, self.dev, self.ws, self.specs[i], plan.blocks[i]
+        ci, mid, co, cs, k, s = b["ci"], b["mid"], b["co"], b["se"], b["k"], b["s"]
+        hi, ho, hwi, hwo = r.inp.shape[1], r.a.shape[1], r.inp.shape[1] ** 2, r.a.shape[1] ** 2
+        assert dy.shape == r.y.shape and (r.e is None) == (b["e"] == 1) and ho == (hi + s - 1) // s, i
+        self.block_dy[i] = dy
+        g = self.bgrads[i] = dict(exp_w=torch.empty(ci, mid, device=dev), exp_b=torch.empty(mid, device=dev)) if r.e is not None else {}
+        g.update(dw=torch.empty(k, k, mid, device=dev), dw_b=torch.empty(mid, device=dev), se_w1=torch.empty(cs, mid, device=dev),
+                 se_b1=torch.empty(cs, device=dev), se_w2=torch.empty(mid, cs, device=dev), se_b2=torch.empty(mid, device=dev),
+                 proj_w=torch.empty(mid, co, device=dev), proj_b=torch.empty(co, device=dev))
+        self.bwd.keep_alive(*r, *g.values())
+        wd, bd = plan._w(lay["dw"][0]), plan._w(lay["dw"][1])
+        xd = r.inp if r.e is None else r.e   # what the depthwise layer reads
+        # the projection: D = dy Wp'^T; xs = a g, asum, dgate; dWp', dbp' with x = xs
+        self.bwd.add("stl_det_pointwise_bwd_data", self._pw_desc(plan, lay["project"], None, dy, ws.s1, None, None, hwo, mid, co))
+        self.bwd.add("stl_det_mbconv_gate_bwd", r.a, ws.s1, r.gate, ws.s2, ws.gate_ws, ws.asum, ws.dgate, B, hwo, mid)
+        self.bwd.add("stl_det_pointwise_bwd_weight", self._pw_desc(plan, lay["project"], ws.s2, dy, None, g["proj_w"], g["proj_b"], hwo, mid, co))
+        # the gate: dpool and the SE gradients
+        self.bwd.add("stl_det_se_bwd", ws.asum, ws.dgate, r.gate, B, hwo, mid, cs, *[plan._w(o) for o in lay["se"]], ws.se_ws, ws.dpool,
+                     g["se_w1"], g["se_b1"], g["se_w2"], g["se_b2"])
+        # the depthwise layer: u recomputed by the forward's launch without the activation; du overwrites D; db_d'; dw_d'
+        list_dwconv(self.bwd, 0, xd, wd, bd, ws.s2, B, hi, mid, k, s, 0)
+        self.bwd.add("stl_det_mbconv_act_bwd", ws.s1, ws.s2, r.gate, ws.dpool, ws.s1, ws.act_ws, g["dw_b"], B, hwo, mid)
+        self._block_dw_bwd(i, "weight", hi, xd, ws.s1, g["dw"])
+        dx = torch.empty_like(r.inp) if need_dx else None
+        if r.e is not None:
+            # the expand layer: its pre-activation z_e recomputed the same way, dz_e = dwconv^T(du) swish'(z_e); dWe', dbe'
+            list_pointwise(self.bwd, 0, plan.pw_fields(r.inp, ws.s2, hwi, ci, mid, lay["expand"], 0), False)
+            self._block_dw_bwd(i, "data", hi, ws.s1, wd, ws.s2, ws.s3)
+            self.bwd.add("stl_det_pointwise_bwd_weight", self._pw_desc(plan, lay["expand"], r.inp, ws.s3, None, g["exp_w"], g["exp_b"], hwi, ci, mid))
+            if need_dx:
+                self.bwd.add("stl_det_pointwise_bwd_data", self._pw_desc(plan, lay["expand"], None, ws.s3, dx, None, None, hwi, ci, mid))
+        elif need_dx:   # no expand layer: the depthwise layer reads the block input, its data gradient is the input's
+            self._block_dw_bwd(i, "data", hi, ws.s1, wd, None, dx)
+        if need_dx:
+            # joined in this order: the block's own data gradient, dy through the skip, then -- where the input is P4 / P3 -- the
+            # data gradients of the first cell's 1x1 layers that read it: p4_down_channel, p4_down_channel_2 / p3_down_channel
+            if b["skip"]:
+                self.bwd.add("stl_det_grad_add", dx, dy, None, None, dx, dx.numel())
+            p3, p4, _ = plan.backbone
+            for key in P4_READERS if r.inp is p4 else P3_READERS if r.inp is p3 else ():
+                self.bwd.add("stl_det_grad_add", dx, self._first_conv_bwd_data(plan, key, r.inp), None, None, dx, dx.numel())
+        return dx
+
+    def _stem(self, plan, lay, dy) -> None:
+        """With the stem, block 0 also produces its input's gradient (``tr.stem_dy``, that of the stem's output) and stl_det_stem_bwd
+        follows (the pre-activation recomputed from the canvas the forward read; no image gradient); its ``[3][3][3][Co]`` gradient is
+        permuted to ``[Co, 3, 3, 3]`` and folded through ``_bn0`` as a conv without bias (``block_raw_grads``)."""
+        assert dy.shape == plan.blocks[0].inp.shape
+        self.stem_dy = dy
+        S, ho, co, dev = plan.canvas.shape[1], dy.shape[1], dy.shape[3], self.dev
+        self.sgrads = dict(w=torch.empty(3, 3, 3, co, device=dev), b=torch.empty(co, device=dev))
+        stem_part = torch.empty(capi.lib().stl_det_stem_bwd_parts(self.B * ho * ho) * 28 * co, device=dev)
+        # the canvas the forward read: the plan's own, or the batch's (set_canvas before each backward)
+        self.canvas_arg = ctypes.c_void_p(plan.canvas.data_ptr())
+        self.bwd.keep_alive(plan.canvas, dy, stem_part, *self.sgrads.values())
+        self.bwd.add("stl_det_stem_bwd", self.canvas_arg, plan._w(lay[0]), plan._w(lay[1]), dy, stem_part, self.sgrads["w"],
+                     self.sgrads["b"], self.B, S, S, co)
+
+    def set_canvas(self, canvas) -> None:
+        """The canvas the forward about to be differentiated read (None: the plan's own); the caller keeps it alive until the backward."""
+        if self.stem:
+            self.canvas_arg.value = self.own_canvas if canvas is None else canvas.data_ptr()
 
     def set_grads(self, dreg: torch.Tensor, dlogit: torch.Tensor) -> None:
         self.dreg, self.dlogit = dreg, dlogit
@@ -477,7 +478,7 @@ def trainable_parameters(m) -> List[Tuple[str, torch.nn.Parameter]]:
     depthwise conv and BN, the two SE convs, project conv and BN), then those of the last ``m.train_bifpn`` BiFPN cells
     in state_dict order (after ``set_train_bifpn("all")`` every cell's, the first cell's 24 conv and BN tensors among them), then
     head_parameters(m)."""
-    kb = getattr(m, "train_backbone", 0)
+    kb = getattr(m, "train_backbone", 0)   # (the trainer's tests pass models that have the heads only)
     allb = m.backbone_net.model._blocks if kb else ()
     blocks = [(f"backbone_net.model._blocks.{i}.{name}", p) for i in range(len(allb) - kb, len(allb)) for name, p in allb[i].named_parameters()]
     if getattr(m, "train_stem", False):   # set_train_trunk("all"): the stem's three tensors first (a block without an expand layer has 10, the others 13)
@@ -504,21 +505,15 @@ def cell_raw_grads(m, tr: HeadTrain) -> Dict[str, torch.Tensor]:
     for (j, node), g in tr.cgrads.items():
         sep, pre = getattr(m.bifpn[j], node), f"bifpn.{j}.{node}."
         out[pre + "depthwise_conv.conv.weight"] = g["dw"].permute(2, 0, 1)[:, None]
-        pw, bn = sep.pointwise_conv.conv, sep.bn
-        W, b = pw.weight.detach().reshape(pw.out_channels, pw.in_channels), pw.bias.detach()
-        dW, db, dgam, dbeta = fold_chain(W, b, bn.weight.detach(), bn.running_mean, bn.running_var, bn.eps, g["pw_w"].t(), g["pw_b"])
-        out[pre + "pointwise_conv.conv.weight"], out[pre + "pointwise_conv.conv.bias"] = dW[:, :, None, None], db
-        out[pre + "bn.weight"], out[pre + "bn.bias"] = dgam, dbeta.clone()
+        (out[pre + "pointwise_conv.conv.weight"], out[pre + "pointwise_conv.conv.bias"], out[pre + "bn.weight"],
+         out[pre + "bn.bias"]) = pw_raw_grads(sep.pointwise_conv.conv, sep.bn, g["pw_w"], g["pw_b"])
         wname = dict(zip(_BiFPN.NODES, _BiFPN.WEIGHTS))[node][0]
         p = getattr(m.bifpn[j], wname).detach()
         out[f"bifpn.{j}.{wname}"] = fusion_weight_grads(p, g["what"][:p.numel()])
     for key, g in tr.fgrads.items():   # the first cell's 1x1 layers: Sequential(conv, BN[, pool])
         seq, pre = getattr(m.bifpn[0], key), f"bifpn.0.{key}."
-        pw, bn = seq[0].conv, seq[1]
-        W, b = pw.weight.detach().reshape(pw.out_channels, pw.in_channels), pw.bias.detach()
-        dW, db, dgam, dbeta = fold_chain(W, b, bn.weight.detach(), bn.running_mean, bn.running_var, bn.eps, g["pw_w"].t(), g["pw_b"])
-        out[pre + "0.conv.weight"], out[pre + "0.conv.bias"] = dW[:, :, None, None], db
-        out[pre + "1.weight"], out[pre + "1.bias"] = dgam, dbeta.clone()
+        out[pre + "0.conv.weight"], out[pre + "0.conv.bias"], out[pre + "1.weight"], out[pre + "1.bias"] = \
+            pw_raw_grads(seq[0].conv, seq[1], g["pw_w"], g["pw_b"])
     return out
 
 
@@ -530,11 +525,8 @@ def block_raw_grads(m, tr: HeadTrain) -> Dict[str, torch.Tensor]:
         blk, pre = m.backbone_net.model._blocks[i], f"backbone_net.model._blocks.{i}."
         layers = [("_expand_conv", "_bn0", g["exp_w"], g["exp_b"])] if "exp_w" in g else []   # (a block without an expand layer)
         for conv, bn, gw, gb in layers + [("_project_conv", "_bn2", g["proj_w"], g["proj_b"])]:
-            pw, n = getattr(blk, conv).conv, getattr(blk, bn)
-            W = pw.weight.detach().reshape(pw.out_channels, pw.in_channels)
-            dW, _, dgam, dbeta = fold_chain(W, None, n.weight.detach(), n.running_mean, n.running_var, n.eps, gw.t(), gb)
-            out[pre + conv + ".conv.weight"] = dW[:, :, None, None]
-            out[pre + bn + ".weight"], out[pre + bn + ".bias"] = dgam, dbeta.clone()
+            out[pre + conv + ".conv.weight"], _, out[pre + bn + ".weight"], out[pre + bn + ".bias"] = \
+                pw_raw_grads(getattr(blk, conv).conv, getattr(blk, bn), gw, gb)
         n = blk._bn1
         dw, dgam, dbeta = dw_fold_chain(blk._depthwise_conv.conv.weight.detach()[:, 0], n.weight.detach(), n.running_mean, n.running_var,
                                         n.eps, g["dw"].permute(2, 0, 1), g["dw_b"])
@@ -558,18 +550,14 @@ def raw_grads(m, tr: HeadTrain) -> Dict[str, torch.Tensor]:
     for h in HEADS:
         hd, g = getattr(m, h), tr.grads[h]
         for i, cv in enumerate(hd.conv_list):
-            pre = f"{h}.conv_list.{i}."
+            pre, pw = f"{h}.conv_list.{i}.", cv.pointwise_conv.conv
             out[pre + "depthwise_conv.conv.weight"] = g["dw"][:, i].sum(0).permute(2, 0, 1)[:, None]
-            pw = cv.pointwise_conv.conv
-            W, b = pw.weight.detach().reshape(pw.out_channels, pw.in_channels), pw.bias.detach()
-            dW, db = torch.zeros_like(W), torch.zeros_like(b)
-            for lv in range(5):
-                bn = hd.bn_list[lv][i]
-                a, bb, dgam, dbeta = fold_chain(W, b, bn.weight.detach(), bn.running_mean, bn.running_var, bn.eps,
-                                                g["pw_w"][lv, i].t(), g["pw_b"][lv, i])
+            dW, db = torch.zeros_like(pw.weight), torch.zeros_like(pw.bias)
+            for lv in range(5):   # the conv is shared by the five levels, each with a BN of its own
+                a, bb, out[f"{h}.bn_list.{lv}.{i}.weight"], out[f"{h}.bn_list.{lv}.{i}.bias"] = \
+                    pw_raw_grads(pw, hd.bn_list[lv][i], g["pw_w"][lv, i], g["pw_b"][lv, i])
                 dW, db = dW + a, db + bb
-                out[f"{h}.bn_list.{lv}.{i}.weight"], out[f"{h}.bn_list.{lv}.{i}.bias"] = dgam, dbeta.clone()
-            out[pre + "pointwise_conv.conv.weight"], out[pre + "pointwise_conv.conv.bias"] = dW[:, :, None, None], db
+            out[pre + "pointwise_conv.conv.weight"], out[pre + "pointwise_conv.conv.bias"] = dW, db
         out[f"{h}.header.depthwise_conv.conv.weight"] = g["hdw"].sum(0).permute(2, 0, 1)[:, None]
         out[f"{h}.header.pointwise_conv.conv.weight"] = g["hpw_w"].sum(0).t()[:, :, None, None]
         out[f"{h}.header.pointwise_conv.conv.bias"] = g["hpw_b"].sum(0)

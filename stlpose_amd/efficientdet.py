@@ -35,7 +35,7 @@ from __future__ import annotations
 
 import ctypes
 import math
-from typing import Dict, List, Optional
+from typing import Dict, List, NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -372,6 +372,18 @@ def list_fuse(ops: LaunchList, code: int, out, terms, wparam):
     return f
 
 
+# What the training backward (detector_train) reads of the forward, as _Plan keeps it.  blocks[i], an MBConv block: its input, the
+# expand layer's output (None in a block without one), the depthwise layer's output, the squeeze-excitation gate [B, mid], its output;
+# cells[j][node], a BiFPN node: the fused map, the depthwise layer's output, the node's output, the listed DetFuse, the maps it fuses;
+# first_convs[name], one of the first cell's six 1x1 layers: the backbone map it reads, its output, its pack (w, bias, Kp, Np);
+# first_pools, the first cell's two plain pools in forward order: the listed DetFuse, input, output
+_T = torch.Tensor
+BlockMaps = NamedTuple("BlockMaps", [("inp", _T), ("e", Optional[_T]), ("a", _T), ("gate", _T), ("y", _T)])
+NodeMaps = NamedTuple("NodeMaps", [("f", _T), ("d", _T), ("y", _T), ("desc", ctypes.Structure), ("terms", List[_T])])
+FirstConv = NamedTuple("FirstConv", [("x", _T), ("y", _T), ("pk", tuple)])
+FirstPool = NamedTuple("FirstPool", [("desc", ctypes.Structure), ("x", _T), ("y", _T)])
+
+
 class _Plan:
     """Every launch of one forward at batch B on the 512 canvas, with its buffers: ``calls``, a LaunchList replayed by
     ``run``; ``canvas`` is the input, ``feats`` the five BiFPN outputs (NHWC), ``reg`` / ``cls`` the head outputs.  In a 16-bit
@@ -396,7 +408,7 @@ class _Plan:
         self._cost(2 * x.numel() * 27, 4 * self.canvas.numel() + self.es * x.numel())
         h = H
         feats, specs = [], net.specs
-        self.blocks = []   # per MBConv block (input, expand output e or None, depthwise output a, SE gate, output): the blocks' backward reads them
+        self.blocks: List[BlockMaps] = []   # per MBConv block: the blocks' backward reads them
         for i, (b, lay) in enumerate(zip(specs, L["blocks"])):
             if b["s"] == 2:   # the wrapper keeps the input of every stride-2 block (efficientdet_utils/model.py:413-414)
                 feats.append((x, h))
@@ -425,14 +437,14 @@ class _Plan:
                 self._cost(x.numel() + 4 * B * b["mid"] * b["se"], 4 * x.numel(), launches=2)
             y = self._buf(B, h, h, b["co"])
             self._pw(x, y, h * h, b["mid"], b["co"], lay["project"], act=0, in_scale=scale, residual=inp if b["skip"] else None)
-            self.blocks.append((inp, e, x, scale, y))
+            self.blocks.append(BlockMaps(inp, e, x, scale, y))
             x = y
         feats.append((x, h))
         p3, p4, p5 = feats[-3:]
         self.backbone = [f for f, _ in feats[-3:]]   # P3, P4, P5
         c = m.fpn_channels
         levels = None
-        self.cells = []   # per BiFPN cell {node: (fused map f, depthwise output d, node output, DetFuse, its term maps)}: the cells' backward reads them
+        self.cells: List[Dict[str, NodeMaps]] = []   # per BiFPN cell {node: its maps}: the cells' backward reads them
         for cell, lay in zip(m.bifpn, L["bifpn"]):
             levels = self._bifpn(cell, lay, levels, p3, p4, p5, c)
         self.feats = levels
@@ -511,15 +523,14 @@ class _Plan:
             h6, h7 = (h5 + 1) // 2, (h5 + 3) // 4
             p6 = self._buf(B, h6, h6, c)
             p7 = self._buf(B, h7, h7, c)
-            # what the first cell's backward reads: its two plain pools (DetFuse, input, output) in forward order and its six 1x1
-            # layers {name: (backbone map, output map, pack)}
-            self.first_pools = [(self._fuse(p6, [(t, 2)], None), t, p6), (self._fuse(p7, [(p6, 2)], None), p6, p7)]
-            self.first_convs = {"p5_to_p6": (x5, t, lay["p5_to_p6"])}
+            # what the first cell's backward reads: its two plain pools in forward order and its six 1x1 layers by name
+            self.first_pools = [FirstPool(self._fuse(p6, [(t, 2)], None), t, p6), FirstPool(self._fuse(p7, [(p6, 2)], None), p6, p7)]
+            self.first_convs = {"p5_to_p6": FirstConv(x5, t, lay["p5_to_p6"])}
             ins = []
             for (xx, hh), key in ((p3, "p3_down_channel"), (p4, "p4_down_channel"), (p5, "p5_down_channel")):
                 y = self._buf(B, hh, hh, c)
                 self._pw(xx, y, hh * hh, xx.shape[3], c, lay[key], act=0)
-                self.first_convs[key] = (xx, y, lay[key])
+                self.first_convs[key] = FirstConv(xx, y, lay[key])
                 ins.append(y)
             p3_in, p4_in, p5_in = ins
             p6_in, p7_in = p6, p7
@@ -534,7 +545,7 @@ class _Plan:
             f = self._buf(B, h, h, c)
             desc = self._fuse(f, terms, wp[wname])
             d, y = self._sep(f, lay[name], h, c)
-            kept[name] = (f, d, y, desc, [t for t, _ in terms])
+            kept[name] = NodeMaps(f, d, y, desc, [t for t, _ in terms])
             return y
         p6_up = node("conv6_up", "p6_w1", [(p6_in, 0), (p7_in, 1)], hs[3])
         p5_up = node("conv5_up", "p5_w1", [(p5_in, 0), (p6_up, 1)], hs[2])
@@ -545,7 +556,7 @@ class _Plan:
             for (xx, hh), key in ((p4, "p4_down_channel_2"), (p5, "p5_down_channel_2")):
                 y = self._buf(B, hh, hh, c)
                 self._pw(xx, y, hh * hh, xx.shape[3], c, lay[key], act=0)
-                self.first_convs[key] = (xx, y, lay[key])
+                self.first_convs[key] = FirstConv(xx, y, lay[key])
                 ins.append(y)
             p4_in, p5_in = ins
         p4_out = node("conv4_down", "p4_w2", [(p4_in, 0), (p4_up, 0), (p3_out, 2)], hs[1])

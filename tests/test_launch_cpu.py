@@ -1,6 +1,7 @@
 """CPU: ``stlpose_amd.launch.LaunchList`` -- how ``add`` converts and keeps its arguments, the error path of ``run`` (descriptors
 that fail the library's first host-side check: nothing is launched), slicing and selection -- and the launch plans of the
-Python-listed models against the signatures recorded before they moved onto it (tests/golden/launch/plans.json)."""
+Python-listed models against the signatures recorded before they moved onto it (tests/golden/launch/plans.json), and the detector's training lists at every depth, with the
+buffer behind each pointer, against those recorded before one builder per stage listed them (detector_train.json)."""
 import ctypes as C
 import json
 import os
@@ -107,3 +108,27 @@ def test_plans_are_the_recorded_ones(model, built_lib):
             assert not diff, f"{key}: arguments of entry {diff[0]} ({g['names'][diff[0]]}) changed"
         else:
             assert g == w, key
+
+
+def _detector_train_keys():
+    from tests import launch_plans
+    return list(launch_plans.DETECTOR_TRAIN)
+
+
+@pytest.mark.parametrize("key", _detector_train_keys())
+def test_detector_training_lists_are_the_recorded_ones(key, built_lib):
+    """The detector's training forward and backward at every depth (tests/launch_plans.py: DETECTOR_TRAIN) hold the same ordered
+    entry points with the same arguments as on the commit detector_train.json was recorded from, every pointer names the same
+    buffer with the same room behind it, and no pointer lies outside the tensors that the plan keeps (launch_plans.aliasing)."""
+    from tests import launch_plans
+    want = json.load(open(os.path.join(HERE, "golden", "launch", "detector_train.json")))["plans"][key]
+    got = launch_plans.detector_train(key)
+    assert set(got) == set(want) == {"fwd", "bwd"}
+    for which in ("fwd", "bwd"):
+        g, w = got[which], want[which]
+        for i, (gn, wn) in enumerate(zip(g["names"], w["names"])):
+            assert gn == wn, f"{key}: {which}[{i}] is {gn}, recorded {wn}"
+        assert len(g["names"]) == len(w["names"]), f"{key}: {which} has {len(g['names'])} entries, recorded {len(w['names'])}"
+        for i, name in enumerate(g["names"]):
+            assert g["crc"][i] == w["crc"][i], f"{key}: {which}[{i}] ({name}): its arguments changed"
+            assert g["alias"][i] == w["alias"][i], f"{key}: {which}[{i}] ({name}): a pointer names another buffer, or the room behind one changed"

@@ -80,7 +80,7 @@ def main(outdir, baseline=None):
             tr = plan.train
             # the blocks in eager torch: from the stored input of the first of them, against the native gradient of P5
             gp5 = tr.gp5.detach().clone().permute(0, 3, 1, 2).contiguous()
-            x_in = plan.blocks[blocks[0]][0].detach().permute(0, 3, 1, 2).contiguous()
+            x_in = plan.blocks[blocks[0]].inp.detach().permute(0, 3, 1, 2).contiguous()
             pre = tuple(f"{KR.PRE}{i}." for i in blocks)
             esd = {n: v.detach().clone() for n, v in m.state_dict().items() if n.startswith(pre) and v.is_floating_point()}
             for n, v in esd.items():

@@ -73,7 +73,7 @@ def main(outdir):
                 if k == "all":   # from the backbone's maps
                     ins = [f.permute(0, 3, 1, 2).contiguous() for f in p.backbone]
                 else:
-                    ins = [p.cells[n - k - 1][name][2].permute(0, 3, 1, 2).contiguous() for name in LEVEL_NODES]
+                    ins = [p.cells[n - k - 1][name].y.permute(0, 3, 1, 2).contiguous() for name in LEVEL_NODES]
                 esd = BR.train_state(m.state_dict(), cells, torch.float32)
                 esd = {name: v.detach().to(dev).requires_grad_(v.requires_grad) for name, v in esd.items()}
                 eopt = torch.optim.SGD([v for v in esd.values() if v.requires_grad], lr=1e-5)

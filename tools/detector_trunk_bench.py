@@ -49,11 +49,11 @@ def kernels_alone(specs, plan, B, ceiling, st):
     """The two new depthwise kernels at the largest (h_in^2 mid) of each (k, s)."""
     dev, lib, out = plan.dev, capi.lib(), []
     for k, s in ((3, 1), (3, 2), (5, 1), (5, 2)):
-        cand = [(plan.blocks[i][0].shape[1] ** 2 * b["mid"], i) for i, b in enumerate(specs) if (b["k"], b["s"]) == (k, s)]
+        cand = [(plan.blocks[i].inp.shape[1] ** 2 * b["mid"], i) for i, b in enumerate(specs) if (b["k"], b["s"]) == (k, s)]
         if not cand:
             continue
         _, i = max(cand)
-        h, c = plan.blocks[i][0].shape[1], specs[i]["mid"]
+        h, c = plan.blocks[i].inp.shape[1], specs[i]["mid"]
         ho = (h + s - 1) // s
         x, z, dx = (torch.randn(B, h, h, c, device=dev) for _ in range(3))
         dy, w, dw = torch.randn(B, ho, ho, c, device=dev), torch.randn(k, k, c, device=dev), torch.empty(k, k, c, device=dev)
@@ -128,7 +128,7 @@ def main(outdir, baseline=None, models=(0, 3), batches=(8, 32)):
             def eager_step():
                 eopt.zero_grad(set_to_none=True)
                 for i in range(nb - 1, -1, -1):   # one block's maps at a time
-                    UR.block_forward(esd, i, specs[i], nchw(plan.blocks[i][0])).backward(nchw(tr.block_dy[i]))
+                    UR.block_forward(esd, i, specs[i], nchw(plan.blocks[i].inp)).backward(nchw(tr.block_dy[i]))
                 UR.stem_forward(esd, canvas).backward(stem_dy)
                 eopt.step()
             trunk_bwd = LaunchList(tr.bwd.keep)
